@@ -23,7 +23,13 @@ and the other matchers of the path, measured on one GPU (rank 0, N = 1 only), un
   ndt_gicp   BASELINE config #5: registrators::NdtWithGicp, 120k scan vs 2M-pt submap
 Every timed pose is compared with the CPU oracle run on the same clouds and guess (`parity.*_vs_oracle`).
 
-  python bench.py                      # N=1, a few minutes (most of it the CPU oracle legs)
+A plain run measures the headline alone: it sets up, warms up, times `--steps` steps and prints the line (value, ms_per_step,
+config).  Everything else above -- the extra figures, the per-kernel roofline (HIP events in the timed region), the CPU baseline
+and parity legs, single_pair, other_workloads and end_to_end -- runs with `--full` only.  `--dump-outputs DIR` writes what the
+last timed step returned (poses, fitness scores, iterations of every pair) as DIR/<name>.npy.
+
+  python bench.py                      # N=1, the headline alone (~10 s of setup)
+  python bench.py --full               # N=1, every figure (a few minutes, most of it the CPU oracle legs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -57,11 +63,57 @@ def _device_id(torch, index: int) -> str:
     return f"{index}:{getattr(p, 'uuid', '')}:{getattr(p, 'pci_bus_id', '')}:{getattr(p, 'gcnArchName', p.name)}"
 
 
-def build_workload(n_distinct: int, n_points: int, device):
+def _host_threads() -> int:
+    """Worker threads for the host side of the set-up: the CPUs this process may run on, at most 16."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+def build_workload(n_distinct: int, n_points: int, device, threads: int | None = None):
     """`n_distinct` consecutive scan pairs (i, i + 1) of the synthetic drive; scan i prepared as pair i's target by
-    the caller-side CalculateNormals (builder/map_builder.cc:286,389)."""
-    from staticmapping_amd import synth
-    return synth.drive_pairs(n_distinct, n_points, device, seed=5)
+    the caller-side CalculateNormals (builder/map_builder.cc:286,389).  The same pairs as synth.drive_pairs(n_distinct,
+    n_points, device, seed=5), bit for bit (tests/test_bench_workload.py).  The scans are made one after the other on
+    this thread (ray casts made from several threads at once did not reproduce their scans); their CalculateNormals,
+    the library's host code and most of the time, runs on a pool of host threads meanwhile."""
+    from concurrent.futures import ThreadPoolExecutor
+    from staticmapping_amd import synth, _capi
+    from staticmapping_amd.matcher import calculate_normals
+    _capi.load_library()
+    seed = 5
+    poses = synth.drive_poses(n_distinct + 2, seed=seed, speed=8.0, speed_spread=2.0, yaw_rate_max=0.2, segment_s=1.0)
+    scene = synth.make_drive_scene(poses, seed=seed)
+    scans, normals = [], []
+    with ThreadPoolExecutor(threads or _host_threads()) as ex:
+        for k, P in enumerate(poses[1:n_distinct + 2]):      # scan k is taken at poses[k + 1]; scans 0 .. n_distinct - 1 are targets too
+            scans.append(synth.velodyne_scan(synth.scene_near(scene, P[:3, 3]), P, seed=500 + k, n_points=n_points, device=device))
+            if k < n_distinct:
+                normals.append(ex.submit(calculate_normals, scans[k][:, :3].astype(np.float64)))
+        normals = [f.result() for f in normals]
+    rel = [np.linalg.inv(poses[k]) @ poses[k + 1] for k in range(len(poses) - 1)]     # rel[k]: scan k+1 -> scan k
+    pairs = []
+    for k in range(n_distinct):
+        q, n = normals[k]
+        pairs.append(dict(src=scans[k + 1], q=q, n=n, T=rel[k + 1], guess_cv=rel[k], guess_id=np.eye(4)))
+    return pairs
+
+
+def dump_outputs(dirname: str, T, scores, iterations, max_bytes: int = 64 << 20):
+    """What the timed path returned in its last step, every pair of every rank in global pair order, as DIR/<name>.npy:
+    poses [n, 4, 4], fitness_scores [n], iterations [n] and pair_index [n] (the pairs' global indices), all float64.
+    Beyond `max_bytes` a fixed, seeded sample of the pairs is written."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(T)
+    idx = np.arange(n)
+    row_bytes = 8 * (16 + 1 + 1 + 1)
+    if n * row_bytes > max_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=max_bytes // row_bytes, replace=False))
+    arrays = {"poses": np.asarray(T, dtype=np.float64)[idx], "fitness_scores": np.asarray(scores, dtype=np.float64)[idx],
+              "iterations": np.asarray(iterations, dtype=np.float64)[idx], "pair_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def oracle_pose(w, guess, max_iteration, early_exit, nthreads=1, nn_eps=None):
@@ -81,7 +133,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=512, help="scan pairs per GPU per step")
     ap.add_argument("--distinct", type=int, default=512, help="distinct synthetic scan pairs (cycled over the slots; each slot uploaded).  Default: every "
-                    "slot of the default batch holds a pair of its own (513 scans of the synthetic drive, ~25 s to generate and prepare)")
+                    "slot of the default batch holds a pair of its own (513 scans of the synthetic drive, made on up to 16 host threads)")
     ap.add_argument("--points", type=int, default=N_POINTS)
     ap.add_argument("--nn-mode", choices=["grid", "brute"], default="grid")
     ap.add_argument("--cell", type=float, default=0.25)
@@ -90,11 +142,15 @@ def main():
     ap.add_argument("--ball-radius", type=float, default=0.0, help="smhip_icp_options.ball_radius: first-iteration search radius (0 = the library's default, 0.3 m)")
     ap.add_argument("--streams", type=int, default=0, help="smhip_icp_options.overlap_streams: parts a batch is split into (0 = the library's default, 2)")
     ap.add_argument("--headline", choices=["identity", "extrapolated"], default="extrapolated")
-    ap.add_argument("--cpu-pairs", type=int, default=0, help="oracle / cpu_baseline sample: distinct pairs run on the host (0 = the first 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (no parity-vs-oracle either)")
-    ap.add_argument("--no-figures", action="store_true", help="skip the extra figures")
-    ap.add_argument("--no-other", action="store_true", help="skip other_workloads (NDT / NdtWithGicp), single_pair and end_to_end")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the end_to_end leg (generated drive through the C++ sequence driver)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: extra figures, per-kernel roofline (HIP events in the "
+                    "timed region), CPU baseline and parity legs, single_pair, other_workloads, end_to_end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the poses, fitness scores and iterations the last timed step "
+                    "returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-pairs", type=int, default=0, help="--full: oracle / cpu_baseline sample: distinct pairs run on the host (0 = the first 64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle legs (no parity-vs-oracle either)")
+    ap.add_argument("--no-figures", action="store_true", help="--full: skip the extra figures")
+    ap.add_argument("--no-other", action="store_true", help="--full: skip other_workloads (NDT / NdtWithGicp), single_pair and end_to_end")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the end_to_end leg (generated drive through the C++ sequence driver)")
     args = ap.parse_args()
 
     import torch
@@ -147,6 +203,7 @@ def main():
     n_total = B * world
     t_gen = time.perf_counter()
     work = build_workload(args.distinct, args.points, dev)
+    torch.cuda.empty_cache()         # the ray casts' temporaries
     t_gen = time.perf_counter() - t_gen
     D = len(work)
     ns = max(len(w["src"]) for w in work)
@@ -210,7 +267,8 @@ def main():
         else:
             prof = None
         T_all, sc_all, it_all = shard.unpack_pose_rows(gathered)
-        return dict(elapsed=elapsed, value=n_total * steps / elapsed, T=T_all, it=it_all, stats=stats, prof=prof, guesses=guesses, split=split)
+        return dict(elapsed=elapsed, value=n_total * steps / elapsed, T=T_all, scores=sc_all, it=it_all, stats=stats, prof=prof, guesses=guesses,
+                    split=split)
 
     def truth_errors(T_all):
         worst_rot = worst_t = 0.0
@@ -226,33 +284,62 @@ def main():
 
     head_key = "guess_id" if args.headline == "identity" else "guess_cv"
     other_key = "guess_cv" if args.headline == "identity" else "guess_id"
-    # Which kernel class does this workload spend the most time in?  One untimed step with events around every launch (after a
-    # plain one, so that the library has placed the search-form switch from a batch of these guesses); the timed region then
-    # carries events around that class only -- every bracket is a barrier between two launches, and bracketing all classes
-    # took 6 % off the batch rate.
-    guesses0 = [work[g % D][head_key] for g in mine]
-    m.enqueue_batch(B, guesses0); m.fetch_batch(B)
-    m.enable_profile(True)
-    m.enqueue_batch(B, guesses0); m.fetch_batch(B)
-    pre = m.get_profile()
-    m.enable_profile(False)
-    # the class of the single kernel with the largest summed time
-    single = {"nn_main": pre["ms_nn_main"], "nn_certify": pre["ms_nn_certify"], "accumulate": pre["ms_error_elements"], "nn_listed": pre["ms_nn_listed"]}
-    dom_single = max(single, key=lambda k: single[k])
-    prof_class = {"nn_main": 2, "nn_certify": 2, "accumulate": 3, "nn_listed": 4}[dom_single]
-    if world > 1:      # every rank must time the same thing
-        t = torch.tensor([prof_class], dtype=torch.int32, device=coll_dev)
-        dist.broadcast(t, 0)
-        prof_class = int(t.item())
+    prof_class = 0                   # a plain run: no HIP events in the timed region
+    if args.full:
+        # Which kernel class does this workload spend the most time in?  One untimed step with events around every launch (after a
+        # plain one, so that the library has placed the search-form switch from a batch of these guesses); the timed region then
+        # carries events around that class only -- every bracket is a barrier between two launches, and bracketing all classes
+        # took 6 % off the batch rate.
+        guesses0 = [work[g % D][head_key] for g in mine]
+        m.enqueue_batch(B, guesses0); m.fetch_batch(B)
+        m.enable_profile(True)
+        m.enqueue_batch(B, guesses0); m.fetch_batch(B)
+        pre = m.get_profile()
+        m.enable_profile(False)
+        # the class of the single kernel with the largest summed time
+        single = {"nn_main": pre["ms_nn_main"], "nn_certify": pre["ms_nn_certify"], "accumulate": pre["ms_error_elements"], "nn_listed": pre["ms_nn_listed"]}
+        dom_single = max(single, key=lambda k: single[k])
+        prof_class = {"nn_main": 2, "nn_certify": 2, "accumulate": 3, "nn_listed": 4}[dom_single]
+        if world > 1:      # every rank must time the same thing
+            t = torch.tensor([prof_class], dtype=torch.int32, device=coll_dev)
+            dist.broadcast(t, 0)
+            prof_class = int(t.item())
     head = timed_run(head_key, args.steps, args.warmup, profile_nn=prof_class)
+    assert int(head["it"].min()) == ICP_ITERS == int(head["it"].max()), "a pair did not run exactly 20 iterations"
+    elapsed, value, nn_prof = head["elapsed"], head["value"], head["prof"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["T"], head["scores"], head["it"])
+    line = {
+        "metric": "scan-pair alignments/sec (120k-pt KITTI-64, 20 ICP iters)",
+        "value": round(value, 2), "unit": "alignments/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/f64",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE config #2: IcpFast point-to-plane, 120k-pt synthetic Velodyne-64 scan pair "
+                               f"vs CalculateNormals target (~{int(nt_mean)} pts), exactly 20 iterations, rho 0.7; {D} distinct consecutive "
+                               f"pairs of a synthetic drive (speed 6-10 m/s, yaw rate +-0.2 rad/s, seed 5), guess = "
+                               + ("identity (SURVEY cfg 2 / cfg 4)" if args.headline == "identity" else "previous pair's motion"),
+                   "pairs_per_gpu": B, "global_pairs_per_step": n_total, "distinct_pairs": D, "source_points": ns,
+                   "target_points_mean": int(nt_mean), "iterations": ICP_ITERS, "nn_mode": args.nn_mode,
+                   "grid_cell_m": args.cell, "guess": args.headline, "split_after": head["split"],
+                   "parallelism": f"pairs round-robin over {world} GPU(s), one RCCL gather of poses",
+                   "rccl_ranks": coll["ranks_in_all_reduce"], "collective_backend": coll["backend"], "rank_devices": coll["devices"]},
+        "workload_generation_s": round(t_gen, 1),
+    }
+    if not args.full:
+        m.close()
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        return
     by_rank = [(rank, prof_class, int(head["split"]))]
     if world > 1:       # what every rank timed: the same kernel class (broadcast above) and where its library placed the search-form switch
         got = [None] * world
         dist.all_gather_object(got, by_rank[0])
         by_rank = sorted(got)
         assert len({c for _, c, _ in by_rank}) == 1, by_rank
-    assert int(head["it"].min()) == ICP_ITERS == int(head["it"].max()), "a pair did not run exactly 20 iterations"
-    elapsed, value, nn_prof = head["elapsed"], head["value"], head["prof"]
     h_rot, h_t, h_med = truth_errors(head["T"])
 
     out = None
@@ -416,21 +503,8 @@ def main():
         traffic = traffic_of(dom, pairs_per_launch)
         alg_bytes = algorithmic_bytes_per_alignment(ns, nt_mean)
         out = {
-            "metric": "scan-pair alignments/sec (120k-pt KITTI-64, 20 ICP iters)",
-            "value": round(value, 2), "unit": "alignments/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE config #2: IcpFast point-to-plane, 120k-pt synthetic Velodyne-64 scan pair "
-                                   f"vs CalculateNormals target (~{int(nt_mean)} pts), exactly 20 iterations, rho 0.7; {D} distinct consecutive "
-                                   f"pairs of a synthetic drive (speed 6-10 m/s, yaw rate +-0.2 rad/s, seed 5), guess = "
-                                   + ("identity (SURVEY cfg 2 / cfg 4)" if args.headline == "identity" else "previous pair's motion"),
-                       "pairs_per_gpu": B, "global_pairs_per_step": n_total, "distinct_pairs": D, "source_points": ns,
-                       "target_points_mean": int(nt_mean), "iterations": ICP_ITERS, "nn_mode": args.nn_mode,
-                       "grid_cell_m": args.cell, "guess": args.headline, "split_after": head["split"],
-                       "parallelism": f"pairs round-robin over {world} GPU(s), one RCCL gather of poses",
-                       "rccl_ranks": coll["ranks_in_all_reduce"], "collective_backend": coll["backend"], "rank_devices": coll["devices"],
-                       "split_after_by_rank": [sp for _, _, sp in by_rank], "profiled_class_by_rank": [c for _, c, _ in by_rank]},
+            **line,
+            "config": dict(line["config"], split_after_by_rank=[sp for _, _, sp in by_rank], profiled_class_by_rank=[c for _, c, _ in by_rank]),
             "roofline": {"bound": "hbm", "kernel": dom,
                          "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
@@ -472,7 +546,6 @@ def main():
             "kernel_ms_per_step": {k: round(v, 3) for k, v in prof.items() if k.startswith("ms_")},
             "profiled_class": {2: "nn kernels (fused search, certificate pass)", 3: "accumulate", 4: "listed search"}[prof_class],
             "parity": {"worst_rot_err_vs_truth_rad": h_rot, "worst_trans_err_vs_truth_m": h_t, "median_trans_err_vs_truth_m": h_med},
-            "workload_generation_s": round(t_gen, 1),
         }
         if not args.no_cpu_baseline and rank == 0:     # (the CPU oracle legs: rank 0 alone, the other ranks wait at the final barrier)
             cpu, par = cpu_baseline_and_parity(work, figures, head, head_key, args.cpu_pairs or min(D, 64), world)

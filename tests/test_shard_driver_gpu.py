@@ -114,7 +114,7 @@ def test_bench_runs_its_multi_rank_sequence_to_the_end(tmp_path):
     env = dict(os.environ, SMHIP_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--pairs", "32", "--distinct", "8", "--cpu-pairs", "2"],
+                        "--pairs", "32", "--distinct", "8", "--cpu-pairs", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

@@ -7,9 +7,9 @@ out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 t0=$SECONDS
-python bench.py > "$out/bench_line.json" 2> "$out/bench.err"
-echo "default bench.py run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err"
+python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"
+echo "bench.py --full run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --full --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err"
 find "$out/trace" -name '*kernel_stats.csv' -exec cp {} "$out/bench_kernel_stats.csv" \;
 # trace averages over the launches of the timed region only: 4 untimed steps first (one plain and one fully profiled step that pick
 # the kernel class to bracket, 2 warm-up steps), then 5 timed steps; per step 4 launches of nn_ball_lds (iterations 0-1 x 2 halves)

@@ -9,9 +9,9 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
 t0=$SECONDS
-timeout -k 5 480 python bench.py > "$out/bench_line.json" 2> "$out/bench.err" < /dev/null
-echo "default bench.py run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
-timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err" < /dev/null
+timeout -k 5 480 python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err" < /dev/null
+echo "bench.py --full run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
+timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --full --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err" < /dev/null
 f=$(find "$out/trace" -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp "$f" "$out/bench_kernel_stats.csv"
 # trace averages over the launches of the timed region only: 4 untimed steps first, then 5 timed steps; a 512-pair step runs as

@@ -18,9 +18,9 @@ if want tests; then
 fi
 if want bench; then
   t0=$SECONDS
-  timeout -k 5 900 python bench.py > "$out/bench_line.json" 2> "$out/bench.err" < /dev/null
-  echo "default bench.py run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
-  timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err" < /dev/null
+  timeout -k 5 900 python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err" < /dev/null
+  echo "bench.py --full run: $((SECONDS - t0)) s wall" > "$out/bench_wall.txt"
+  timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --full --no-cpu-baseline --no-end-to-end --no-other > "$out/bench_line_traced.json" 2> "$out/trace.err" < /dev/null
   f=$(find "$out/trace" -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && grep -v "at::native" "$f" | cut -c1-400 > "$out/bench_kernel_stats.csv"
   # trace averages over the launches of the timed region only (4 untimed steps first, then 5 timed steps; 2 parts of 256 pairs per step)
