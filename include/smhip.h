@@ -471,6 +471,15 @@ void smhip_mrvm_set_offset_z(smhip_mrvm_handle h, float offset);                
  * Applied with a warning (status OK, text in smhip_mrvm_last_error): points beyond +-2^20 voxels are skipped (their number:
  * smhip_mrvm_last_skipped; the flag does not carry over to the next insert), a table > 70 % full that cannot grow. */
 smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3]);
+/* ApplyTransformToOutput(pose) + InsertPointCloud(cloud, pose translation), map_builder.cc:842-848: n raw rows of `stride_floats`
+ * floats (4: KITTI x y z reflectance, factor = 0; 5: InnerPointType) go up as they are, and a kernel writes the world-frame rows
+ * with the reference's TransformPoint (builder/data/cloud_types.cc:167-178): the matrix cast to float, x' = ((m00 x + m01 y) +
+ * m02 z) + m03 with every product and sum rounded to float (no fused multiply-add, as the reference's -O2 build without -march);
+ * intensity = row[3] * intensity_scale in float (255 for raw KITTI rows, kitti_reader.cc:113).  pose: column-major 4x4; origin =
+ * its translation cast to float.  Refused before the map is touched: a non-finite pose, a stride other than 4 or 5, and
+ * everything smhip_mrvm_insert_f32 refuses; warnings as there. */
+smhip_status smhip_mrvm_insert_transformed_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                               float intensity_scale);
 smhip_status smhip_mrvm_last_skipped(smhip_mrvm_handle h, int* n);
 smhip_status smhip_mrvm_voxel_count(smhip_mrvm_handle h, int* n);
 smhip_status smhip_mrvm_set_max_table_log2(smhip_mrvm_handle h, int max_table_log2);   /* 10..28; default 28 */
@@ -487,6 +496,11 @@ smhip_status smhip_mrvm_output(smhip_mrvm_handle h, float threshold, float* xyzi
  * constructor puts there). */
 #define SMHIP_MRVM_AVERAGE 1
 #define SMHIP_MRVM_RGB 2
+/* SMHIP_MRVM_SORTED (combinable with the two above): rows ordered by the packed voxel key ascending -- x, then y, then z of the
+ * voxel, each as a signed integer -- and within a voxel in stored-point order; the order is computed on the device (a radix sort
+ * of the voxels by key and an exclusive scan of their row counts), so the same map gives the same rows on every call and run.
+ * Without it the rows come in table order, as before. */
+#define SMHIP_MRVM_SORTED 4
 smhip_status smhip_mrvm_output_ex(smhip_mrvm_handle h, float threshold, int flags, float* rows, int capacity, int* n_out);
 /* parity-test hook: every voxel of the map -- key (3 ints), probability byte, max intensity, number of stored points and
  * the points themselves (max_point_num_in_cell x 5 floats per voxel), in no particular order */

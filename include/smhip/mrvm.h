@@ -1,15 +1,19 @@
 // smhip/mrvm.h -- C++ mirror of static_map::MultiResolutionVoxelMap (/root/reference/builder/multi_resolution_voxel_map.h:67-131)
 // over the device implementation in libsmhip.so: same settings struct, same three calls the map builder makes
-// (builder/map_builder.cc:832-900): Initialise, InsertPointCloud(cloud, origin), OutputToPointCloud(threshold, cloud).
+// (builder/map_builder.cc:832-900): Initialise, InsertPointCloud(cloud, origin), OutputToPointCloud(threshold, cloud), plus what
+// SaveMaps adds around them: InsertPointCloud(cloud, pose) = ApplyTransformToOutput(pose) + insert on the device, and
+// OutputToPointCloud(threshold, filename) = the map as a PCD file (smhip/pcd.h), rows in voxel-key order.
 // Header-only; link with -lsmhip.
 #ifndef SMHIP_MRVM_H_
 #define SMHIP_MRVM_H_
 
 #include <cstdio>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../smhip.h"
+#include "pcd.h"
 #include "registrator.h"
 
 namespace smhip {
@@ -63,11 +67,33 @@ class MultiResolutionVoxelMapHip {
     if (cloud.empty()) { std::fprintf(stderr, "[ERROR] cloud is empty.\n"); return false; }   // PRINT_ERROR + return, :61-64
     SMHIP_CHECK(handle_ != nullptr, "InsertPointCloud before Initialise");
     static_assert(sizeof(data::InnerPointType) == 5 * sizeof(float), "InnerPointType is five floats");
-    const smhip_status st = smhip_mrvm_insert_f32(handle_, &cloud[0].x, 5, static_cast<int>(cloud.size()), origin);
-    if (st != SMHIP_OK) { std::fprintf(stderr, "[ERROR] MultiResolutionVoxelMapHip::InsertPointCloud: %s\n", smhip_mrvm_last_error(handle_)); return false; }
-    // applied, with something to say (points beyond the coordinate range skipped, table filling up): the reference has neither limit
-    if (smhip_mrvm_last_error(handle_)[0]) std::fprintf(stderr, "[WARNING] MultiResolutionVoxelMapHip::InsertPointCloud: %s\n", smhip_mrvm_last_error(handle_));
-    return true;
+    return Reported(smhip_mrvm_insert_f32(handle_, &cloud[0].x, 5, static_cast<int>(cloud.size()), origin));
+  }
+  // map_builder.cc:842-848: the frame's cloud as ApplyTransformToOutput(pose) leaves it (TransformPoint, the pose cast to float, no
+  // fused multiply-add), inserted with origin = the pose's translation cast to float -- the transform runs on the device.  rows:
+  // n x stride_floats (4: KITTI x y z reflectance, factor 0; 5: InnerPointType); intensity = row[3] * intensity_scale (255 for
+  // raw KITTI rows).  false: the device refused the cloud (printed).
+  bool InsertPointCloud(const float* rows, int stride_floats, int n, const registrator::Matrix4d& pose, float intensity_scale = 1.f) {
+    if (n <= 0 || rows == nullptr) { std::fprintf(stderr, "[ERROR] cloud is empty.\n"); return false; }
+    SMHIP_CHECK(handle_ != nullptr, "InsertPointCloud before Initialise");
+    const smhip_status st = smhip_mrvm_insert_transformed_f32(handle_, rows, stride_floats, n, pose.data(), intensity_scale);
+    return Reported(st);
+  }
+  bool InsertPointCloud(const InnerCloud& cloud, const registrator::Matrix4d& pose) {
+    static_assert(sizeof(data::InnerPointType) == 5 * sizeof(float), "InnerPointType is five floats");
+    if (cloud.empty()) { std::fprintf(stderr, "[ERROR] cloud is empty.\n"); return false; }
+    return InsertPointCloud(&cloud[0].x, 5, static_cast<int>(cloud.size()), pose, 1.f);
+  }
+  // .cc:217-242: the map as a PCD file, PointXYZRGB with settings_.output_rgb, else PointXYZI, one averaged point per voxel with
+  // settings_.output_average.  Rows in voxel-key order (SMHIP_MRVM_SORTED): the same map gives the same file.  compress (the
+  // reference's binary_compressed) is not supported: the file is DATA binary either way.  false: nothing written (an empty map
+  // -- the reference's warning -- or an error).
+  bool OutputToPointCloud(const float threshold, const std::string& filename, bool compress = false) {
+    if (compress) std::fprintf(stderr, "[WARNING] binary_compressed PCD is not supported: writing DATA binary.\n");
+    const int flags = SMHIP_MRVM_SORTED | (settings_.output_rgb ? SMHIP_MRVM_RGB : 0) | (settings_.output_average ? SMHIP_MRVM_AVERAGE : 0);
+    std::vector<PointXYZI> rows;                   // (PointXYZRGB has the same 16 bytes: the 4th float holds the packed colour)
+    Output(threshold, flags, &rows);
+    return pcd::SaveBinary(filename, rows.empty() ? nullptr : &rows[0].x, rows.size(), settings_.output_rgb);
   }
   // .cc:125-170 (PointXYZI; one averaged point per voxel with settings_.output_average)
   void OutputToPointCloud(const float threshold, std::vector<PointXYZI>* cloud) {
@@ -82,6 +108,12 @@ class MultiResolutionVoxelMapHip {
   int VoxelCount() const { int n = 0; if (handle_) smhip_mrvm_voxel_count(handle_, &n); return n; }
 
  private:
+  bool Reported(smhip_status st) {
+    if (st != SMHIP_OK) { std::fprintf(stderr, "[ERROR] MultiResolutionVoxelMapHip::InsertPointCloud: %s\n", smhip_mrvm_last_error(handle_)); return false; }
+    // applied, with something to say (points beyond the coordinate range skipped, table filling up): the reference has neither limit
+    if (smhip_mrvm_last_error(handle_)[0]) std::fprintf(stderr, "[WARNING] MultiResolutionVoxelMapHip::InsertPointCloud: %s\n", smhip_mrvm_last_error(handle_));
+    return true;
+  }
   template <typename P>
   void Output(const float threshold, int flags, std::vector<P>* cloud) {
     SMHIP_CHECK(cloud != nullptr && handle_ != nullptr, "OutputToPointCloud: null cloud / not initialised");

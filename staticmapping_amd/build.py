@@ -40,7 +40,8 @@ def needs_build() -> bool:
 def build_shard_driver(force: bool = False, verbose: bool = False) -> str:
     """The C++ host program of BASELINE config #4: links libsmhip.so + librccl.so (no device code of its own)."""
     src = os.path.join(CSRC, "shard_driver.cc")
-    deps = [src, os.path.join(ROOT, "include", "smhip.h"), LIB_PATH]
+    deps = [src, os.path.join(ROOT, "include", "smhip.h"), os.path.join(ROOT, "include", "smhip", "kitti_scans.h"),
+            os.path.join(ROOT, "include", "smhip", "pcd.h"), LIB_PATH]
     if not force and os.path.exists(SHARD_EXE) and all(os.path.getmtime(d) <= os.path.getmtime(SHARD_EXE) for d in deps):
         return SHARD_EXE
     cmd = [_hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", SHARD_EXE,

@@ -14,6 +14,13 @@
 // rank 0 to the others through a small file (--id-file, default under /tmp): no MPI, no sockets of our own.
 // All arithmetic happens behind the C ABI of include/smhip.h; the gather is ncclAllGather on the doubles
 // smhip_icp_export_results_device leaves in device memory -- the poses never visit the host before the collective.
+//
+// --map PATH: the static map of MapBuilder::SaveMaps (builder/map_builder.cc:825-910).  Once kitti_pose.txt is written and the
+// matchers are gone, rank 0 reads the scans again in order and inserts frame k under pose k into one device
+// MultiResolutionVoxelMap (ApplyTransformToOutput on the device, origin = the pose's translation), then writes PATH as a PCD
+// file with rows in voxel-key order.  The poses are the ones AS WRITTEN to the pose file (8 significant digits, parsed back),
+// so the map is a function of that file: --map-poses FILE builds the same map, byte for byte, with no alignment, no RCCL and
+// one process -- also from poses that came from elsewhere.
 #include <dirent.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -24,7 +31,9 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <cstdarg>
 #include <chrono>
 #include <condition_variable>
 #include <cmath>
@@ -39,6 +48,7 @@
 
 #include "../../include/smhip.h"
 #include "../../include/smhip/kitti_scans.h"
+#include "../../include/smhip/pcd.h"
 
 namespace {
 
@@ -53,6 +63,11 @@ struct Args {
   int batch = 256, iterations = 20, early_exit = 0, max_pairs = -1, readers = 8, matchers = 1, warmup = 1, parts = 0;
   double guess_tx = 0.0;
   bool quiet = false;
+  // the static map (--map); the MRVM settings are MrvmSettings' (multi_resolution_voxel_map.h:54-65), whose defaults these are
+  std::string map_path, map_poses;
+  int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
+  float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
+  bool map_average = false, map_rgb = false;
 };
 
 [[noreturn]] void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -103,10 +118,30 @@ Args Parse(int argc, char** argv) {
     else if (k == "--parts") a.parts = std::atoi(val().c_str());
     else if (k == "--guess-tx") a.guess_tx = std::atof(val().c_str());
     else if (k == "--quiet") a.quiet = true;
+    else if (k == "--map") a.map_path = val();
+    else if (k == "--map-poses") a.map_poses = val();
+    else if (k == "--map-every") a.map_every = std::atoi(val().c_str());
+    else if (k == "--map-part-every") a.map_part_every = std::atoi(val().c_str());
+    else if (k == "--map-resolution") a.map_resolution = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--map-threshold") a.map_threshold = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--map-hit") a.map_hit = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--map-miss") a.map_miss = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--map-points-per-cell") a.map_points_per_cell = std::atoi(val().c_str());
+    else if (k == "--map-z-offset") a.map_z_offset = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--map-average") a.map_average = true;
+    else if (k == "--map-rgb") a.map_rgb = true;
+    else if (k == "--map-max-table-log2") a.map_max_table_log2 = std::atoi(val().c_str());
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
-             "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]");
+             "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
+             "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
+             "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
+             "[--map-max-table-log2 28]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
+  if (!a.map_poses.empty() && a.map_path.empty()) Die("--map-poses needs --map PATH");
+  if (a.map_every < 1 || a.map_part_every < 0 || a.map_points_per_cell < 1 || a.map_max_table_log2 < 10 || a.map_max_table_log2 > 28 ||
+      !(a.map_resolution > 0.f))
+    Die("bad map setting (--map-every >= 1, --map-part-every >= 0, --map-points-per-cell >= 1, --map-max-table-log2 10..28, --map-resolution > 0)");
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
   if (a.world < 0 && std::getenv("WORLD_SIZE")) a.world = std::atoi(std::getenv("WORLD_SIZE"));
   if (a.local_rank < 0 && std::getenv("LOCAL_RANK")) a.local_rank = std::atoi(std::getenv("LOCAL_RANK"));
@@ -149,6 +184,158 @@ ncclUniqueId ExchangeId(const Args& a, int rank) {
     usleep(10000);
   }
   Die("timed out waiting for " + a.id_file + " (no file with this run's nonce appeared)");
+}
+
+std::string Fmt(const char* fmt, ...) {
+  va_list ap, aq;
+  va_start(ap, fmt);
+  va_copy(aq, ap);
+  const int n = std::vsnprintf(nullptr, 0, fmt, ap);
+  va_end(ap);
+  std::string out(static_cast<size_t>(std::max(n, 0)) + 1, '\0');
+  std::vsnprintf(&out[0], out.size(), fmt, aq);
+  va_end(aq);
+  out.resize(static_cast<size_t>(std::max(n, 0)));
+  return out;
+}
+
+// kitti_pose.txt (map_builder.cc:626-641): 12 numbers per line, the row-major top 3x4 -> column-major 4x4.  Reading stops at the
+// first line that does not hold 12 numbers.  false: the file cannot be opened.
+using Pose = std::array<double, 16>;
+bool ReadPoses(const std::string& path, std::vector<Pose>* poses) {
+  std::ifstream f(path);
+  if (!f) return false;
+  std::string text;
+  while (std::getline(f, text)) {
+    double v[12];
+    const char* p = text.c_str();
+    int got = 0;
+    for (; got < 12; ++got) {
+      char* end = nullptr;
+      v[got] = std::strtod(p, &end);
+      if (end == p) break;
+      p = end;
+    }
+    if (got < 12) break;
+    Pose m{};
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m[4 * c + r] = v[4 * r + c];
+    m[15] = 1.0;
+    poses->push_back(m);
+  }
+  return true;
+}
+
+// the frames --map inserts: 0, K, 2K, ... below n_frames (--map-every K stands in for the reference's key-frame selection)
+std::vector<int> MapFrames(const Args& a, int n_frames) {
+  std::vector<int> v;
+  for (int k = 0; k < n_frames; k += a.map_every) v.push_back(k);
+  return v;
+}
+
+struct MapResult { int frames = 0, parts = 0; long long voxels = 0, points = 0; double seconds = 0.0; };
+
+std::string MapJsonFields(const Args& a, const MapResult& m) {
+  return Fmt(", \"map_file\": \"%s\", \"map_frames\": %d, \"map_voxels\": %lld, \"map_points\": %lld, \"map_parts\": %d, \"map_seconds\": %.4f, "
+             "\"map_ms_per_frame\": %.3f", a.map_path.c_str(), m.frames, m.voxels, m.points, m.parts, m.seconds,
+             m.frames > 0 ? 1e3 * m.seconds / m.frames : 0.0);
+}
+
+// SaveMaps (map_builder.cc:825-910) over `frames`: frame k's raw rows (intensity x 255, kitti_reader.cc:113) inserted under
+// poses[k] into one device map.  --map-part-every N writes <stem>_part_<i>.pcd after every N inserted frames and starts a fresh
+// map (separate_output / separate_step, :860-890, counted in frames rather than submaps); otherwise the whole map goes to --map
+// PATH.  Every file has its rows in voxel-key order (SMHIP_MRVM_SORTED).  Returns 0, or 3 when the map refused a frame: the
+// files of this run are then removed.  map_voxels / map_points are summed over the parts.
+int BuildMap(const Args& a, const std::vector<std::string>& files, const std::vector<int>& frames, const std::vector<Pose>& poses, int device,
+             MapResult* res) {
+  const auto t0 = std::chrono::steady_clock::now();
+  size_t max_bytes = 16;
+  for (int k : frames) { struct stat sb; if (stat(files[k].c_str(), &sb) == 0) max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
+  smhip_mrvm_settings set;
+  smhip_mrvm_default_settings(&set);
+  set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution; set.hit_prob = a.map_hit; set.miss_prob = a.map_miss;
+  set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
+  const int flags = SMHIP_MRVM_SORTED | (a.map_average ? SMHIP_MRVM_AVERAGE : 0) | (a.map_rgb ? SMHIP_MRVM_RGB : 0);
+  std::string stem = a.map_path;
+  if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".pcd") == 0) stem.resize(stem.size() - 4);
+  std::vector<std::string> written;
+  smhip_mrvm_handle h = nullptr;
+  auto fresh_map = [&]() {
+    if (h) smhip_mrvm_destroy(h);
+    h = nullptr;
+    const smhip_status st = smhip_mrvm_create(device, std::min(22, a.map_max_table_log2), static_cast<int>(slot_floats / 4), &set, &h);
+    if (st != SMHIP_OK) Die(std::string("smhip_mrvm_create: ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
+    if (smhip_mrvm_set_max_table_log2(h, a.map_max_table_log2) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+  };
+  auto write_map = [&](const std::string& path) {     // OutputToPointCloud(threshold, filename), multi_resolution_voxel_map.cc:217-242
+    int v = 0, n = 0, m = 0;
+    if (smhip_mrvm_voxel_count(h, &v) != SMHIP_OK || smhip_mrvm_output_ex(h, a.map_threshold, flags, nullptr, 0, &n) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+    std::vector<float> rows(4 * static_cast<size_t>(n));
+    if (n > 0 && smhip_mrvm_output_ex(h, a.map_threshold, flags, rows.data(), n, &m) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+    if (m != n) Die("map: output changed size between two calls");
+    res->voxels += v;
+    if (smhip::pcd::SaveBinary(path, n > 0 ? rows.data() : nullptr, static_cast<size_t>(n), a.map_rgb)) {
+      written.push_back(path);
+      res->points += n;
+      ++res->parts;
+    }
+  };
+  fresh_map();
+  smhip::kitti::ScanPrefetcher scans(files, frames, a.readers, 2 * std::max(1, a.readers) + 2, /*hold_until_release=*/false, slot_floats);
+  int in_part = 0, part = 0, rc = 0;
+  for (size_t i = 0; i < frames.size(); ++i) {
+    int n = 0, fi = -1;
+    const float* rows = scans.Next(&n, &fi);
+    if (!rows || fi != frames[i]) Die("map: prefetcher out of step");
+    if (n < 0) Die("cannot read " + files[fi]);
+    if (n == 0) {
+      std::fprintf(stderr, "smhip_shard: map: %s is empty, skipped\n", files[fi].c_str());     // InsertPointCloud: "cloud is empty.", :61-64
+    } else {
+      const smhip_status st = smhip_mrvm_insert_transformed_f32(h, rows, 4, n, poses[fi].data(), 255.f);
+      if (st != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: map: frame %d refused: %s\n", fi, smhip_mrvm_last_error(h));
+        rc = 3;
+        break;
+      }
+      if (smhip_mrvm_last_error(h)[0]) std::fprintf(stderr, "smhip_shard: map: frame %d: %s\n", fi, smhip_mrvm_last_error(h));
+    }
+    ++res->frames;
+    if (a.map_part_every > 0 && ++in_part == a.map_part_every) {
+      write_map(stem + "_part_" + std::to_string(part++) + ".pcd");
+      fresh_map();
+      in_part = 0;
+    }
+  }
+  if (rc == 0) {
+    if (a.map_part_every == 0) write_map(a.map_path);
+    else if (in_part > 0) write_map(stem + "_part_" + std::to_string(part) + ".pcd");
+  } else {
+    for (const auto& f : written) std::remove(f.c_str());
+  }
+  smhip_mrvm_destroy(h);
+  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+// --map-poses FILE: the map alone, one process, no alignment and no RCCL.  The pose file is checked before any GPU work: it needs
+// a pose for every frame the map inserts.
+int RunMapOnly(const Args& a) {
+  const auto files = ListScans(a.scans_dir);
+  int n_frames = static_cast<int>(files.size());
+  if (a.max_pairs > 0) n_frames = std::min(n_frames, a.max_pairs + 1);
+  std::vector<Pose> poses;
+  if (!ReadPoses(a.map_poses, &poses)) Die("cannot open " + a.map_poses);
+  const std::vector<int> frames = MapFrames(a, n_frames);
+  if (frames.empty()) Die("no scans in " + a.scans_dir);
+  if (static_cast<int>(poses.size()) <= frames.back())
+    Die(a.map_poses + " holds " + std::to_string(poses.size()) + " poses; the map needs one for every frame up to " + std::to_string(frames.back()) +
+        " (" + std::to_string(frames.back() + 1) + " lines)");
+  MapResult m;
+  const int rc = BuildMap(a, files, frames, poses, 0, &m);
+  if (rc == 0 && !a.quiet)
+    std::printf("%s}\n", (Fmt("{\"driver\": \"smhip_shard (map only)\", \"poses_file\": \"%s\", \"poses_in_file\": %d", a.map_poses.c_str(),
+                              static_cast<int>(poses.size())) + MapJsonFields(a, m)).c_str());
+  return rc;
 }
 
 int RunRank(const Args& a, int rank, int world, int device) {
@@ -352,6 +539,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
   const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
   int rc = 0;
+  std::string line;                                                      // rank 0's summary, printed after the map phase with --map
   if (rank == 0) {
     std::vector<double> all(static_cast<size_t>(kPoseDoubles) * per * world);
     HIPOK(hipMemcpy(all.data(), all_dev, sizeof(double) * all.size(), hipMemcpyDeviceToHost));
@@ -377,12 +565,13 @@ int RunRank(const Args& a, int rank, int world, int device) {
     }
     out.close();
     if (!a.quiet || bad) {
-      std::printf("{\"driver\": \"smhip_shard (C++, RCCL all-gather)\", \"n_gpus\": %d, \"pairs\": %d, \"pairs_rank0\": %d, \"seconds\": %.4f, "
+      line = Fmt("{\"driver\": \"smhip_shard (C++, RCCL all-gather)\", \"n_gpus\": %d, \"pairs\": %d, \"pairs_rank0\": %d, \"seconds\": %.4f, "
                   "\"pairs_per_s\": %.2f, \"read_upload_prepare_s_rank0\": %.4f, \"wait_for_readers_s_rank0\": %.4f, \"upload_s_rank0\": %.4f, "
                   "\"prepare_targets_s_rank0\": %.4f, \"mean_score\": %.6f, \"mean_iterations\": %.2f, "
-                  "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"}\n",
+                  "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
+      if (a.map_path.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;
   }
@@ -391,6 +580,16 @@ int RunRank(const Args& a, int rank, int world, int device) {
   if (pinned) for (float* b : ring_buffers) (void)hipHostFree(b);
   NCCLOK(ncclCommDestroy(comm));
   for (int k = 0; k < NH; ++k) (void)hipStreamDestroy(streams[k]);
+  if (rank == 0 && !a.map_path.empty()) {
+    // the static map from the poses as written: the pose file read back (--map-poses on that file builds the same map)
+    MapResult m;
+    if (rc == 0) {
+      std::vector<Pose> poses;
+      if (!ReadPoses(a.out_path, &poses) || static_cast<int>(poses.size()) != n_pairs + 1) Die("cannot read back " + a.out_path);
+      rc = BuildMap(a, files, MapFrames(a, n_pairs + 1), poses, device, &m);
+    }
+    if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? MapJsonFields(a, m).c_str() : "");
+  }
   return rc;
 }
 
@@ -402,6 +601,7 @@ int main(int argc, char** argv) {
   setenv("GPU_MAX_HW_QUEUES", "8", 0);
   Args a = Parse(argc, argv);
   if (a.id_file.empty()) a.id_file = "/tmp/smhip_shard_id_" + std::to_string(a.rank >= 0 ? static_cast<long>(getppid()) : static_cast<long>(getpid()));
+  if (!a.map_poses.empty()) return RunMapOnly(a);                       // the map alone: one process, no RCCL
   if (a.rank >= 0) {                                                     // one rank of a launched group
     const int world = a.world > 0 ? a.world : 1;
     if (a.nonce == 0) {                                                  // external launcher: every rank sees the same MASTER_PORT

@@ -15,6 +15,11 @@
 // every existing voxel the ray may still update), mrvm_apply (the two maps applied count times, from tables the host
 // computes with the reference's own float / double expressions).  The first max_point_num_in_cell points of a voxel
 // (:100-103, in point order) come from one radix sort of (voxel slot, point index).
+//
+// Two additions on the way to a map file (map_builder.cc:825-910): mrvm_transform writes a frame's world-frame rows from its raw
+// rows and pose (the reference's TransformPoint, every product and sum rounded to float), and the SORTED output orders the rows by
+// voxel key on the device (select the voxels kept, radix sort them by key, exclusive scan of their row counts), so that the same
+// map gives the same file on every run.
 #include <cstring>
 #include <string.h>
 
@@ -108,6 +113,27 @@ __global__ void mrvm_begin(MrvmDev d) {
   d.counters[0] = 0;
   d.counters[2] &= 2u;
   d.counters[5] = 0;
+}
+
+// ApplyTransformToOutput(pose), map_builder.cc:842-843, through TransformPoint (builder/data/cloud_types.cc:167-178): the pose cast
+// to float times (x, y, z, 1) as Eigen's 4x4 * 4-vector product accumulates it, column by column -- x' = ((m00 x + m01 y) + m02 z)
+// + m03 (times 1, exact).  The reference is built with -O2 and no -march: no fused multiply-add, so every product and every sum is
+// rounded on its own.  hipcc contracts a * b + c into an FMA by default, through __fmul_rn / __fadd_rn too (inlined, they carry
+// the file's contraction flag): the arithmetic is written out here with contraction switched off for this body, and the ISA
+// holds v_mul_f32 / v_add_f32 only.
+struct MrvmPose { float m[12]; };                // row-major top 3x4 of the pose, each entry cast to float
+__global__ __launch_bounds__(256) void mrvm_transform(const float* raw, int stride, int n, MrvmPose t, float scale, float* cloud) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float* r = raw + (size_t)stride * j;
+  const float x = r[0], y = r[1], z = r[2];
+  float* o = cloud + 5 * (size_t)j;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    o[i] = ((t.m[4 * i] * x + t.m[4 * i + 1] * y) + t.m[4 * i + 2] * z) + t.m[4 * i + 3];
+  o[3] = r[3] * scale;                           // intensity (kitti_reader.cc:113 scales by 255)
+  o[4] = stride > 4 ? r[4] : 0.f;                // factor
 }
 
 // end voxels of the cloud: :86-104
@@ -227,11 +253,9 @@ __global__ __launch_bounds__(256) void mrvm_update_counts(MrvmDev d, int n, cons
 // their order, divided by float(size)), bit 1 = the PointXYZRGB overload (4th column = the bits of (255 << 24 | g << 16 | g << 8 | g) with
 // g = min(255, uint32(max_intensity * 1.4)), :181-186), else PointXYZI (4th column = the voxel's max intensity when
 // use_max_intensity, else the point's own -- 0 for an averaged point, whose intensity is never assigned, :148-151)
-__global__ __launch_bounds__(256) void mrvm_output(MrvmDev d, uint8_t thr, int use_max, int flags, float* xyzi, int capacity) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s > d.tmask || d.keys[s] == 0ull || d.prob[s] < thr) return;
+// the rows of voxel s (kept: present, prob >= thr, npts > 0) from row `base` on, up to `capacity`
+__device__ __forceinline__ void mrvm_voxel_rows(const MrvmDev& d, uint32_t s, int use_max, int flags, float* xyzi, uint32_t base, int capacity) {
   const int c = d.npts[s];
-  if (c <= 0) return;
   const bool average = flags & 1, rgb = flags & 2;
   float grey = 0.f;
   if (rgb) {
@@ -240,7 +264,6 @@ __global__ __launch_bounds__(256) void mrvm_output(MrvmDev d, uint8_t thr, int u
     if (g > 255u) g = 255u;
     grey = __uint_as_float(0xff000000u | (g << 16) | (g << 8) | g);            // a = 255: what pcl::PointXYZRGB's constructor (PCL >= 1.8) leaves in the byte the reference never assigns
   }
-  const uint32_t base = atomicAdd(&d.counters[3], average ? 1u : (uint32_t)c);
   if (average) {
     if ((long long)base >= capacity) return;
     float ax = 0.f, ay = 0.f, az = 0.f;
@@ -261,6 +284,38 @@ __global__ __launch_bounds__(256) void mrvm_output(MrvmDev d, uint8_t thr, int u
     o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = rgb ? grey : (use_max ? (float)d.max_int[s] : p[3]);
   }
 }
+__global__ __launch_bounds__(256) void mrvm_output(MrvmDev d, uint8_t thr, int use_max, int flags, float* xyzi, int capacity) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > d.tmask || d.keys[s] == 0ull || d.prob[s] < thr) return;
+  const int c = d.npts[s];
+  if (c <= 0) return;
+  const uint32_t base = atomicAdd(&d.counters[3], (flags & 1) ? 1u : (uint32_t)c);
+  mrvm_voxel_rows(d, s, use_max, flags, xyzi, base, capacity);
+}
+
+// SORTED output: the voxels kept (flag per slot, for rocprim::select), their keys (for the radix sort), their row counts (for the
+// exclusive scan: one more entry than voxels, 0, so that the scan's last entry is the total) and the rows at the scanned offsets
+__global__ __launch_bounds__(256) void mrvm_keep_flags(MrvmDev d, uint8_t thr, uint8_t* keep) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > d.tmask) return;
+  keep[s] = d.keys[s] != 0ull && d.prob[s] >= thr && d.npts[s] > 0;
+}
+__global__ __launch_bounds__(256) void mrvm_gather_keys(MrvmDev d, const uint32_t* slots, int v, unsigned long long* keys) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < v) keys[i] = d.keys[slots[i]];
+}
+__global__ __launch_bounds__(256) void mrvm_row_counts(MrvmDev d, const uint32_t* slots, int v, int flags, uint32_t* counts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > v) return;
+  counts[i] = i == v ? 0u : ((flags & 1) ? 1u : (uint32_t)d.npts[slots[i]]);
+}
+__global__ __launch_bounds__(256) void mrvm_sorted_rows(MrvmDev d, const uint32_t* slots, const uint32_t* offsets, int v, int use_max, int flags,
+                                                        float* xyzi, int capacity) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v) return;
+  mrvm_voxel_rows(d, slots[i], use_max, flags, xyzi, offsets[i], capacity);
+}
+
 // every voxel, for the parity tests
 __global__ __launch_bounds__(256) void mrvm_dump(MrvmDev d, int32_t* keys3, uint8_t* prob, int32_t* max_int, int32_t* npts, float* pts, int capacity) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -290,6 +345,7 @@ struct smhip_mrvm_context {
   size_t T = 0;
   int max_cloud = 0;
   float* cloud_dev = nullptr;
+  float* raw_dev = nullptr;             // [max_cloud][5] raw rows of smhip_mrvm_insert_transformed_f32 (allocated on its first call)
   float* stage = nullptr;               // pinned
   uint32_t* counters_host = nullptr;    // pinned
   uint8_t* tables_dev = nullptr;
@@ -348,6 +404,64 @@ static void mrvm_grow_for(smhip_mrvm_context* h, int n) {
 }
 
 #define MCHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return SMHIP_ERR_HIP; } } while (0)
+
+// smhip_mrvm_output_ex with SMHIP_MRVM_SORTED: the kept voxels' slots (rocprim::select over the table), sorted by key (radix sort
+// of (key, slot)), their row counts scanned (exclusive) into write positions, then one thread per voxel writes its rows there --
+// no row's place depends on which thread got there first.  Scratch memory lives for the call.
+static smhip_status mrvm_output_sorted(smhip_mrvm_handle h, float threshold, int flags, float* rows, int capacity, int* n_out) {
+  struct Scratch {                                         // freed on every way out
+    std::vector<void*> p;
+    ~Scratch() { for (void* q : p) (void)hipFree(q); }
+    hipError_t get(void** q, size_t bytes) { hipError_t e = hipMalloc(q, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*q); return e; }
+  } sc;
+  const uint8_t thr = static_cast<uint8_t>(threshold * kTable);                                         // .cc:132
+  const size_t T = h->T;
+  const MrvmDev& d = h->d;
+  MCHK(h, hipMemcpyAsync(h->counters_host, d.counters, 16, hipMemcpyDeviceToHost, h->stream));
+  MCHK(h, hipStreamSynchronize(h->stream));
+  const size_t occupied = h->counters_host[1];             // voxels in the table: at most this many are kept
+  uint8_t* keep = nullptr; uint32_t *slots = nullptr, *slots2 = nullptr, *count = nullptr, *cnt = nullptr, *off = nullptr;
+  unsigned long long *keys = nullptr, *keys2 = nullptr;
+  MCHK(h, sc.get((void**)&keep, T));
+  MCHK(h, sc.get((void**)&slots, 4 * occupied)); MCHK(h, sc.get((void**)&slots2, 4 * occupied));
+  MCHK(h, sc.get((void**)&keys, 8 * occupied)); MCHK(h, sc.get((void**)&keys2, 8 * occupied));
+  MCHK(h, sc.get((void**)&cnt, 4 * (occupied + 1))); MCHK(h, sc.get((void**)&off, 4 * (occupied + 1))); MCHK(h, sc.get((void**)&count, 4));
+  size_t b1 = 0, b2 = 0, b3 = 0;
+  MCHK(h, rocprim::select(nullptr, b1, rocprim::counting_iterator<uint32_t>(0), keep, slots, count, T, h->stream));
+  MCHK(h, rocprim::radix_sort_pairs(nullptr, b2, keys, keys2, slots, slots2, (unsigned)std::max<size_t>(occupied, 1), 0, 63, h->stream));
+  MCHK(h, rocprim::exclusive_scan(nullptr, b3, cnt, off, 0u, occupied + 1, rocprim::plus<uint32_t>(), h->stream));
+  size_t bytes = std::max(b1, std::max(b2, b3));
+  void* tmp = nullptr;
+  MCHK(h, sc.get(&tmp, bytes));
+  hipLaunchKernelGGL(mrvm_keep_flags, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, h->stream, d, thr, keep);
+  size_t b = bytes;
+  MCHK(h, rocprim::select(tmp, b, rocprim::counting_iterator<uint32_t>(0), keep, slots, count, T, h->stream));
+  MCHK(h, hipMemcpyAsync(h->counters_host + 8, count, 4, hipMemcpyDeviceToHost, h->stream));
+  MCHK(h, hipStreamSynchronize(h->stream));
+  const int v = (int)std::min<size_t>(h->counters_host[8], occupied);
+  *n_out = 0;
+  if (v == 0) return SMHIP_OK;
+  const dim3 gv((unsigned)((v + 256) / 256)), b256(256);
+  hipLaunchKernelGGL(mrvm_gather_keys, gv, b256, 0, h->stream, d, slots, v, keys);
+  b = bytes;                                               // the key's top bit is always set: bits 0..62
+  MCHK(h, rocprim::radix_sort_pairs(tmp, b, keys, keys2, slots, slots2, (unsigned)v, 0, 63, h->stream));
+  hipLaunchKernelGGL(mrvm_row_counts, gv, b256, 0, h->stream, d, slots2, v, flags, cnt);
+  b = bytes;
+  MCHK(h, rocprim::exclusive_scan(tmp, b, cnt, off, 0u, (size_t)v + 1, rocprim::plus<uint32_t>(), h->stream));
+  MCHK(h, hipMemcpyAsync(h->counters_host + 8, off + v, 4, hipMemcpyDeviceToHost, h->stream));
+  MCHK(h, hipStreamSynchronize(h->stream));
+  const uint32_t total = h->counters_host[8];
+  *n_out = (int)total;
+  if (capacity <= 0) return SMHIP_OK;
+  const size_t m = std::min<size_t>((size_t)capacity, total);
+  float* dev = nullptr;
+  MCHK(h, sc.get((void**)&dev, sizeof(float) * 4 * m));
+  hipLaunchKernelGGL(mrvm_sorted_rows, gv, b256, 0, h->stream, d, slots2, off, v, h->set.use_max_intensity, flags, dev, (int)m);
+  MCHK(h, hipGetLastError());
+  MCHK(h, hipMemcpyAsync(rows, dev, sizeof(float) * 4 * m, hipMemcpyDeviceToHost, h->stream));
+  MCHK(h, hipStreamSynchronize(h->stream));
+  return SMHIP_OK;
+}
 
 extern "C" {
 
@@ -423,10 +537,11 @@ const char* smhip_mrvm_last_error(smhip_mrvm_handle h) { return h ? h->err.c_str
 
 void smhip_mrvm_set_offset_z(smhip_mrvm_handle h, float offset) { if (h) h->set.z_offset = offset; }   // SetOffsetZ, .cc:55-57
 
-smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3]) {
-  if (!h || !origin) return SMHIP_ERR_INVALID_ARGUMENT;
-  if (!points || n <= 0) { h->err = "cloud is empty."; return SMHIP_ERR_INVALID_ARGUMENT; }             // PRINT_ERROR + return, .cc:61-64
-  if (stride_floats < 4) { h->err = "rows need x y z intensity"; return SMHIP_ERR_INVALID_ARGUMENT; }
+// InsertPointCloud behind both entries.  pose == nullptr: `points` are map-frame rows of `stride_floats` >= 4 floats, packed to
+// InnerPointType rows on the host.  Otherwise the raw rows (stride 4 or 5) go up as they are and mrvm_transform writes the
+// world-frame rows on the device.
+static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3], const MrvmPose* pose,
+                                float intensity_scale) {
   if (n > h->max_cloud) { h->err = "cloud larger than max_cloud_points"; return SMHIP_ERR_CAPACITY; }
   {   // every ray starts at the origin: a non-finite or far-away one would walk ~2^21 voxels per ray for nothing.  Checked before
       // anything is touched, so a refused cloud leaves the map as it was.
@@ -441,6 +556,10 @@ smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int
   h->err.clear();
   h->last_skipped = 0;
   MCHK(h, hipSetDevice(h->device));
+  if (pose && !h->raw_dev) {
+    MCHK(h, hipMalloc((void**)&h->raw_dev, sizeof(float) * 5 * (size_t)h->max_cloud));
+    h->allocs.push_back(h->raw_dev);
+  }
   MCHK(h, hipStreamSynchronize(h->stream));
   if (h->voxels_stale) {                                    // the previous insert ended early: its voxels are in the table, not in `voxels`
     MCHK(h, hipMemcpy(h->counters_host, h->d.counters, 16, hipMemcpyDeviceToHost));
@@ -448,17 +567,26 @@ smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int
   }
   h->voxels_stale = true;
   mrvm_grow_for(h, n);                                      // room for the voxels this cloud can add, like the reference's std::map
-  for (int i = 0; i < n; ++i) {
-    const float* r = points + (size_t)stride_floats * i;
-    float* o = h->stage + 5 * (size_t)i;
-    o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = stride_floats > 4 ? r[4] : 0.f;
+  if (pose) {
+    std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);
+  } else {
+    for (int i = 0; i < n; ++i) {
+      const float* r = points + (size_t)stride_floats * i;
+      float* o = h->stage + 5 * (size_t)i;
+      o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = stride_floats > 4 ? r[4] : 0.f;
+    }
   }
   MrvmDev& d = h->d;
   ++d.epoch;
   d.o[0] = origin[0]; d.o[1] = origin[1]; d.o[2] = origin[2] + h->set.z_offset;                         // .cc:66-67
-  MCHK(h, hipMemcpyAsync(h->cloud_dev, h->stage, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(mrvm_begin, dim3(1), dim3(1), 0, h->stream, d);                                    // touched count, this cloud's flags
   const dim3 g((n + 255) / 256), b(256);
+  if (pose) {
+    MCHK(h, hipMemcpyAsync(h->raw_dev, h->stage, sizeof(float) * (size_t)stride_floats * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mrvm_transform, g, b, 0, h->stream, h->raw_dev, stride_floats, n, *pose, intensity_scale, h->cloud_dev);
+  } else {
+    MCHK(h, hipMemcpyAsync(h->cloud_dev, h->stage, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(mrvm_begin, dim3(1), dim3(1), 0, h->stream, d);                                    // touched count, this cloud's flags
   hipLaunchKernelGGL(mrvm_hit, g, b, 0, h->stream, d, n);
   hipLaunchKernelGGL(mrvm_miss, g, b, 0, h->stream, d, n);
   // the points kept per voxel: before the hit counts are consumed? they are independent of them -- sort (slot, index) pairs
@@ -492,6 +620,27 @@ smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int
   return SMHIP_OK;
 }
 
+smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3]) {
+  if (!h || !origin) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (!points || n <= 0) { h->err = "cloud is empty."; return SMHIP_ERR_INVALID_ARGUMENT; }             // PRINT_ERROR + return, .cc:61-64
+  if (stride_floats < 4) { h->err = "rows need x y z intensity"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  return mrvm_insert(h, points, stride_floats, n, origin, nullptr, 1.f);
+}
+
+smhip_status smhip_mrvm_insert_transformed_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                               float intensity_scale) {
+  if (!h || !pose) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (!rows || n <= 0) { h->err = "cloud is empty."; return SMHIP_ERR_INVALID_ARGUMENT; }               // PRINT_ERROR + return, .cc:61-64
+  if (stride_floats != 4 && stride_floats != 5) { h->err = "raw rows are x y z intensity [factor]: stride 4 or 5"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(pose[k])) { h->err = "pose is not finite: cloud refused"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  MrvmPose t;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) t.m[4 * r + c] = static_cast<float>(pose[4 * c + r]);                  // transform.cast<float>()
+  const float origin[3] = {t.m[3], t.m[7], t.m[11]};                                                 // GlobalTranslation().cast<float>()
+  return mrvm_insert(h, rows, stride_floats, n, origin, &t, intensity_scale);
+}
+
 smhip_status smhip_mrvm_set_max_table_log2(smhip_mrvm_handle h, int max_table_log2) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   if (max_table_log2 < 10 || max_table_log2 > 28) { h->err = "max_table_log2 must be in 10..28"; return SMHIP_ERR_INVALID_ARGUMENT; }
@@ -519,9 +668,10 @@ smhip_status smhip_mrvm_voxel_count(smhip_mrvm_handle h, int* n) {
 
 smhip_status smhip_mrvm_output_ex(smhip_mrvm_handle h, float threshold, int flags, float* rows, int capacity, int* n_out) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
-  if (!n_out || (capacity > 0 && !rows) || (flags & ~3)) { h->err = "output: null pointer or unknown flag"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (!n_out || (capacity > 0 && !rows) || (flags & ~7)) { h->err = "output: null pointer or unknown flag"; return SMHIP_ERR_INVALID_ARGUMENT; }
   h->err.clear();                                           // (an insert's warning text does not outlive the next call)
   MCHK(h, hipSetDevice(h->device));
+  if (flags & SMHIP_MRVM_SORTED) return mrvm_output_sorted(h, threshold, flags & 3, rows, capacity, n_out);
   float* dev = nullptr;
   if (capacity > 0) MCHK(h, hipMalloc((void**)&dev, sizeof(float) * 4 * (size_t)capacity));
   MCHK(h, hipMemsetAsync(h->d.counters + 3, 0, 4, h->stream));

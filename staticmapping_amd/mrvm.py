@@ -60,22 +60,43 @@ class MultiResolutionVoxelMapHip:
         self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
         self.last_skipped = n.value
 
+    def insert_transformed(self, rows, pose, intensity_scale: float = 1.0):
+        """ApplyTransformToOutput(pose) + InsertPointCloud (map_builder.cc:842-848), the transform on the device: rows [N, 4] (KITTI
+        x y z reflectance; factor 0) or [N, 5] (InnerPointType) in the sensor frame, pose [4, 4] (row-major numpy) sensor -> map.
+        The reference's TransformPoint: the pose cast to float, every product and sum rounded to float; origin = the pose's
+        translation cast to float; intensity = row[3] * intensity_scale in float (255 for raw KITTI rows, kitti_reader.cc:113)."""
+        p = np.ascontiguousarray(rows, dtype=np.float32)
+        T = np.asarray(pose, dtype=np.float64)
+        if p.ndim != 2 or T.shape != (4, 4):
+            raise ValueError("rows must be [N, 4|5], pose [4, 4]")
+        cm = np.ascontiguousarray(T.T).ravel()                    # column-major, as everywhere in the ABI
+        self._check(self._lib.smhip_mrvm_insert_transformed_f32(self._h, p.ctypes.data_as(_capi.c_float_p), p.shape[1], p.shape[0],
+                                                                cm.ctypes.data_as(_capi.c_double_p), float(intensity_scale)))
+        self.last_warning = self._lib.smhip_mrvm_last_error(self._h).decode()
+        n = ctypes.c_int32()
+        self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
+        self.last_skipped = n.value
+
     def voxel_count(self) -> int:
         n = ctypes.c_int32()
         self._check(self._lib.smhip_mrvm_voxel_count(self._h, ctypes.byref(n)))
         return n.value
 
-    def output_to_point_cloud(self, threshold: float | None = None, average: bool = False, rgb: bool = False) -> np.ndarray:
+    def output_to_point_cloud(self, threshold: float | None = None, average: bool = False, rgb: bool = False, sorted: bool = False,
+                              packed_rgb: bool = False) -> np.ndarray:
         """OutputToPointCloud (multi_resolution_voxel_map.cc:125-216): rows x y z intensity; average = MrvmSettings::output_average
-        (one mean point per voxel); rgb = the PointXYZRGB overload, 4th column = the grey level 0..255 (the packed colour's byte)."""
+        (one mean point per voxel); rgb = the PointXYZRGB overload, 4th column = the grey level 0..255 (the packed colour's byte), or
+        with packed_rgb the packed colour's bits as PCL's `rgb` float (what pcd.write_pcd(..., rgb=True) expects).  sorted: rows in
+        voxel-key order (x, then y, then z of the voxel), stored-point order within a voxel -- ordered on the device, the same map
+        gives the same array every time; otherwise table order."""
         thr = self.settings.prob_threshold if threshold is None else threshold
-        flags = (1 if average else 0) | (2 if rgb else 0)
+        flags = (1 if average else 0) | (2 if rgb else 0) | (4 if sorted else 0)
         n = ctypes.c_int32()
         self._check(self._lib.smhip_mrvm_output_ex(self._h, thr, flags, None, 0, ctypes.byref(n)))
         out = np.zeros((max(n.value, 1), 4), np.float32)
         self._check(self._lib.smhip_mrvm_output_ex(self._h, thr, flags, out.ctypes.data_as(_capi.c_float_p), len(out), ctypes.byref(n)))
         out = out[:n.value]
-        if rgb:                                   # packed r << 16 | g << 8 | b in the float's bits, r = g = b
+        if rgb and not packed_rgb:                # packed r << 16 | g << 8 | b in the float's bits, r = g = b
             out[:, 3] = (out[:, 3].copy().view(np.uint32) & 0xff).astype(np.float32)
         return out
 
