@@ -47,6 +47,7 @@ class VoxelGrid:
         order = np.argsort(idx, kind="stable")
         idx_s, p_s = idx[order], pts[order].astype(np.float64)
         uniq, start, count = np.unique(idx_s, return_index=True, return_counts=True)
+        self.occupied = len(uniq)                                      # voxels with any point, searchable or not
         means, icovs, cents, valid, keys = [], [], [], [], []
         for u, s, n in zip(uniq, start, count):
             if n < min_points:                                         # :297

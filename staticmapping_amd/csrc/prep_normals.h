@@ -33,8 +33,8 @@ hipError_t prep_sample_morton(PrepWorkspace* w, hipStream_t st, const float4* in
 // pcl::ApproximateVoxelGrid (leaf x leaf x leaf) of `raw` (n points, arrival order = array order) into `out`
 // (room for n entries; out[k].w = k).  Blocks until *m_host (number of centroids) is known.
 hipError_t prep_approx_voxel_grid(PrepWorkspace* w, hipStream_t st, const float4* raw, int n, float leaf, float4* out, int* m_host);
-// The same for S clouds at once (S <= 64; the workspace must hold sum(n) points): cloud c = raw[c][0 .. n[c]) (device pointers) into
-// out[c] (room for n[c] entries), m_host[c] centroids; per cloud exactly prep_approx_voxel_grid's output.  One synchronise for the batch.
+// The same for S clouds at once (one pass per 64 clouds; the workspace must hold sum(n) points): cloud c = raw[c][0 .. n[c]) (device pointers) into
+// out[c] (room for n[c] entries), m_host[c] centroids; per cloud exactly prep_approx_voxel_grid's output.  One synchronise per pass.
 hipError_t prep_approx_voxel_grid_batch(PrepWorkspace* w, hipStream_t st, int S, const float4* const* raw, const int* n, float leaf,
                                         float4* const* out, int* m_host);
 // Generic use of the workspace's radix sort by other builders (the NDT voxel grid): fill prep_keys(w, 0) / prep_values(w, 0)

@@ -828,7 +828,8 @@ hipError_t prep_approx_voxel_grid(PrepWorkspace* w, hipStream_t st, const float4
 
 // ---- S clouds at once: one key pass, ONE stable sort on (cloud, history entry), one scan, one flush, one sort of the runs by
 // (cloud, emission time), one emit; the counts come back with a single synchronise.  Per cloud the output is exactly
-// prep_approx_voxel_grid's.  The workspace must hold sum(n) points; S <= kAvgMaxClouds.
+// prep_approx_voxel_grid's.  The workspace must hold sum(n) points; one pass takes at most kAvgMaxClouds clouds (more take
+// one pass per kAvgMaxClouds).
 namespace {
 constexpr int kAvgMaxClouds = 64;
 struct AvgClouds {
@@ -902,7 +903,7 @@ __global__ void avg_emit_b(const AvgClouds cl, const float4* cent, const int32_t
 }
 }  // namespace
 
-hipError_t prep_approx_voxel_grid_batch(PrepWorkspace* w, hipStream_t st, int S, const float4* const* raw, const int* n, float leaf, float4* const* out, int* m_host) {
+static hipError_t avg_grid_pass(PrepWorkspace* w, hipStream_t st, int S, const float4* const* raw, const int* n, float leaf, float4* const* out, int* m_host) {
   if (!w || S <= 0 || S > kAvgMaxClouds || !(leaf > 0.f)) return hipErrorInvalidValue;
   AvgClouds cl{};
   cl.S = S;
@@ -937,6 +938,17 @@ hipError_t prep_approx_voxel_grid_batch(PrepWorkspace* w, hipStream_t st, int S,
   hipLaunchKernelGGL(avg_emit_b, dim3((R + 255) / 256), dim3(256), 0, st, cl, w->avg_cent, w->node_at[1], runp);
   for (int c = 0; c < S; ++c) m_host[c] = w->host_pinned[c + 1] - w->host_pinned[c];
   return hipGetLastError();
+}
+
+// every cloud's output depends on that cloud alone, and a pass reads its run counts after a synchronise while the passes queue in
+// order on `st`: consecutive passes may start the workspace at 0 again
+hipError_t prep_approx_voxel_grid_batch(PrepWorkspace* w, hipStream_t st, int S, const float4* const* raw, const int* n, float leaf, float4* const* out, int* m_host) {
+  if (S <= 0) return hipErrorInvalidValue;
+  for (int c0 = 0; c0 < S; c0 += kAvgMaxClouds) {
+    const hipError_t e = avg_grid_pass(w, st, std::min(kAvgMaxClouds, S - c0), raw + c0, n + c0, leaf, out + c0, m_host + c0);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // the arrays of the one-workgroup-per-scan forest (batches of >= kForestMinScans scans), allocated on first use or ahead of it

@@ -825,9 +825,9 @@ static smhip_status ndt_gicp_stage_clouds(smhip_handle h, int job) {
   return SMHIP_OK;
 }
 
-// the same for jobs first .. first + K - 1 at once when the voxel filter is on: ONE ApproximateVoxelGrid pass over every cloud that
-// has to be filtered (all sources, and the targets that are not kept), one Morton ordering of the down-sampled sources, one
-// synchronise -- instead of two sorts, a scan and a synchronise per cloud
+// the same for jobs first .. first + K - 1 at once when the voxel filter is on: ONE ApproximateVoxelGrid pass over every 64 clouds
+// that have to be filtered (all sources, and the targets that are not kept), one Morton ordering of the down-sampled sources, one
+// synchronise per pass -- instead of two sorts, a scan and a synchronise per cloud
 static smhip_status ndt_gicp_stage_clouds_batch(smhip_handle h, int first, int K) {
   GicpHost& g = gicp_of(h);
   const size_t NS = h->dev.ns_cap, NT = h->dev.nt_cap;
