@@ -438,6 +438,32 @@ smhip_status smhip_filter_get_output(smhip_handle h, float* points5, int32_t* so
 /* the filtered cloud becomes SetInputSource of `slot` without leaving the device */
 smhip_status smhip_filter_output_to_source(smhip_handle h, int slot);
 
+/* ---- the extended descriptor: every filter above plus GroundRemoval / GroundRemoval2 / RangeImage ------------
+ * (pre_processors/filter_ground_removal.cc, filter_ground_removal2.cc, filter_range_image.cc Filter()).  Slots:
+ *   RANGE .. BOUNDING_BOX_REMOVAL  p[0..5] as in smhip_filter_desc, i[0] axis_index; seed as there
+ *   GROUND_REMOVAL   p[0] leaf_size, p[1] height_threshold; i[0] min_point_num_in_voxel
+ *   GROUND_REMOVAL2  p[0] r_max, p[1] r_min, p[2] start_ground_height, p[3] long_line_threshold, p[4] max_long_line_height,
+ *                    p[5] max_start_height, p[6] max_error, p[7] max_slope, p[8] max_b (unused by the reference),
+ *                    p[9] max_dist_to_line, p[10] search_angle; i[0] bin_num, i[1] segment_num, i[2] thread_num (ignored)
+ *   RANGE_IMAGE      p[0] top_angle, p[1] btm_angle, p[2] offset_x, p[3] offset_y, p[4] offset_z;
+ *                    i[0] vertical_line_num, i[1] horizontal_line_num
+ * Device limits (refused with SMHIP_ERR_INVALID_ARGUMENT): bin_num <= 4096, bin_num * segment_num <= 2^22, the search
+ * of neighbouring segments within one turn, vertical_line_num * horizontal_line_num <= 2^22, voxel indices within +-2^20.
+ * Rows with a non-finite x, y or z are kept by both ground filters and dropped by RangeImage. */
+enum { SMHIP_FILTER_GROUND_REMOVAL = 6, SMHIP_FILTER_GROUND_REMOVAL2 = 7, SMHIP_FILTER_RANGE_IMAGE = 8 };
+typedef struct smhip_filter_desc_ex {
+  int32_t type;
+  uint32_t seed;
+  int32_t i[4];
+  float p[12];
+} smhip_filter_desc_ex;
+void smhip_filter_default_ex(int type, smhip_filter_desc_ex* f);
+/* 1 = the reference accepts it and the device can hold it */
+int smhip_filter_config_valid_ex(const smhip_filter_desc_ex* f);
+/* smhip_filter_chain_f32 for extended descriptors; smhip_filter_get_output / _output_to_source read its result */
+smhip_status smhip_filter_chain_ex_f32(smhip_handle h, const float* points, int stride_floats, int n,
+                                       const smhip_filter_desc_ex* chain, int n_filters, int* n_out);
+
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one
  * InsertPointCloud per frame, builder/map_builder.cc:832-900), on the device.  Results equal the reference's insert loop

@@ -5,9 +5,12 @@
 //   /root/reference/pre_processors/xml_interface.h:36-75         XmlInterface::SetValue by parameter name
 //   /root/reference/pre_processors/filter_interface.h:38-64      filter::Interface (InitFromXmlText, ConfigsValid, Filter)
 //   /root/reference/pre_processors/filter_{range,axis_range,bounding_box,random_sample,voxel_grid}.{h,cc}
+//   (the reference's) pre_processors/filter_{ground_removal,ground_removal2,range_image}.{h,cc}   (Filter only)
 //   /root/reference/pre_processors/filter_factory.{h,cc}         Factory: the <filters> chain
-// free of glog / pugixml / pcl.  Every filter runs on the GPU through smhip_filter_chain_f32; a Factory runs its whole
-// chain in one call and can hand the result to a matcher slot without a host round trip (FilterToSource).
+// free of glog / pugixml / pcl.  Every filter runs on the GPU through smhip_filter_chain_f32 (GroundRemoval, GroundRemoval2 and
+// RangeImage through smhip_filter_chain_ex_f32); a Factory runs its whole chain in one call and can hand the result to a matcher
+// slot without a host round trip (FilterToSource).  The default Factory registers the first five only; Factory(true) or
+// EnableGroundFilters() adds the other three.
 // Header-only; link with -lsmhip.
 #ifndef SMHIP_FILTERS_H_
 #define SMHIP_FILTERS_H_
@@ -100,16 +103,30 @@ class Interface {
     RunChain(chain, cloud, true);
   }
   const smhip_filter_desc& Desc() const { return desc_; }
+  // the same filter as an extended descriptor (smhip.h slot table)
+  virtual smhip_filter_desc_ex DescEx() const {
+    smhip_filter_desc_ex e{};
+    e.type = desc_.type; e.seed = desc_.seed; e.i[0] = desc_.axis_index;
+    for (int q = 0; q < 6; ++q) e.p[q] = desc_.p[q];
+    return e;
+  }
 
  protected:
-  bool SetValue(const std::string& name, double value) {                       // xml_interface.h:46-66
+  virtual bool SetValue(const std::string& name, double value) {               // xml_interface.h:46-66
     auto it = params_.find(name);
     if (it == params_.end()) return false;
     if (it->second == -1) desc_.axis_index = static_cast<int32_t>(value);
     else desc_.p[it->second] = static_cast<float>(value);
     return true;
   }
-  void RunChain(const std::vector<smhip_filter_desc>& chain, const data::InnerCloudType::Ptr& cloud, bool indices) {
+  static smhip_status Launch(smhip_handle h, const float* rows5, int n, const std::vector<smhip_filter_desc>& chain, int* m) {
+    return smhip_filter_chain_f32(h, rows5, 5, n, chain.data(), static_cast<int>(chain.size()), m);
+  }
+  static smhip_status Launch(smhip_handle h, const float* rows5, int n, const std::vector<smhip_filter_desc_ex>& chain, int* m) {
+    return smhip_filter_chain_ex_f32(h, rows5, 5, n, chain.data(), static_cast<int>(chain.size()), m);
+  }
+  template <typename Desc>
+  void RunChain(const std::vector<Desc>& chain, const data::InnerCloudType::Ptr& cloud, bool indices) {
     if (!context_) context_ = DeviceContext::Default();
     smhip_handle h = context_->handle();
     cloud->points.clear();                                                     // FilterPrepare, filter_interface.cc:86-92
@@ -117,7 +134,7 @@ class Interface {
     inliers_.clear(); outliers_.clear();
     const int n = static_cast<int>(inner_cloud_->points.size());
     int m = 0;
-    smhip_status s = smhip_filter_chain_f32(h, &inner_cloud_->points[0].x, 5, n, chain.data(), static_cast<int>(chain.size()), &m);
+    smhip_status s = Launch(h, &inner_cloud_->points[0].x, n, chain, &m);
     if (s != SMHIP_OK) { std::fprintf(stderr, "[FATAL] filter chain: %s (%s)\n", smhip_status_string(s), smhip_last_error(h)); std::abort(); }
     cloud->points.resize(m);
     std::vector<int32_t> src(m);
@@ -170,22 +187,89 @@ class RandomSampler : public Interface {
   void Filter(const data::InnerCloudType::Ptr& cloud) override { Interface::Filter(cloud); desc_.seed += 0x9e3779b9u; }   // a fresh stream per call
 };
 
+// GroundRemoval / GroundRemoval2 / RangeImage: parameters in the slots of smhip_filter_desc_ex (int parameters arrive as
+// type="0"); they run through smhip_filter_chain_ex_f32.  None of them has a ConfigsValid() in the reference: this one is false
+// only for what the device cannot hold (smhip_filter_config_valid_ex).
+class ExInterface : public Interface {
+ public:
+  bool ConfigsValid() const override { return smhip_filter_config_valid_ex(&ex_) != 0; }
+  smhip_filter_desc_ex DescEx() const override { return ex_; }
+  void Filter(const data::InnerCloudType::Ptr& cloud) override {
+    if (!cloud || !inner_cloud_) { std::fprintf(stderr, "[WARNING] nullptr cloud, do nothing!\n"); return; }
+    RunChain(std::vector<smhip_filter_desc_ex>(1, ex_), cloud, true);
+  }
+
+ protected:
+  ExInterface(int type, std::map<std::string, int> params) {                   // params: name -> p[] slot, or -1 - i[] slot
+    smhip_filter_default_ex(type, &ex_);
+    desc_.type = type;
+    params_ = std::move(params);
+  }
+  bool SetValue(const std::string& name, double value) override {
+    auto it = params_.find(name);
+    if (it == params_.end()) return false;
+    if (it->second < 0) ex_.i[-1 - it->second] = static_cast<int32_t>(value);
+    else ex_.p[it->second] = static_cast<float>(value);
+    return true;
+  }
+  smhip_filter_desc_ex ex_{};
+};
+
+// filter_ground_removal.cc:28-38
+class GroundRemoval : public ExInterface {
+ public:
+  GroundRemoval() : ExInterface(SMHIP_FILTER_GROUND_REMOVAL, {{"leaf_size", 0}, {"height_threshold", 1}, {"min_point_num_in_voxel", -1}}) {}
+  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<GroundRemoval>(); }
+  std::string GetName() const override { return "GroundRemoval"; }
+};
+
+// filter_ground_removal2.cc:72-110 (thread_num is accepted and ignored)
+class GroundRemoval2 : public ExInterface {
+ public:
+  GroundRemoval2()
+      : ExInterface(SMHIP_FILTER_GROUND_REMOVAL2,
+                    {{"r_max", 0}, {"r_min", 1}, {"start_ground_height", 2}, {"long_line_threshold", 3}, {"max_long_line_height", 4},
+                     {"max_start_height", 5}, {"max_error", 6}, {"max_slope", 7}, {"max_b", 8}, {"max_dist_to_line", 9},
+                     {"search_angle", 10}, {"bin_num", -1}, {"segment_num", -2}, {"thread_num", -3}}) {}
+  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<GroundRemoval2>(); }
+  std::string GetName() const override { return "GroundRemoval2"; }
+};
+
+// filter_range_image.cc:28-52 (Filter only: DepthCluster and ToPng are not mirrored)
+class RangeImage : public ExInterface {
+ public:
+  RangeImage()
+      : ExInterface(SMHIP_FILTER_RANGE_IMAGE, {{"top_angle", 0}, {"btm_angle", 1}, {"offset_x", 2}, {"offset_y", 3}, {"offset_z", 4},
+                                               {"vertical_line_num", -1}, {"horizontal_line_num", -2}}) {}
+  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<RangeImage>(); }
+  std::string GetName() const override { return "RangeImage"; }
+};
+
 // filter_factory.cc:47-106
 class Factory : public Interface {
  public:
-  Factory() {
+  explicit Factory(bool ground_filters = false) {
     supported_filters_.emplace("RandomSampler", std::make_shared<RandomSampler>());
     supported_filters_.emplace("Range", std::make_shared<Range>());
     supported_filters_.emplace("VoxelGrid", std::make_shared<VoxelGrid>());
     supported_filters_.emplace("AxisRange", std::make_shared<AxisRange>());
     supported_filters_.emplace("BoundingBoxRemoval", std::make_shared<BoundingBoxRemoval>());
+    if (ground_filters) EnableGroundFilters();
   }
-  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<Factory>(); }
+  // opt-in: registers GroundRemoval, GroundRemoval2 and RangeImage, and InitFromXmlText then skips <!-- ... --> comments as
+  // pugixml does (the default parse reads filters inside comments too)
+  void EnableGroundFilters() {
+    ground_filters_ = true;
+    supported_filters_.emplace("GroundRemoval", std::make_shared<GroundRemoval>());
+    supported_filters_.emplace("GroundRemoval2", std::make_shared<GroundRemoval2>());
+    supported_filters_.emplace("RangeImage", std::make_shared<RangeImage>());
+  }
+  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<Factory>(ground_filters_); }
   std::string GetName() const override { return ""; }
   bool ConfigsValid() const override { return true; }
 
   void InitFromXmlText(const char* text) {                                     // <filters> <filter .../> ... </filters>
-    const std::string t(text ? text : "");
+    const std::string t = ground_filters_ ? WithoutComments(text ? text : "") : std::string(text ? text : "");
     size_t pos = 0;
     while ((pos = t.find("<filter ", pos)) != std::string::npos) {
       const std::string name = Attribute(t, pos, "name");
@@ -207,15 +291,17 @@ class Factory : public Interface {
   }
   void Filter(const data::InnerCloudType::Ptr& cloud) override {              // filter_factory.cc:83-106
     if (!cloud || !inner_cloud_) { std::fprintf(stderr, "[WARNING] nullptr cloud, do nothing!\n"); return; }
-    RunChain(Chain(), cloud, false);
+    if (HasExFilter()) RunChain(ChainEx(), cloud, false);
+    else RunChain(Chain(), cloud, false);
   }
   // the same chain, the result handed to a matcher's source slot on the device (no host copy of the filtered cloud)
   bool FilterToSource(smhip_handle matcher, int slot, int* n_out) {
     if (!inner_cloud_) return false;
-    const std::vector<smhip_filter_desc> chain = Chain();
+    const int n = static_cast<int>(inner_cloud_->points.size());
     int m = 0;
-    if (smhip_filter_chain_f32(matcher, &inner_cloud_->points[0].x, 5, static_cast<int>(inner_cloud_->points.size()), chain.data(),
-                               static_cast<int>(chain.size()), &m) != SMHIP_OK) return false;
+    const smhip_status s = HasExFilter() ? Launch(matcher, &inner_cloud_->points[0].x, n, ChainEx(), &m)
+                                         : Launch(matcher, &inner_cloud_->points[0].x, n, Chain(), &m);
+    if (s != SMHIP_OK) return false;
     if (n_out) *n_out = m;
     return smhip_filter_output_to_source(matcher, slot) == SMHIP_OK;
   }
@@ -227,8 +313,32 @@ class Factory : public Interface {
     for (const auto& f : filters_) c.push_back(f->Desc());
     return c;
   }
+  std::vector<smhip_filter_desc_ex> ChainEx() const {
+    std::vector<smhip_filter_desc_ex> c;
+    for (const auto& f : filters_) c.push_back(f->DescEx());
+    return c;
+  }
+  bool HasExFilter() const {
+    for (const auto& f : filters_)
+      if (f->Desc().type >= SMHIP_FILTER_GROUND_REMOVAL) return true;
+    return false;
+  }
+  static std::string WithoutComments(const std::string& t) {
+    std::string out;
+    size_t pos = 0;
+    while (true) {
+      const size_t a = t.find("<!--", pos);
+      if (a == std::string::npos) { out.append(t, pos, std::string::npos); break; }
+      out.append(t, pos, a - pos);
+      const size_t b = t.find("-->", a + 4);
+      if (b == std::string::npos) break;                                       // an unterminated comment runs to the end
+      pos = b + 3;
+    }
+    return out;
+  }
   std::vector<std::shared_ptr<Interface>> filters_;
   std::map<std::string, std::shared_ptr<Interface>> supported_filters_;
+  bool ground_filters_ = false;
 };
 
 }  // namespace filter

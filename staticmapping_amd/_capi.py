@@ -75,6 +75,10 @@ class FilterDesc(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("p", ctypes.c_float * 6)]
 
 
+class FilterDescEx(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("seed", ctypes.c_uint32), ("i", ctypes.c_int32 * 4), ("p", ctypes.c_float * 12)]
+
+
 class MrvmSettings(ctypes.Structure):
     _fields_ = [("prob_threshold", ctypes.c_float), ("high_resolution", ctypes.c_float), ("hit_prob", ctypes.c_float),
                 ("miss_prob", ctypes.c_float), ("z_offset", ctypes.c_float), ("max_point_num_in_cell", ctypes.c_int32),
@@ -153,6 +157,10 @@ SIGNATURES = {
                                               ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_filter_get_output": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, ctypes.c_int]),
     "smhip_filter_output_to_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "smhip_filter_default_ex": (None, [ctypes.c_int, ctypes.POINTER(FilterDescEx)]),
+    "smhip_filter_config_valid_ex": (ctypes.c_int, [ctypes.POINTER(FilterDescEx)]),
+    "smhip_filter_chain_ex_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FilterDescEx),
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -6,18 +6,26 @@
 //   filter_bounding_box.cc:53-83   BoundingBoxRemoval  DROP the points inside [min, max] (common/bounding_box.cc:117-121)
 //   filter_random_sample.cc:41-85  RandomSampler       keep a point when a uniform draw <= sampling_rate
 //   filter_voxel_grid.cc:38-80     VoxelGrid           one average point (double sums) per lround(p / size) voxel
+//   filter_ground_removal.cc        GroundRemoval       drop small voxels and flat low ones    } kernels in ground_filters.hip;
+//   filter_ground_removal2.cc       GroundRemoval2      drop points near fitted ground lines   } what is and is not pinned:
+//   filter_range_image.cc           RangeImage          keep the first point of every pixel    } DESIGN.md §6, "Pre-filters"
 //   filter_factory.cc:83-106       Factory::Filter     the filters of <filters> applied in order
 // They run on every scan right before the registrator (builder/data/data_collector.h, config/lidar_only_kitti.xml:18-41).
 // All but VoxelGrid are order-preserving compactions: flag -> exclusive scan (rocPRIM building block) -> scatter;
 // consecutive predicate filters share one pass.  VoxelGrid is a stable radix sort on the packed voxel index and one
 // thread per voxel summing its points in arrival order in double, so each output point carries the reference's bits
 // (the reference emits voxels in unordered_map order, i.e. unspecified; here they come out sorted by voxel index).
+// The three ground / image filters end in the same flag -> scan -> scatter, so their output keeps the input order (GroundRemoval
+// emits voxel by voxel in the reference, in std::map order of the voxel index; GroundRemoval2 and RangeImage keep input order).
+// Every chain runs on smhip_filter_desc_ex; smhip_filter_chain_f32 widens its descriptors first.
 #include <cstring>
 #include <string.h>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 
@@ -130,6 +138,8 @@ __global__ void filt_voxel_average(const float4* pts, const int32_t* idx, const 
   out_src[v] = -1;
 }
 
+#include "ground_filters.hip"
+
 __global__ void filt_init(const float4* in, int n, int stride5, const float* fac_in, float4* pts, float* fac, int32_t* src) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -155,6 +165,15 @@ struct FilterWorkspace {
   int cur = 0;              // which of pts[2] holds the current cloud
   int n = 0;
   bool has_index = true;    // false once a VoxelGrid has run
+  // the ground / image filters' tables: allocated on first use, grown when a larger grid or image comes
+  float *gd = nullptr, *gz = nullptr, *runmin = nullptr;   // cap floats each (GroundRemoval2, per sorted point)
+  int32_t *vmin = nullptr, *vmax = nullptr;                // cap each (GroundRemoval, per voxel)
+  int grid_cap = 0;                                        // GroundRemoval2: S * B grids and line slots
+  int32_t *gend = nullptr, *gfirst = nullptr, *nlines = nullptr;
+  float4* lines = nullptr;
+  int seg_cap = 0;
+  int pix_cap = 0;                                         // RangeImage: V * H pixels
+  int32_t* pix = nullptr;
 };
 
 FilterWorkspace* filt_create(int max_points) {
@@ -189,6 +208,8 @@ void filt_destroy(FilterWorkspace* w) {
   }
   (void)hipFree(w->flag); (void)hipFree(w->pos); (void)hipFree(w->start); (void)hipFree(w->counts); (void)hipFree(w->fac_in);
   (void)hipFree(w->tmp);
+  (void)hipFree(w->gd); (void)hipFree(w->gz); (void)hipFree(w->runmin); (void)hipFree(w->vmin); (void)hipFree(w->vmax);
+  (void)hipFree(w->gend); (void)hipFree(w->gfirst); (void)hipFree(w->nlines); (void)hipFree(w->lines); (void)hipFree(w->pix);
   if (w->host_pinned) (void)hipHostFree(w->host_pinned);
   delete w;
 }
@@ -218,18 +239,118 @@ static hipError_t compact(FilterWorkspace* w, hipStream_t st) {      // flags ar
   return hipSuccess;
 }
 
-hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc* chain, int nf, int* n_out) {
+static hipError_t grow(void** p, size_t bytes) {
+  (void)hipFree(*p);
+  *p = nullptr;
+  return hipMalloc(p, bytes);
+}
+
+// the per-point tables of the ground filters and a temporary buffer large enough for the segmented scan
+static hipError_t ensure_ground(FilterWorkspace* w) {
+  if (w->gd) return hipSuccess;
+  const size_t N = (size_t)std::max(w->cap, 1);
+  FCHK(hipMalloc((void**)&w->gd, N * 4)); FCHK(hipMalloc((void**)&w->gz, N * 4)); FCHK(hipMalloc((void**)&w->runmin, N * 4));
+  FCHK(hipMalloc((void**)&w->vmin, N * 4)); FCHK(hipMalloc((void**)&w->vmax, N * 4));
+  size_t b = 0;
+  FCHK(rocprim::inclusive_scan_by_key(nullptr, b, (const unsigned long long*)nullptr, (const float*)nullptr, (float*)nullptr, N,
+                                      rocprim::minimum<float>(), rocprim::equal_to<unsigned long long>(), (hipStream_t)0));
+  if (b + 256 > w->tmp_bytes) {
+    FCHK(grow(&w->tmp, b + 256));
+    w->tmp_bytes = b + 256;
+  }
+  return hipSuccess;
+}
+
+static int key_bits(unsigned long long max_key) { int b = 1; while (b < 64 && (max_key >> b) != 0) ++b; return b; }
+
+// GroundRemoval2 on the current cloud: bin -> stable sort by grid -> segmented running minimum -> line fits -> cluster -> compact
+static hipError_t run_ground_removal2(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex& f) {
+  const int n = w->n, gp = (n + 255) / 256, c = w->cur;
+  const int B = f.i[0], S = f.i[1], G = B * S;
+  FCHK(ensure_ground(w));
+  if (G > w->grid_cap) {
+    FCHK(grow((void**)&w->gend, (size_t)G * 4)); FCHK(grow((void**)&w->gfirst, (size_t)G * 4));
+    FCHK(grow((void**)&w->lines, (size_t)G * sizeof(float4)));
+    w->grid_cap = G;
+  }
+  if (S > w->seg_cap) { FCHK(grow((void**)&w->nlines, (size_t)S * 4)); w->seg_cap = S; }
+  Gr2Args a{};
+  a.two_pi = (float)(M_PI * 2);                                          // const float double_pi = M_PI * 2, :146
+  a.delta_alpha = a.two_pi / (float)S;
+  a.delta_bin = (f.p[0] - f.p[1]) / (float)B;
+  a.r_min = f.p[1];
+  a.start_h = f.p[2]; a.long_thr = f.p[3]; a.long_h = f.p[4]; a.start_max = f.p[5]; a.max_err = f.p[6]; a.max_slope = f.p[7];
+  a.max_dist = f.p[9];
+  a.B = B; a.S = S; a.G = G;
+  a.search_step = gr2_search_step(f.p[10], S);
+  hipLaunchKernelGGL(gr2_bin, dim3(gp), dim3(256), 0, st, w->pts[c], n, a, w->keys[0], w->idx[0]);
+  size_t bytes = w->tmp_bytes;
+  FCHK(rocprim::radix_sort_pairs(w->tmp, bytes, w->keys[0], w->keys[1], w->idx[0], w->idx[1], (unsigned)n, 0, key_bits((unsigned long long)G), st));
+  hipLaunchKernelGGL(gr2_gather, dim3(gp), dim3(256), 0, st, w->pts[c], w->keys[1], w->idx[1], n, G, w->gd, w->gz, w->gend);
+  bytes = w->tmp_bytes;
+  FCHK(rocprim::inclusive_scan_by_key(w->tmp, bytes, w->keys[1], w->gz, w->runmin, (size_t)n, rocprim::minimum<float>(),
+                                      rocprim::equal_to<unsigned long long>(), st));
+  FCHK(hipMemsetD32Async((hipDeviceptr_t)w->gfirst, INT_MAX, (size_t)G, st));
+  hipLaunchKernelGGL(gr2_mark, dim3(gp), dim3(256), 0, st, w->keys[1], w->gz, w->runmin, w->gend, n, G, w->start, w->gfirst);
+  hipLaunchKernelGGL(gr2_fit_lines, dim3(S), dim3(64), sizeof(float2) * (size_t)B, st, w->gd, w->gz, w->gfirst, a, w->lines, w->nlines);
+  hipLaunchKernelGGL(gr2_cluster, dim3(gp), dim3(256), 0, st, w->keys[1], w->idx[1], w->gd, w->gz, w->start, n, a, w->lines, w->nlines,
+                     w->flag);
+  return compact(w, st);
+}
+
+// GroundRemoval on the current cloud: truncated voxel keys -> radix sort -> per-voxel size and z range -> flags -> compact
+static hipError_t run_ground_removal(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex& f) {
+  const int n = w->n, gp = (n + 255) / 256, c = w->cur;
+  FCHK(ensure_ground(w));
+  FCHK(hipMemsetAsync(w->counts + 1, 0, 4, st));
+  hipLaunchKernelGGL(gr_keys, dim3(gp), dim3(256), 0, st, w->pts[c], n, f.p[0], w->keys[0], w->idx[0], w->counts + 1);
+  size_t bytes = w->tmp_bytes;
+  FCHK(rocprim::radix_sort_pairs(w->tmp, bytes, w->keys[0], w->keys[1], w->idx[0], w->idx[1], (unsigned)n, 0, 64, st));
+  hipLaunchKernelGGL(filt_voxel_heads, dim3(gp), dim3(256), 0, st, w->keys[1], n, w->flag);
+  bytes = w->tmp_bytes;
+  FCHK(rocprim::inclusive_scan(w->tmp, bytes, w->flag, w->pos, (size_t)n, rocprim::plus<int32_t>(), st));
+  hipLaunchKernelGGL(filt_voxel_starts, dim3(gp), dim3(256), 0, st, w->flag, w->pos, n, w->start, w->counts);
+  FCHK(hipMemsetD32Async((hipDeviceptr_t)w->vmin, INT_MAX, (size_t)n, st));
+  FCHK(hipMemsetD32Async((hipDeviceptr_t)w->vmax, INT_MIN, (size_t)n, st));
+  hipLaunchKernelGGL(gr_minmax, dim3(gp), dim3(256), 0, st, w->pts[c], w->keys[1], w->idx[1], w->pos, n, w->vmin, w->vmax);
+  hipLaunchKernelGGL(gr_flags, dim3(gp), dim3(256), 0, st, w->keys[1], w->idx[1], w->pos, w->start, w->counts, n, f.p[1], f.i[0],
+                     w->vmin, w->vmax, w->flag);
+  FCHK(hipMemcpyAsync(w->host_pinned + 2, w->counts + 1, 4, hipMemcpyDeviceToHost, st));
+  FCHK(hipStreamSynchronize(st));
+  if (w->host_pinned[2] != 0) return hipErrorInvalidValue;               // a voxel index beyond +-2^20
+  return compact(w, st);
+}
+
+// RangeImage::Filter on the current cloud: pixel per row, atomicMin of the row index per pixel, keep the winners
+static hipError_t run_range_image(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex& f) {
+  const int n = w->n, gp = (n + 255) / 256, c = w->cur;
+  const int V = f.i[0], H = f.i[1];
+  if (V * H > w->pix_cap) { FCHK(grow((void**)&w->pix, (size_t)V * H * 4)); w->pix_cap = V * H; }
+  RiArgs a{};
+  a.ox = f.p[2]; a.oy = f.p[3]; a.oz = f.p[4];
+  a.hres = (float)(M_PI * 2 / (double)(float)H);                        // :84-85
+  a.vres = (float)((double)((f.p[0] - f.p[1]) / (float)V / 180.f) * M_PI);   // :86-88
+  a.btm_rad = (double)(f.p[1] / 180.f) * M_PI;                          // :105
+  a.V = V; a.H = H;
+  FCHK(hipMemsetD32Async((hipDeviceptr_t)w->pix, INT_MAX, (size_t)V * H, st));
+  hipLaunchKernelGGL(ri_pixel, dim3(gp), dim3(256), 0, st, w->pts[c], n, a, w->idx[0], w->pix);
+  hipLaunchKernelGGL(ri_flags, dim3(gp), dim3(256), 0, st, w->idx[0], w->pix, n, w->flag);
+  return compact(w, st);
+}
+
+static bool is_predicate(int t) { return t == SMHIP_FILTER_RANGE || t == SMHIP_FILTER_AXIS_RANGE || t == SMHIP_FILTER_BOUNDING_BOX_REMOVAL; }
+
+hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex* chain, int nf, int* n_out) {
   if (!w || (nf > 0 && !chain)) return hipErrorInvalidValue;
   int k = 0;
   while (k < nf && w->n > 0) {
-    const smhip_filter_desc& f = chain[k];
+    const smhip_filter_desc_ex& f = chain[k];
     const int n = w->n, gp = (n + 255) / 256;
-    if (f.type == SMHIP_FILTER_RANGE || f.type == SMHIP_FILTER_AXIS_RANGE || f.type == SMHIP_FILTER_BOUNDING_BOX_REMOVAL) {
+    if (is_predicate(f.type)) {
       PredGroup g{};
-      while (k < nf && g.n < kMaxFused && (chain[k].type == SMHIP_FILTER_RANGE || chain[k].type == SMHIP_FILTER_AXIS_RANGE ||
-                                           chain[k].type == SMHIP_FILTER_BOUNDING_BOX_REMOVAL)) {
+      while (k < nf && g.n < kMaxFused && is_predicate(chain[k].type)) {
         Pred& p = g.f[g.n++];
-        p.type = chain[k].type; p.axis = chain[k].axis_index;
+        p.type = chain[k].type; p.axis = chain[k].i[0];
         for (int q = 0; q < 6; ++q) p.p[q] = chain[k].p[q];
         ++k;
       }
@@ -259,6 +380,15 @@ hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter
       w->n = w->host_pinned[0];
       w->cur = o;
       w->has_index = false;
+    } else if (f.type == SMHIP_FILTER_GROUND_REMOVAL) {
+      ++k;
+      FCHK(run_ground_removal(w, st, f));
+    } else if (f.type == SMHIP_FILTER_GROUND_REMOVAL2) {
+      ++k;
+      FCHK(run_ground_removal2(w, st, f));
+    } else if (f.type == SMHIP_FILTER_RANGE_IMAGE) {
+      ++k;
+      FCHK(run_range_image(w, st, f));
     } else {
       return hipErrorInvalidValue;
     }

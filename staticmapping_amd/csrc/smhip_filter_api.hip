@@ -1,7 +1,8 @@
 // smhip_filter_api.hip -- C ABI of the device pre-filters (included by smhip_api.hip); kernels in cloud_filters.hip.
-// Mirrors pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, Factory}
-// (/root/reference/pre_processors/filter_*.cc): constructor defaults, ConfigsValid() and Filter().
+// Mirrors pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, GroundRemoval, GroundRemoval2,
+// RangeImage, Factory} (the reference's pre_processors/filter_*.cc): constructor defaults, ConfigsValid() and Filter().
 #include <cfloat>
+#include <cmath>
 
 extern "C" {
 
@@ -41,14 +42,44 @@ static smhip_status filter_ensure(smhip_handle h) {
   return SMHIP_OK;
 }
 
-smhip_status smhip_filter_chain_f32(smhip_handle h, const float* points, int stride_floats, int n, const smhip_filter_desc* chain,
-                                    int n_filters, int* n_out) {
-  if (!h || !points || n < 0 || n_filters < 0 || (n_filters > 0 && !chain) || (stride_floats != 4 && stride_floats != 5)) {
-    if (h) h->err = "bad arguments (stride must be 4 = x y z intensity or 5 = InnerPointType)";
-    return SMHIP_ERR_INVALID_ARGUMENT;
+static smhip_filter_desc_ex widen(const smhip_filter_desc& f) {
+  smhip_filter_desc_ex e;
+  std::memset(&e, 0, sizeof(e));
+  e.type = f.type; e.seed = f.seed; e.i[0] = f.axis_index;
+  for (int q = 0; q < 6; ++q) e.p[q] = f.p[q];
+  return e;
+}
+
+constexpr long kMaxFilterCells = 1l << 22;        // GroundRemoval2 grids, RangeImage pixels
+constexpr int kMaxBins = 4096;                    // GroundRemoval2: one segment's line points in LDS
+
+// why the device cannot run the descriptor (nullptr = it can); the three new filters have no ConfigsValid() of their own
+static const char* config_problem_ex(const smhip_filter_desc_ex* f) {
+  if (!f) return "null descriptor";
+  switch (f->type) {
+    case SMHIP_FILTER_GROUND_REMOVAL:
+      if (!(f->p[0] > 0.f) || !std::isfinite(f->p[0])) return "GroundRemoval: leaf_size must be a positive finite number";
+      return nullptr;
+    case SMHIP_FILTER_GROUND_REMOVAL2:
+      if (f->i[0] <= 0 || f->i[1] <= 0) return "GroundRemoval2: bin_num and segment_num must be positive";
+      if (f->i[0] > kMaxBins) return "GroundRemoval2: bin_num above the device limit of 4096";
+      if ((long)f->i[0] * f->i[1] > kMaxFilterCells) return "GroundRemoval2: bin_num * segment_num above the device limit of 2^22";
+      if (gr2_search_step(f->p[10], f->i[1]) > f->i[1]) return "GroundRemoval2: search_angle reaches past a whole turn";
+      return nullptr;
+    case SMHIP_FILTER_RANGE_IMAGE:
+      if (f->i[0] <= 0 || f->i[1] <= 0) return "RangeImage: vertical_line_num and horizontal_line_num must be positive";
+      if ((long)f->i[0] * f->i[1] > kMaxFilterCells) return "RangeImage: image larger than the device limit of 2^22 pixels";
+      return nullptr;
   }
-  for (int k = 0; k < n_filters; ++k)
-    if (!smhip_filter_config_valid(&chain[k])) { h->err = "filter " + std::to_string(k) + ": ConfigsValid() is false"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  smhip_filter_desc d;
+  std::memset(&d, 0, sizeof(d));
+  d.type = f->type; d.seed = f->seed; d.axis_index = f->i[0];
+  for (int q = 0; q < 6; ++q) d.p[q] = f->p[q];
+  return smhip_filter_config_valid(&d) ? nullptr : "ConfigsValid() is false";
+}
+
+static smhip_status filter_chain(smhip_handle h, const float* points, int stride_floats, int n, const smhip_filter_desc_ex* chain,
+                                 int n_filters, int* n_out) {
   if (n > std::max(h->dev.ns_cap, h->dev.nt_cap)) { h->err = "cloud larger than the handle's capacity"; return SMHIP_ERR_CAPACITY; }
   HIPCHK(h, hipSetDevice(h->device));
   smhip_status s = filter_ensure(h);
@@ -68,6 +99,53 @@ smhip_status smhip_filter_chain_f32(smhip_handle h, const float* points, int str
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (n_out) *n_out = filt_count(h->filt);
   return SMHIP_OK;
+}
+
+smhip_status smhip_filter_chain_f32(smhip_handle h, const float* points, int stride_floats, int n, const smhip_filter_desc* chain,
+                                    int n_filters, int* n_out) {
+  if (!h || !points || n < 0 || n_filters < 0 || (n_filters > 0 && !chain) || (stride_floats != 4 && stride_floats != 5)) {
+    if (h) h->err = "bad arguments (stride must be 4 = x y z intensity or 5 = InnerPointType)";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  for (int k = 0; k < n_filters; ++k)
+    if (!smhip_filter_config_valid(&chain[k])) { h->err = "filter " + std::to_string(k) + ": ConfigsValid() is false"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  std::vector<smhip_filter_desc_ex> ex((size_t)n_filters);
+  for (int k = 0; k < n_filters; ++k) ex[k] = widen(chain[k]);
+  return filter_chain(h, points, stride_floats, n, ex.data(), n_filters, n_out);
+}
+
+void smhip_filter_default_ex(int type, smhip_filter_desc_ex* f) {
+  if (!f) return;
+  std::memset(f, 0, sizeof(*f));
+  f->type = type;
+  switch (type) {
+    case SMHIP_FILTER_GROUND_REMOVAL:                                                         // filter_ground_removal.cc:28-38
+      f->p[0] = 0.8f; f->p[1] = 0.15f; f->i[0] = 10; break;
+    case SMHIP_FILTER_GROUND_REMOVAL2:                                                        // filter_ground_removal2.cc:72-110
+      f->p[0] = 100.f; f->p[1] = 1.f; f->p[2] = -0.25f; f->p[3] = 1.0f; f->p[4] = 0.1f; f->p[5] = 0.2f; f->p[6] = 0.05f;
+      f->p[7] = (float)std::tan(M_PI / 12.); f->p[8] = 0.1f; f->p[9] = 0.05f; f->p[10] = 10.f;
+      f->i[0] = 200; f->i[1] = 180; f->i[2] = 4; break;
+    case SMHIP_FILTER_RANGE_IMAGE:                                                            // filter_range_image.cc:28-52
+      f->p[0] = 30.f; f->p[1] = -15.f; f->i[0] = 40; f->i[1] = 1800; break;
+    default: {
+      smhip_filter_desc d;
+      smhip_filter_default(type, &d);
+      *f = widen(d);
+    }
+  }
+}
+
+int smhip_filter_config_valid_ex(const smhip_filter_desc_ex* f) { return config_problem_ex(f) == nullptr ? 1 : 0; }
+
+smhip_status smhip_filter_chain_ex_f32(smhip_handle h, const float* points, int stride_floats, int n, const smhip_filter_desc_ex* chain,
+                                       int n_filters, int* n_out) {
+  if (!h || !points || n < 0 || n_filters < 0 || (n_filters > 0 && !chain) || (stride_floats != 4 && stride_floats != 5)) {
+    if (h) h->err = "bad arguments (stride must be 4 = x y z intensity or 5 = InnerPointType)";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  for (int k = 0; k < n_filters; ++k)
+    if (const char* why = config_problem_ex(&chain[k])) { h->err = "filter " + std::to_string(k) + ": " + why; return SMHIP_ERR_INVALID_ARGUMENT; }
+  return filter_chain(h, points, stride_floats, n, chain, n_filters, n_out);
 }
 
 smhip_status smhip_filter_get_output(smhip_handle h, float* points5, int32_t* source_index, int n) {

@@ -1,6 +1,7 @@
 """ctypes view of the device pre-filters (include/smhip.h, `smhip_filter_*`): the Python mirror of
-pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, Factory}
-(/root/reference/pre_processors/filter_*.cc).  Filters are dicts with the reference's parameter names."""
+pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, GroundRemoval, GroundRemoval2,
+RangeImage, Factory} (the reference's pre_processors/filter_*.cc).  Filters are descriptors set by the reference's parameter
+names: `FilterDesc` for the first five, `FilterDescEx` for GroundRemoval, GroundRemoval2 and RangeImage."""
 from __future__ import annotations
 
 import ctypes
@@ -11,15 +12,39 @@ import numpy as np
 from . import _capi
 
 RANGE, AXIS_RANGE, RANDOM_SAMPLER, VOXEL_GRID, BOUNDING_BOX_REMOVAL = 1, 2, 3, 4, 5
+GROUND_REMOVAL, GROUND_REMOVAL2, RANGE_IMAGE = 6, 7, 8
 NAMES = {"Range": RANGE, "AxisRange": AXIS_RANGE, "RandomSampler": RANDOM_SAMPLER, "VoxelGrid": VOXEL_GRID,
          "BoundingBoxRemoval": BOUNDING_BOX_REMOVAL}
+GROUND_NAMES = {"GroundRemoval": GROUND_REMOVAL, "GroundRemoval2": GROUND_REMOVAL2, "RangeImage": RANGE_IMAGE}
 _PARAMS = {RANGE: ("min_range", "max_range"), AXIS_RANGE: ("min", "max"), RANDOM_SAMPLER: ("sampling_rate",),
            VOXEL_GRID: ("voxel_size",), BOUNDING_BOX_REMOVAL: ("min_x", "min_y", "min_z", "max_x", "max_y", "max_z")}
+# the FilterDescEx slots of the new filters (include/smhip.h): name -> ("p" | "i", index)
+_PARAMS_EX = {
+    GROUND_REMOVAL: {"leaf_size": ("p", 0), "height_threshold": ("p", 1), "min_point_num_in_voxel": ("i", 0)},
+    GROUND_REMOVAL2: {"r_max": ("p", 0), "r_min": ("p", 1), "start_ground_height": ("p", 2), "long_line_threshold": ("p", 3),
+                      "max_long_line_height": ("p", 4), "max_start_height": ("p", 5), "max_error": ("p", 6), "max_slope": ("p", 7),
+                      "max_b": ("p", 8), "max_dist_to_line": ("p", 9), "search_angle": ("p", 10), "bin_num": ("i", 0),
+                      "segment_num": ("i", 1), "thread_num": ("i", 2)},
+    RANGE_IMAGE: {"top_angle": ("p", 0), "btm_angle": ("p", 1), "offset_x": ("p", 2), "offset_y": ("p", 3), "offset_z": ("p", 4),
+                  "vertical_line_num": ("i", 0), "horizontal_line_num": ("i", 1)}}
 
 
-def make_filter(name_or_type, **params) -> _capi.FilterDesc:
-    """A filter with its constructor defaults, then `params` (reference names; plus `axis_index`, `seed`)."""
-    t = NAMES[name_or_type] if isinstance(name_or_type, str) else int(name_or_type)
+def make_filter(name_or_type, **params):
+    """A filter with its constructor defaults, then `params` (reference names; plus `axis_index`, `seed`).
+    GroundRemoval, GroundRemoval2 and RangeImage give a FilterDescEx, the others a FilterDesc."""
+    t = {**NAMES, **GROUND_NAMES}[name_or_type] if isinstance(name_or_type, str) else int(name_or_type)
+    if t in _PARAMS_EX:
+        d = _capi.FilterDescEx()
+        _capi.load_library().smhip_filter_default_ex(t, ctypes.byref(d))
+        for k, v in params.items():
+            if k not in _PARAMS_EX[t]:
+                raise KeyError(f"{k} is not a parameter of filter type {t}")
+            arr, slot = _PARAMS_EX[t][k]
+            if arr == "i":
+                d.i[slot] = int(v)
+            else:
+                d.p[slot] = float(v)
+        return d
     d = _capi.FilterDesc()
     _capi.load_library().smhip_filter_default(t, ctypes.byref(d))
     for k, v in params.items():
@@ -34,34 +59,61 @@ def make_filter(name_or_type, **params) -> _capi.FilterDesc:
     return d
 
 
-def config_valid(d: _capi.FilterDesc) -> bool:
+def config_valid(d) -> bool:
+    if isinstance(d, _capi.FilterDescEx):
+        return bool(_capi.load_library().smhip_filter_config_valid_ex(ctypes.byref(d)))
     return bool(_capi.load_library().smhip_filter_config_valid(ctypes.byref(d)))
 
 
-def chain_from_xml(text: str, seed: int = 0) -> list:
-    """The <filters> element of the reference's configs (filter_factory.cc:47-81): unsupported names are skipped."""
+def widen(d) -> _capi.FilterDescEx:
+    """A FilterDesc as the FilterDescEx that selects the same filter (axis_index -> i[0])."""
+    if isinstance(d, _capi.FilterDescEx):
+        return d
+    e = _capi.FilterDescEx()
+    e.type, e.seed, e.i[0] = d.type, d.seed, d.axis_index
+    for k in range(6):
+        e.p[k] = d.p[k]
+    return e
+
+
+def chain_from_xml(text: str, seed: int = 0, ground_filters: bool = False) -> list:
+    """The <filters> element of the reference's configs (filter_factory.cc:47-81): unsupported names are skipped.
+    ground_filters=True also takes GroundRemoval, GroundRemoval2 and RangeImage, and skips <!-- ... --> comments as pugixml
+    does (the default keeps the historical parse, which reads filters inside comments too)."""
+    if ground_filters:
+        text = re.sub(r"<!--.*?-->", "", text, flags=re.S)
+    names = {**NAMES, **GROUND_NAMES} if ground_filters else NAMES
     out = []
     for m in re.finditer(r'<filter\s+name="([^"]+)"\s*(?:/>|>(.*?)</filter>)', text, flags=re.S):
         name, body = m.group(1), m.group(2) or ""
-        if name not in NAMES:
+        if name not in names:
             continue
         params = {}
         for p in re.finditer(r'<param\s+type="(\d)"\s+name="([^"]+)"\s*>\s*([^<]*?)\s*</param>', body):
             params[p.group(2)] = int(float(p.group(3))) if p.group(1) == "0" else float(p.group(3))
-        if NAMES[name] == RANDOM_SAMPLER:
+        if names[name] == RANDOM_SAMPLER:
             params.setdefault("seed", seed + len(out))
         out.append(make_filter(name, **params))
     return out
 
 
+def _launch(matcher, a, chain, n_out):
+    """smhip_filter_chain_f32 when every descriptor is a FilterDesc, else smhip_filter_chain_ex_f32 on the widened chain"""
+    if all(isinstance(d, _capi.FilterDesc) for d in chain):
+        arr = (_capi.FilterDesc * max(1, len(chain)))(*chain)
+        fn = matcher._lib.smhip_filter_chain_f32
+    else:
+        arr = (_capi.FilterDescEx * max(1, len(chain)))(*[widen(d) for d in chain])
+        fn = matcher._lib.smhip_filter_chain_ex_f32
+    matcher._check(fn(matcher._h, a.ctypes.data_as(_capi.c_float_p), a.shape[1], a.shape[0], arr, len(chain), ctypes.byref(n_out)))
+
+
 def run_chain(matcher, points, chain):
     """Factory::Filter on the device.  points: float32 [N,4] (KITTI rows) or [N,5] (InnerPointType rows).
-    Returns (filtered [M,5] float32, source_index [M] int32)."""
+    `chain` may mix FilterDesc and FilterDescEx.  Returns (filtered [M,5] float32, source_index [M] int32)."""
     a = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
-    arr = (_capi.FilterDesc * max(1, len(chain)))(*chain)
     n_out = ctypes.c_int()
-    matcher._check(matcher._lib.smhip_filter_chain_f32(matcher._h, a.ctypes.data_as(_capi.c_float_p), a.shape[1], a.shape[0],
-                                                       arr, len(chain), ctypes.byref(n_out)))
+    _launch(matcher, a, chain, n_out)
     out = np.zeros((n_out.value, 5), np.float32)
     src = np.zeros(n_out.value, np.int32)
     matcher._check(matcher._lib.smhip_filter_get_output(matcher._h, out.ctypes.data_as(_capi.c_float_p),
@@ -72,10 +124,8 @@ def run_chain(matcher, points, chain):
 def run_chain_resident(matcher, points, chain) -> int:
     """The same without reading the result back: returns the filtered size; follow with output_to_source()."""
     a = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
-    arr = (_capi.FilterDesc * max(1, len(chain)))(*chain)
     n_out = ctypes.c_int()
-    matcher._check(matcher._lib.smhip_filter_chain_f32(matcher._h, a.ctypes.data_as(_capi.c_float_p), a.shape[1], a.shape[0],
-                                                       arr, len(chain), ctypes.byref(n_out)))
+    _launch(matcher, a, chain, n_out)
     return n_out.value
 
 
