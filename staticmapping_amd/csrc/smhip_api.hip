@@ -17,14 +17,20 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "../../include/smhip.h"
 #include "prep_normals.h"
 #include "cloud_filters.h"
+#include "icp_plan.h"
 
 using namespace smhip;
+using plan::ceil_div;
+
+static_assert(plan::kRingCoopLanes == kCoopLanes && plan::kNaboBucket == kKdBucket && plan::kNaboShallowLevels <= kKdStack,
+              "icp_plan.h restates kernel constants");
 
 struct smhip_ndt_state;
 struct smhip_gicp_state;
@@ -43,11 +49,8 @@ struct smhip_context {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  // a batch is split into up to kMaxParts parts on separate streams so that the latency-bound kernels of one part
-  // (finalize, validate, grid build) hide behind the NN / accumulate kernels of the others
-  static constexpr int kMaxParts = 4;
-  hipStream_t side[kMaxParts - 1] = {};
-  hipEvent_t ev_fork = nullptr, ev_join[kMaxParts - 1] = {};
+  hipStream_t side[plan::kMaxParts - 1] = {};      // the streams of a batch's parts beyond the first (icp_plan.h)
+  hipEvent_t ev_fork = nullptr, ev_join[plan::kMaxParts - 1] = {};
   int n_side = 0;
   IcpDev dev{};
   KdDev kd{};                    // SMHIP_NN_NABO: tree arrays, allocated on first use
@@ -68,7 +71,7 @@ struct smhip_context {
   PairInput* in_pinned = nullptr;
   PairState* state_pinned = nullptr;
   int hist_mode = 0;             // nn_mode of the batch whose searched-query history is waiting in hist_pinned
-  int nabo_fused_from = 6;       // reference-search mode: the first iteration of a batch that runs the fused certificate pass (fused_iteration)
+  int nabo_fused_from = 6;       // reference-search mode: the first iteration of a batch that runs the fused certificate pass (plan::fused_now)
   float split_share = 0.2f;      // auto split: the first iteration whose median searched share falls below this runs certify + listed search
   int sums_blocks = kSumsBlocks;  // workgroups of iteration_sums (SMHIP_SUMS_BLOCKS)
   int sums_long_for = 3;         // fused iterations of a batch whose missed pairs iteration_sums cuts into long blocks (SMHIP_SUMS_LONG_FOR)
@@ -81,6 +84,9 @@ struct smhip_context {
   int one_enabled = 1;           // SMHIP_ONE_PAIR=0: single pairs through the separate launches (measurement aid)
   int one_groups_want = 0;       // SMHIP_ONE_GROUPS: groups of its barrier (tuning)
   int one_blocks_want = 0;       // SMHIP_ONE_BLOCKS: its grid (tuning; 0 = as many as a round each needs, at most what is resident)
+  int one_pairs_max = kOnePairs; // SMHIP_ONE_PAIRS: pairs one launch of it may hold (1 = single pairs only)
+  int one_idle = 0;              // SMHIP_ONE_IDLE: with SMHIP_ONE_BLOCKS, keep a grid of mostly idle workgroups on small clouds (tests)
+  int one_no_retry = 0;          // SMHIP_ONE_NO_RETRY: a launch that stopped itself is reported, not done again (fetch_range)
   int wave_search = 0;           // batches: the every-query-searches iterations through nn_ball_lds (0, default: 5-25 % faster on the bench scans)
                                  // or nn_ball_wave (1; SMHIP_WAVE_SEARCH=1) -- same results
   float4* stage = nullptr;       // pinned staging for uploads, 2 * max(ns_cap, nt_cap)
@@ -131,10 +137,7 @@ smhip_status dev_alloc(smhip_context* h, T** p, size_t count) {
   return SMHIP_OK;
 }
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// profiling brackets: category 0 prepare, 1 the refinement launches of FindClosests (validate / ring / fallback), 2 error_elements,
-// 3 solve, 4 the main NN kernel (fused search, or the full libnabo walk), 5 the certificate pass, 6 the listed search / list walk
+// profiling brackets around launches of one category (plan::Category)
 struct Bracket {
   smhip_context* h;
   smhip_context::Ev* ev = nullptr;
@@ -201,7 +204,7 @@ struct Half {
   IcpDev d;
   hipStream_t stream;
   int np;
-  bool small = false;      // few workgroups per launch: use the single-round NN / short-chunk accumulate variants
+  plan::Part part;         // how its launches size themselves (enqueue_range)
   int first_fused = -1;    // the first iteration of this Align that ran the fused path
 };
 
@@ -248,7 +251,7 @@ smhip_status kd_ensure(smhip_context* h) {
 smhip_status enqueue_grid_build(smhip_context* h, const Half& f, int nt_max) {
   const IcpDev& d = f.d;
   const int np = f.np;
-  Bracket br(h, 0, f.stream);
+  Bracket br(h, plan::kCatPrepare, f.stream);
   const dim3 gpts(ceil_div(nt_max, 256), np);
   hipLaunchKernelGGL(tgt_reduce, dim3(kTgtReduceBlocks, np), dim3(256), 0, f.stream, d);
   hipLaunchKernelGGL(grid_setup, dim3(ceil_div(np, 64)), dim3(64), 0, f.stream, d, np);
@@ -298,21 +301,24 @@ bool grid_cached(smhip_context* h, int slot) {
          h->grid_rows[slot] >= (h->dev.use_ball ? 0 : 1);
 }
 
-// single-pair form of enqueue_resets + enqueue_grid_build that skips the build when the slot's target is unchanged
-smhip_status enqueue_prepare_one(smhip_context* h, int slot, int nt_max) {
-  if (!grid_cached(h, slot)) {
-    smhip_status s = enqueue_resets(h, 1, slot);
-    if (s) return s;
-    return enqueue_grid_build(h, whole_batch(h, 1, slot), nt_max);
-  }
-  IcpDev d = h->dev; d.npairs = 1; d.pair_base = slot; d.have_rowbits = h->dev.use_ball ? 0 : 1;
-  HIPCHK(h, hipMemcpyAsync(const_cast<PairInput*>(d.in) + slot, h->in_pinned + slot, sizeof(PairInput), hipMemcpyHostToDevice, h->stream));
-  { smhip_status ps = ensure_packed(h, slot, 1); if (ps) return ps; }
-  hipLaunchKernelGGL(reset_scratch_light, dim3(8), dim3(256), 0, h->stream, d, slot, 1);
-  hipLaunchKernelGGL(pose_setup, dim3(1), dim3(64), 0, h->stream, d, 1);
+// "target kept" prepare of slots [first, first + K), whose search structures are all current: pair inputs, pose and the light scratch reset
+smhip_status enqueue_prepare_kept(smhip_context* h, int first, int K) {
+  const IcpDev d = whole_batch(h, K, first).d;
+  HIPCHK(h, hipMemcpyAsync(const_cast<PairInput*>(d.in) + first, h->in_pinned + first, sizeof(PairInput) * K, hipMemcpyHostToDevice, h->stream));
+  { smhip_status ps = ensure_packed(h, first, K); if (ps) return ps; }
+  hipLaunchKernelGGL(reset_scratch_light, dim3(std::min(1024, 8 * K)), dim3(256), 0, h->stream, d, first, K);
+  hipLaunchKernelGGL(pose_setup, dim3(ceil_div(K, 64)), dim3(64), 0, h->stream, d, K);
   HIPCHK(h, hipGetLastError());
   h->cache_hits++;
   return SMHIP_OK;
+}
+
+// single-pair form of enqueue_resets + enqueue_grid_build that skips the build when the slot's target is unchanged
+smhip_status enqueue_prepare_one(smhip_context* h, int slot, int nt_max) {
+  if (grid_cached(h, slot)) return enqueue_prepare_kept(h, slot, 1);
+  smhip_status s = enqueue_resets(h, 1, slot);
+  if (s) return s;
+  return enqueue_grid_build(h, whole_batch(h, 1, slot), nt_max);
 }
 
 Half whole_batch(smhip_context* h, int np, int first) {
@@ -331,182 +337,95 @@ smhip_status enqueue_prepare(smhip_context* h, int np, int nt_max) {
   return enqueue_grid_build(h, whole_batch(h, np, 0), nt_max);
 }
 
-smhip_status enqueue_find_closests_half(smhip_context* h, const Half& f, int ns_max, int iteration);
-
 inline int nt_max_of(const smhip_context* h, int first, int np) {
   int m = 0;
   for (int p = first; p < first + np; ++p) m = std::max(m, h->nt[p]);
   return m;
 }
 
-smhip_status enqueue_find_closests(smhip_context* h, int np, int ns_max) {
-  return enqueue_find_closests_half(h, whole_batch(h, np, 0), ns_max, 0);
+// the settings the plan reads, as they stand now (callers that patch h->dev or h->opts around a search patch the plan's inputs)
+plan::Inputs plan_inputs(const smhip_context* h) {
+  plan::Inputs in;
+  in.nn_mode = h->opts.nn_mode;
+  in.use_ball = h->dev.use_ball; in.lds_table = h->dev.lds_table; in.certify = h->dev.certify; in.exact_all = h->dev.exact_all;
+  in.split_after = h->dev.split_after; in.split_after_option = h->opts.split_after;
+  in.no_fused_sums = h->opts.no_fused_sums; in.no_single_kernel = h->opts.no_single_kernel;
+  in.no_overlap = h->opts.no_overlap; in.overlap_streams = h->opts.overlap_streams;
+  in.nabo_fused_from = h->nabo_fused_from; in.sums_long_for = h->sums_long_for; in.use_shadow = h->use_shadow; in.wave_search = h->wave_search;
+  in.sums_blocks = h->sums_blocks; in.nabo_listed_blocks = h->nabo_listed_blocks;
+  in.one_enabled = h->one_enabled; in.one_blocks_want = h->one_blocks_want; in.one_groups_want = h->one_groups_want;
+  in.one_idle = h->one_idle; in.one_pairs_max = h->one_pairs_max; in.one_blocks = h->one_blocks;
+  in.profiling = h->profile != 0;
+  in.part_stride = h->dev.part_stride; in.seg_stride = h->dev.seg_stride;
+  in.side_streams = h->n_side;
+  return in;
 }
 
-smhip_status enqueue_find_closests_half(smhip_context* h, const Half& f, int ns_max, int iteration) {
+// launches what a plan names, in its order, on the part's stream
+smhip_status enqueue_launches(smhip_context* h, const Half& f, const plan::Iteration& it) {
+  using K = plan::Kernel;
   const IcpDev& d = f.d;
-  const int np = f.np;
   hipStream_t st = f.stream;
-  const dim3 g(ceil_div(ns_max, kNnThreads), np);
-  if (h->opts.nn_mode == SMHIP_NN_NABO) {
-    // knn(k = 1, epsilon) through libnabo's tree: what it returns IS the match (no bounds, nothing to refine).  Iteration 0
-    // walks every query and records its traversal certificate; later iterations re-walk only the queries that have moved
-    // further than their certificate allows (nabo_kernels.hip)
-    KdDev kd = h->kd;
-    const float e = h->opts.nn_epsilon >= 0.f ? h->opts.nn_epsilon : 3.16f;
-    kd.max_error2 = (1.0f + e) * (1.0f + e);
-    const int nb1 = ceil_div(ns_max, kNnThreads);
-    const bool shallow = nt_max_of(h, d.pair_base, np) <= (kKdBucket << 12);     // 12 stack levels (40 KiB of LDS) cover the target
-    if (d.certify && iteration > 0) {
-      {
-        Bracket br(h, 5, st, np);
-        if (f.small) {
-          hipLaunchKernelGGL((nn_certify<1, true>), dim3(nb1 * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nb1);
-        } else if (d.fused) {
-          // certificate pass + the sums below the predicted quantile band in one pass over the source (fused_iteration decides)
-          const int nbc = ceil_div(ns_max, kNnThreads * kCertifyItems);
-          hipLaunchKernelGGL((nn_certify_acc<kCertifyItems, true>), dim3(nbc * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nbc);
-        } else {
-          const int nbc = ceil_div(ns_max, kNnThreads * kCertifyItems);
-          hipLaunchKernelGGL((nn_certify<kCertifyItems, true>), dim3(nbc * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nbc);
-        }
-      }
-      {
-        Bracket br(h, 6, st, np);
-        const int nbl = f.small ? nb1 : h->nabo_listed_blocks;
-        const dim3 gl(nbl * 8 * ceil_div(np, 8));
-        if (shallow) hipLaunchKernelGGL((nn_nabo<1, true, 12>), gl, dim3(kNnThreads), 0, st, d, kd, nbl);
-        else hipLaunchKernelGGL((nn_nabo<1, true, kKdStack>), gl, dim3(kNnThreads), 0, st, d, kd, nbl);
-      }
-      if (d.fused) {
-        // the walked queries by the fused pass's rule, and the check of its prediction (this mode's nn_validate)
-        Bracket br(h, 1, st);
-        hipLaunchKernelGGL(nabo_validate, dim3(np), dim3(kAccThreads), 0, st, d);
-        hipLaunchKernelGGL(accumulate_listed, dim3(kNaboAccBlocks, np), dim3(kAccThreads), 0, st, d);
-      }
-    } else {
-      Bracket br(h, 4, st, np);
-      if (f.small) {
-        const dim3 g1(nb1 * 8 * ceil_div(np, 8));
-        if (shallow) hipLaunchKernelGGL((nn_nabo<1, false, 12>), g1, dim3(kNnThreads), 0, st, d, kd, nb1);
-        else hipLaunchKernelGGL((nn_nabo<1, false, kKdStack>), g1, dim3(kNnThreads), 0, st, d, kd, nb1);
-      } else {
-        const int nb4 = ceil_div(ns_max, kNnThreads * 4);
-        const dim3 g4(nb4 * 8 * ceil_div(np, 8));
-        if (shallow) hipLaunchKernelGGL((nn_nabo<4, false, 12>), g4, dim3(kNnThreads), 0, st, d, kd, nb4);
-        else hipLaunchKernelGGL((nn_nabo<4, false, kKdStack>), g4, dim3(kNnThreads), 0, st, d, kd, nb4);
-      }
+  KdDev kd = h->kd;
+  const float e = h->opts.nn_epsilon >= 0.f ? h->opts.nn_epsilon : 3.16f;
+  kd.max_error2 = (1.0f + e) * (1.0f + e);
+  constexpr int kShallow = plan::kNaboShallowLevels;
+  const dim3 nn(kNnThreads), acc(kAccThreads), t256(256);
+  std::optional<Bracket> br;
+  for (int i = 0; i < it.n; ++i) {
+    const plan::Launch& l = it.launch[i];
+    if (!l.same_bracket) { br.reset(); br.emplace(h, l.cat, st, f.np); }
+    const dim3 g(l.gx, l.gy);
+    switch (l.kernel) {
+      case K::NaboCertifyOne:     hipLaunchKernelGGL((nn_certify<1, true>), g, nn, 0, st, d, l.nb); break;
+      case K::NaboCertifyAcc:     hipLaunchKernelGGL((nn_certify_acc<kCertifyItems, true>), g, nn, 0, st, d, l.nb); break;
+      case K::NaboCertify:        hipLaunchKernelGGL((nn_certify<kCertifyItems, true>), g, nn, 0, st, d, l.nb); break;
+      case K::NaboListedShallow:  hipLaunchKernelGGL((nn_nabo<1, true, kShallow>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::NaboListedDeep:     hipLaunchKernelGGL((nn_nabo<1, true, kKdStack>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::NaboValidate:       hipLaunchKernelGGL(nabo_validate, g, acc, 0, st, d); break;
+      case K::AccumulateListed:   hipLaunchKernelGGL(accumulate_listed, g, acc, 0, st, d); break;
+      case K::NaboOneShallow:     hipLaunchKernelGGL((nn_nabo<1, false, kShallow>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::NaboOneDeep:        hipLaunchKernelGGL((nn_nabo<1, false, kKdStack>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::NaboFourShallow:    hipLaunchKernelGGL((nn_nabo<4, false, kShallow>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::NaboFourDeep:       hipLaunchKernelGGL((nn_nabo<4, false, kKdStack>), g, nn, 0, st, d, kd, l.nb); break;
+      case K::BallLdsOne:         hipLaunchKernelGGL(nn_ball_lds<1>, g, nn, 0, st, d, l.nb); break;
+      case K::BallWaveFirst:      hipLaunchKernelGGL((nn_ball_wave<kBallItems, true>), g, nn, 0, st, d, l.nb); break;
+      case K::BallWave:           hipLaunchKernelGGL((nn_ball_wave<kBallItems, false>), g, nn, 0, st, d, l.nb); break;
+      case K::BallLdsFirst:       hipLaunchKernelGGL((nn_ball_lds<kBallItems, true>), g, nn, 0, st, d, l.nb); break;
+      case K::BallLds:            hipLaunchKernelGGL(nn_ball_lds<kBallItems>, g, nn, 0, st, d, l.nb); break;
+      case K::CertifyAccShadow:   hipLaunchKernelGGL((nn_certify_acc<kCertifyItems, false, true>), g, nn, 0, st, d, l.nb); break;
+      case K::CertifyAcc:         hipLaunchKernelGGL(nn_certify_acc<kCertifyItems>, g, nn, 0, st, d, l.nb); break;
+      case K::CertifyOne:         hipLaunchKernelGGL(nn_certify<1>, g, nn, 0, st, d, l.nb); break;
+      case K::Certify:            hipLaunchKernelGGL(nn_certify<kCertifyItems>, g, nn, 0, st, d, l.nb); break;
+      case K::ListedPlan:         hipLaunchKernelGGL(listed_plan, g, t256, 0, st, d); break;
+      case K::BallListedItems:    hipLaunchKernelGGL(nn_ball_listed_items, g, nn, 0, st, d); break;
+      case K::BallListed:         hipLaunchKernelGGL(nn_ball_listed, g, nn, 0, st, d, l.nb); break;
+      case K::Ball:               hipLaunchKernelGGL(nn_ball, g, nn, 0, st, d, l.nb); break;
+      case K::RefineOne:          hipLaunchKernelGGL(nn_refine_one, g, nn, 0, st, d); break;
+      case K::Validate:           hipLaunchKernelGGL(nn_validate, g, t256, 0, st, d); break;
+      case K::RingRefine:         hipLaunchKernelGGL(nn_ring<true>, g, nn, 0, st, d); break;
+      case K::RingCoop:           hipLaunchKernelGGL(nn_ring_coop, g, nn, 0, st, d); break;
+      case K::RingWide:           hipLaunchKernelGGL(nn_ring_wide, g, nn, 0, st, d); break;
+      case K::Ring:               hipLaunchKernelGGL(nn_ring<false>, g, nn, 0, st, d); break;
+      case K::Fallback:           hipLaunchKernelGGL(nn_fallback, g, nn, 0, st, d); break;
+      case K::Brute:              hipLaunchKernelGGL(nn_brute, g, nn, 0, st, d); break;
+      case K::IterationSumsBatch: hipLaunchKernelGGL(iteration_sums<kAccItemsBatch>, g, acc, 0, st, d); break;
+      case K::IterationSumsSmall: hipLaunchKernelGGL(iteration_sums<kAccItemsSmall>, g, acc, 0, st, d); break;
+      case K::AccumulateBatch:    hipLaunchKernelGGL(accumulate<kAccItemsBatch>, g, acc, 0, st, d, l.nb); break;
+      case K::AccumulateSmall:    hipLaunchKernelGGL(accumulate<kAccItemsSmall>, g, acc, 0, st, d, l.nb); break;
+      case K::Finalize:           hipLaunchKernelGGL(finalize, g, t256, 0, st, d); break;
     }
-  } else if (h->opts.nn_mode == SMHIP_NN_GRID) {
-    if (d.use_ball) {
-      const int nblk = ceil_div(ns_max, kNnThreads * kBallItems);
-      const dim3 gx(nblk * 8 * ceil_div(np, 8));
-      const dim3 glist(kListedBlocks * 8 * ceil_div(np, 8));
-      // the two-launch form pays from ~16 pairs per launch on (measured with the many-lanes-per-query listed search: equal for
-      // one pair, +4 % at 16, +1 % at 32, +6 % at 2 x 32, +9 % at 256 pairs); an explicit split_after option is honoured
-      // for any size
-      const bool split_now = d.certify && iteration >= d.split_after && (h->opts.split_after > 0 || np >= 16);
-      if (d.lds_table && !split_now) {
-        // certificate, in-workgroup compaction of the failing queries and LDS-staged search in one launch
-        Bracket br(h, 4, st, np);
-        if (f.small) {
-          const int nb1 = ceil_div(ns_max, kNnThreads);
-          hipLaunchKernelGGL(nn_ball_lds<1>, dim3(nb1 * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nb1);
-        } else if (h->wave_search) {
-          // a wave per 64 queries walks the box of its balls once, candidates broadcast from the wave's LDS strip (nn_ball_wave)
-          if (iteration == 0) hipLaunchKernelGGL((nn_ball_wave<kBallItems, true>), gx, dim3(kNnThreads), 0, st, d, nblk);
-          else hipLaunchKernelGGL((nn_ball_wave<kBallItems, false>), gx, dim3(kNnThreads), 0, st, d, nblk);
-        } else if (iteration == 0) {
-          hipLaunchKernelGGL((nn_ball_lds<kBallItems, true>), gx, dim3(kNnThreads), 0, st, d, nblk);
-        } else {
-          hipLaunchKernelGGL(nn_ball_lds<kBallItems>, gx, dim3(kNnThreads), 0, st, d, nblk);
-        }
-      } else if (d.certify && iteration > 0) {
-        // global-memory variant: certificate pass, then a search over the compacted failing queries
-        // (also what the converged iterations of the LDS variant use: a streaming certificate pass at full occupancy and a
-        // near-empty listed search beat the fused kernel once only a handful of certificates fail)
-        {
-          Bracket br(h, d.lds_table ? 5 : 4, st, np);
-          if (d.fused) {
-            // certificate pass + the sums below the predicted quantile band in one pass over the source (fused_iteration decides)
-            const int nbc = ceil_div(ns_max, kNnThreads * kCertifyItems);
-            // (every target of the launch below 32 767 points: the 4-byte shadow of bound + match instead of the two arrays.  Only behind
-            // the LDS-table ball search, whose kernels -- with the listed search and the refinement kernels -- write the shadow with every
-            // match (st_match); nn_ring_wide, nn_brute and nn_nabo set idx / lb alone and never run in such an Align)
-            if (h->use_shadow && d.lds_table && nt_max_of(h, d.pair_base, np) < 0x7fff)
-              hipLaunchKernelGGL((nn_certify_acc<kCertifyItems, false, true>), dim3(nbc * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nbc);
-            else
-              hipLaunchKernelGGL(nn_certify_acc<kCertifyItems>, dim3(nbc * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nbc);
-          } else if (f.small) {
-            const int nb1 = ceil_div(ns_max, kNnThreads);
-            hipLaunchKernelGGL(nn_certify<1>, dim3(nb1 * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nb1);
-          } else {
-            const int nbc = ceil_div(ns_max, kNnThreads * kCertifyItems);
-            hipLaunchKernelGGL(nn_certify<kCertifyItems>, dim3(nbc * 8 * ceil_div(np, 8)), dim3(kNnThreads), 0, st, d, nbc);
-          }
-        }
-        {
-          Bracket br(h, 6, st, np);
-          if (d.fused) {
-            // the lists' lengths differ by an order of magnitude between the pairs of a launch: cut into equal items first
-            hipLaunchKernelGGL(listed_plan, dim3(np), dim3(256), 0, st, d);
-            hipLaunchKernelGGL(nn_ball_listed_items, dim3(kListedItemBlocks), dim3(kNnThreads), 0, st, d);
-          } else {
-            hipLaunchKernelGGL(nn_ball_listed, glist, dim3(kNnThreads), 0, st, d, kListedBlocks);
-          }
-        }
-      } else {
-        Bracket br(h, 4, st, np);
-        hipLaunchKernelGGL(nn_ball, gx, dim3(kNnThreads), 0, st, d, nblk);
-      }
-      if ((f.small || d.fused) && !d.exact_all) {
-        // a few pairs: validate + ring + fallback as ONE launch, a workgroup per pair (near-empty launches cost ~5 us each there).
-        // The same in a batch's fused iterations: the pose has settled there, a quantile that reaches a lower bound is the rare
-        // case, and the two spread-out launches cost 20-25 us each of a ~700 us iteration whether they do anything or not
-        // (8 192 and 16 384 workgroups that look at one flag).
-        Bracket br(h, 1, st);
-        hipLaunchKernelGGL(nn_refine_one, dim3(np), dim3(kNnThreads), 0, st, d);
-        return SMHIP_OK;
-      }
-      { Bracket br(h, 1, st); hipLaunchKernelGGL(nn_validate, dim3(np), dim3(256), 0, st, d); }
-      { Bracket br(h, 1, st); hipLaunchKernelGGL(nn_ring<true>, dim3(32, np), dim3(kNnThreads), 0, st, d); }
-    } else if ((long long)np * ns_max < (1ll << 21)) {
-      // few queries in the whole launch: several lanes per query keep the SIMDs busy
-      Bracket br(h, 4, st, np);
-      hipLaunchKernelGGL(nn_ring_coop, dim3(ceil_div(ns_max, kNnThreads / kCoopLanes), np), dim3(kNnThreads), 0, st, d);
-      hipLaunchKernelGGL(nn_ring_wide, dim3(kWideBlocks, np), dim3(kNnThreads), 0, st, d);
-    } else {
-      Bracket br(h, 4, st, np);
-      hipLaunchKernelGGL(nn_ring<false>, g, dim3(kNnThreads), 0, st, d);
-    }
-    { Bracket br(h, 1, st); hipLaunchKernelGGL(nn_fallback, dim3(kFallbackSlices, np), dim3(kNnThreads), 0, st, d); }
-  } else {
-    Bracket br(h, 4, st, np);
-    hipLaunchKernelGGL(nn_brute, g, dim3(kNnThreads), 0, st, d);
   }
   return SMHIP_OK;
 }
 
-// Does iteration `iteration` of this batch part run the fused path (nn_certify_acc + nn_ball_listed_items: certificate pass and
-// normal-equation sums in one pass over the source)?  Exactly where the two-launch certificate form runs in a batch, unless every
-// bound is refined in every iteration anyway (nothing to speculate on) or the cloud has more record segments than finalize indexes.
-bool fused_iteration(const smhip_context* h, const Half& f, int ns_max, int iteration) {
-  const IcpDev& d = f.d;
-  if (h->opts.nn_mode == SMHIP_NN_NABO) {
-    // the reference-search form: every certificate iteration of a batch (the walk has no bounds to refine); rows of partials for
-    // the certificate pass's workgroups + accumulate_listed's
-    // ... from the iteration on in which the previous batch's median pair walked fewer than a fifth of its queries again: the walked
-    // queries are summed from their lists (accumulate_listed: scattered reads, ten times a streamed point's bytes), which only
-    // pays once they are few; before that `accumulate` streams every point
-    if (!d.certify || h->opts.no_fused_sums || f.small || iteration < std::max(1, h->nabo_fused_from) || f.np < 16) return false;
-    const int nbc = ceil_div(ns_max, kNnThreads * kCertifyItems);
-    return nbc + kNaboAccBlocks <= d.part_stride && nbc * (kNnThreads / 64) + kNaboAccBlocks * (kAccThreads / 64) <= std::min(kFinalizeMaxSeg, (int)d.seg_stride);
-  }
-  if (h->opts.nn_mode != SMHIP_NN_GRID || !d.use_ball || !d.lds_table || !d.certify || h->opts.no_fused_sums || d.exact_all || f.small) return false;
-  if (iteration < 1 || iteration < d.split_after || !(h->opts.split_after > 0 || f.np >= 16)) return false;
-  if (f.np > kListedMaxPairs) return false;
-  // finalize's segment table: the certificate pass's waves + the listed search's items of a list nn_validate accepts
-  return ceil_div(ns_max, kNnThreads * kCertifyItems) * (kNnThreads / 64) + kListedMaxItems <= std::min(kFinalizeMaxSeg, (int)d.seg_stride);
+// FindClosests outside an Align (find_closests, the GICP correspondences): iteration 0 of one launch over pairs [f.d.pair_base, + f.np)
+smhip_status enqueue_find_closests_half(smhip_context* h, const Half& f, int ns_max) {
+  return enqueue_launches(h, f, plan::plan_search_only(plan_inputs(h), plan::whole_part(f.np, nt_max_of(h, f.d.pair_base, f.np)), ns_max));
+}
+
+smhip_status enqueue_find_closests(smhip_context* h, int np, int ns_max) {
+  return enqueue_find_closests_half(h, whole_batch(h, np, 0), ns_max);
 }
 
 smhip_status fill_inputs(smhip_context* h, int np, const double* guesses, int* ns_max, int* nt_max, int first = 0) {
@@ -562,6 +481,9 @@ void sync_options(smhip_context* h) {
   h->one_enabled = 1; h->one_blocks_want = 0;
   { const char* e = std::getenv("SMHIP_ONE_PAIR"); if (e) h->one_enabled = std::atoi(e); }
   { const char* e = std::getenv("SMHIP_ONE_BLOCKS"); if (e) h->one_blocks_want = std::atoi(e); }
+  { const char* e = std::getenv("SMHIP_ONE_PAIRS"); h->one_pairs_max = e ? std::min(std::max(std::atoi(e), 1), kOnePairs) : kOnePairs; }
+  h->one_idle = std::getenv("SMHIP_ONE_IDLE") != nullptr;
+  h->one_no_retry = std::getenv("SMHIP_ONE_NO_RETRY") != nullptr;
   h->one_groups_want = 0;
   { const char* e = std::getenv("SMHIP_ONE_GROUPS"); if (e) h->one_groups_want = std::atoi(e); }
   h->sums_blocks = kSumsBlocks;
@@ -647,8 +569,8 @@ smhip_status smhip_create(int device, void* stream, int pair_slots, int max_sour
                           smhip_handle* out) {
   if (!out || pair_slots < 1 || max_source_points < 1 || max_target_points < 1) return SMHIP_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  // finalize indexes at most kFinalizeMaxSeg accumulate waves per pair: 4 Mi source points per cloud
-  if (max_source_points > kFinalizeMaxSeg * 64 * kAccItemsBatch) return SMHIP_ERR_INVALID_ARGUMENT;
+  const plan::Capacities cap = plan::plan_capacities(max_source_points);
+  if (!cap.ok) return SMHIP_ERR_INVALID_ARGUMENT;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SMHIP_ERR_NO_DEVICE;
   hipDeviceProp_t prop;
@@ -668,16 +590,8 @@ smhip_status smhip_create(int device, void* stream, int pair_slots, int max_sour
   smhip_icp_default_options(&h->opts);
   IcpDev& d = h->dev;
   d.slots = pair_slots; d.ns_cap = max_source_points; d.nt_cap = max_target_points;
-  d.acc_blocks = ceil_div(max_source_points, kAccThreads * kAccItemsSmall);
+  d.acc_blocks = cap.acc_blocks; d.part_stride = cap.part_stride; d.dl_stride = cap.dl_stride; d.bl_stride = cap.bl_stride; d.seg_stride = cap.seg_stride;
   d.acc_items = kAccItemsSmall;
-  // rows of partials: accumulate's workgroups, or the fused certificate pass's plus accumulate_listed's (reference-search mode)
-  d.part_stride = std::max(d.acc_blocks, ceil_div(max_source_points, kNnThreads * kCertifyItems) + std::max(kNaboAccBlocks, kFusedListedMax / kListedSumChunk));
-  d.dl_stride = ceil_div(max_source_points, kNnThreads * kCertifyItems) * (kNnThreads * kCertifyItems);
-  d.bl_stride = std::max(ceil_div(max_source_points, kAccThreads * kAccItemsBatch) * (kAccThreads * kAccItemsBatch), d.dl_stride);
-  // one segment per producing wave: accumulate with short chunks makes the most; the fused path has its certificate pass's waves
-  // plus the listed search's
-  d.seg_stride = std::max(d.acc_blocks * (kAccThreads / 64),
-                          ceil_div(max_source_points, kNnThreads * kCertifyItems) * (kNnThreads / 64) + std::max(kListedBlocks * (kNnThreads / 64), kListedMaxItems) + 1);
   const size_t B = pair_slots, NS = max_source_points, NT = max_target_points;
   smhip_status s = SMHIP_OK;
   auto A = [&](smhip_status r) { if (s == SMHIP_OK) s = r; };
@@ -1178,7 +1092,7 @@ smhip_status smhip_copy_slot(smhip_handle h, int from, int to) {
 // fewer side streams than asked for = less overlap, still correct
 static void ensure_side_streams(smhip_context* h, int n) {
   if (!h->ev_fork) return;
-  for (int k = h->n_side; k < n && k < smhip_context::kMaxParts - 1; ++k) {
+  for (int k = h->n_side; k < n && k < plan::kMaxParts - 1; ++k) {
     if (hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking) != hipSuccess) { h->side[k] = nullptr; return; }
     if (hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(h->side[k]); h->side[k] = nullptr; return; }
     h->n_side = k + 1;
@@ -1198,48 +1112,32 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
   smhip_status s = fill_inputs(h, npairs, guesses, &ns_max, &nt_max, first);
   if (s) return s;
   if (h->hist_pairs > 0) {
-    // the previous batch is complete (stream synchronised above): the first iteration k >= 1 in which the median pair searched
-    // fewer than a fifth of its queries is where certify + listed search starts to beat the fused kernel (measured: the listed
-    // search costs ~1 ms per 64 pairs with every query listed, the fused kernel 0.25-0.35 ms whatever the share)
-    int k = 1;
-    std::vector<float> share((size_t)h->hist_pairs);
-    for (; k < std::min(h->hist_iters, kSearchHist); ++k) {
-      for (int p = 0; p < h->hist_pairs; ++p) share[p] = (float)h->hist_pinned[(size_t)p * kSearchHist + k] / (float)std::max(1, h->hist_ns[p]);
-      std::nth_element(share.begin(), share.begin() + share.size() / 2, share.end());
-      if (share[share.size() / 2] < h->split_share) break;
-    }
-    if (h->hist_mode == SMHIP_NN_NABO) h->nabo_fused_from = std::max(1, std::min(k, 12));   // (see fused_iteration)
-    else h->auto_split = std::max(1, std::min(k, 8));         // 8: from there on the two-launch form won on every workload measured
+    // the previous batch is complete (stream synchronised above): its searched shares place this one's switch to the two-launch form
+    const int k = plan::split_from_history(h->hist_pinned, h->hist_ns.data(), h->hist_pairs, h->hist_iters, h->split_share);
+    if (h->hist_mode == SMHIP_NN_NABO) h->nabo_fused_from = plan::clamp_split(k, plan::kNaboFusedFromMax);
+    else h->auto_split = plan::clamp_split(k, plan::kAutoSplitMax);
     h->hist_pairs = 0;
   }
   if (h->opts.split_after == 0) h->dev.split_after = h->auto_split;
-  h->prof.split_after_used = npairs >= 16 && h->dev.certify ? h->dev.split_after : 0;
   const bool cached_one = npairs == 1 && grid_cached(h, first);
   if (cached_one) s = enqueue_prepare_one(h, first, nt_max);     // target unchanged: pose + scratch reset only
   else s = enqueue_resets(h, npairs, first);
   if (s) return s;
   // Split the batch over several streams: the latency-bound launches of one part (finalize, validate, grid
   // build, near-empty refinement kernels) overlap the throughput-bound NN / accumulate of the others.
-  // Parts are multiples of 8 pairs (the XCD mapping) and at least 16 pairs each.
-  // (default two.  Measured on 512-pair batches with the fixed-grid tail kernels of round 5: 2 / 3 / 4 parts = 25.3 / 25.9 / 26.0 k
-  // alignments/s, identity guesses 15.3 / 15.8 / 15.7 k, mixed 17.4 / 18.1 / 18.4 k -- overlap_streams = 4 is worth 1.5-5 % there; the
-  // sequence driver's 256-pair batches lose 12 % with four parts of 64 pairs, so the default stays where every batch size is served)
-  int want = h->opts.no_overlap ? 1 : (h->opts.overlap_streams > 0 ? h->opts.overlap_streams : 2);
-  want = std::min(want, smhip_context::kMaxParts);
-  if (want > 1 && npairs >= 32) ensure_side_streams(h, want - 1);
-  want = std::min(want, 1 + h->n_side);
-  while (want > 1 && npairs < 16 * want) --want;
-  Half halves[smhip_context::kMaxParts];
-  int nh = want;
-  {
-    int done = 0;
-    for (int k = 0; k < nh; ++k) {
-      int np = (k == nh - 1) ? npairs - done : (((npairs - done) / (nh - k) + 7) / 8) * 8;
-      np = std::min(np, npairs - done);
-      halves[k] = whole_batch(h, np, first + done);
-      halves[k].stream = k == 0 ? h->stream : h->side[k - 1];
-      done += np;
-    }
+  plan::Inputs in = plan_inputs(h);
+  if (const int want = plan::parts_wanted(in, npairs); want > 1) { ensure_side_streams(h, want - 1); in.side_streams = h->n_side; }
+  const plan::Batch batch = plan::plan_batch(in, npairs, ns_max, nt_max);
+  h->prof.split_after_used = batch.split_after_used;
+  Half halves[plan::kMaxParts];
+  const int nh = batch.nparts;
+  for (int k = 0; k < nh; ++k) {
+    const plan::Part& p = batch.part[k];
+    halves[k] = whole_batch(h, p.np, first + p.first);
+    halves[k].stream = k == 0 ? h->stream : h->side[k - 1];
+    halves[k].part = p;
+    halves[k].part.nt_max = nt_max_of(h, first + p.first, p.np);
+    halves[k].d.acc_items = p.acc_items;
   }
   auto fork = [&]() -> smhip_status {
     if (nh > 1) {
@@ -1257,86 +1155,33 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
   };
   s = fork();
   if (s) return s;
-  for (int k = 0; k < nh; ++k) {   // launches of fewer than ~2 workgroups per CU take the small-launch kernel variants
-    halves[k].small = halves[k].np * ceil_div(ns_max, kNnThreads * kBallItems) < 512;
-    // long accumulate chunks once they still leave >= 3 workgroups per CU
-    // (or when short chunks would make more segments than finalize indexes)
-    halves[k].d.acc_items = (halves[k].np * ceil_div(ns_max, kAccThreads * kAccItemsBatch) >= 768 ||
-                             ceil_div(ns_max, kAccThreads * kAccItemsSmall) * (kAccThreads / 64) > kFinalizeMaxSeg) ? kAccItemsBatch : kAccItemsSmall;
-  }
   const int max_it = h->dev.max_iteration;
   bool grid_built = false;
-  // One pair (the front end's call, map_builder.cc:317-333): the whole loop and the score as ONE cooperative launch whose workgroups
-  // meet at grid barriers (icp_one.hip) -- the same matches, distances and kept sets as the launches below.
   h->one_used = 0;
-  // (up to kOnePairs pairs per launch, a row of the grid each: the back end's handful of concurrent submap pairs -- 6 pairs 1.40 ms
-  // against 1.71 as separate launches; SMHIP_ONE_PAIRS=n lowers the limit, 1 = single pairs only)
-  const int one_pairs_max = std::getenv("SMHIP_ONE_PAIRS") ? std::min(std::max(std::atoi(std::getenv("SMHIP_ONE_PAIRS")), 1), kOnePairs) : kOnePairs;
-  if (npairs <= one_pairs_max && h->one_blocks > 0 && !h->opts.no_single_kernel && h->one_enabled && h->opts.nn_mode == SMHIP_NN_GRID && h->dev.use_ball &&
-      h->dev.lds_table && h->dev.certify && !h->dev.exact_all && h->profile == 0) {
-    const int nrounds = ceil_div(ns_max, kNnThreads);
-    // two rounds of 256 points per workgroup (measured on 120 000 points, 20 iterations, target kept: 472 workgroups of one round
-    // 1.15-1.18 ms, 320: 1.11-1.15, 240: 1.06-1.11, 160: 1.04-1.13 -- a barrier waits for the slowest workgroup, and two rounds
-    // even out what one round's few searching queries cost); a multiple of 8: the barrier's groups.  Several pairs (up to
-    // kOnePairs: the back end's handful of concurrent submap pairs) share what the device holds at once, a row of the grid each.
-    int G = h->one_blocks_want > 0 ? std::max(8, (h->one_blocks_want / 8) * 8) : ((ceil_div(nrounds, 2) + 7) / 8) * 8;
-    if (!(h->one_blocks_want > 0 && std::getenv("SMHIP_ONE_IDLE"))) G = std::min(G, ((nrounds + 7) / 8) * 8);   // (SMHIP_ONE_IDLE: tests run small clouds on a grid of mostly idle workgroups)
-    if (G >= 64) G = ((G + 31) / 32) * 32;                 // (whole groups of the barrier; workgroups beyond the rounds only take part in the barriers)
-    G = std::min(G, ((h->one_blocks / npairs) / 8) * 8);
-    // (at most 12 rounds per workgroup -- the kernel holds up to kOneMaxRounds = 16 --: measured on 120 000-point pairs, 6 pairs at 12
-    // rounds 1.52 ms against 1.71 as separate launches, 8 pairs at 15 rounds 1.87 against 1.73)
-    if (G >= 8 && ceil_div(nrounds, G) <= std::min(12, kOneMaxRounds)) {
-      if (!cached_one) { s = enqueue_grid_build(h, halves[0], nt_max); if (s) return s; }
-      grid_built = true;
-      IcpDev d1 = halves[0].d;
-      d1.fused = 0; d1.fused_nabo = 0;
-      // the barrier's groups: 8 (measured on 256 / 480 workgroups: 8 or 16 groups equal, 32 groups 7 % slower -- the barriers wait for
-      // the slowest workgroup, not for their own atomics; SMHIP_ONE_GROUPS overrides)
-      int groups = 8;
-      if (h->one_groups_want > 0 && (h->one_groups_want & (h->one_groups_want - 1)) == 0 && h->one_groups_want <= 32 && G % h->one_groups_want == 0) groups = h->one_groups_want;
-      void* args[] = {&d1, &groups};
-      if (hipLaunchCooperativeKernel(reinterpret_cast<const void*>(icp_one), dim3(G, npairs), dim3(kNnThreads), args, 0, h->stream) == hipSuccess) {
-        h->one_used = 1;
-        h->one_launches += 1;
-        h->last_npairs = npairs;
-        return SMHIP_OK;
-      }
-      // the runtime refused the cooperative launch (it cannot place the grid): not an error of the Align -- the same iterations as
-      // separate launches below, and no further attempts on this handle
-      (void)hipGetLastError();
-      h->one_blocks = 0;
+  if (batch.one_launch) {      // the whole loop and the score as ONE cooperative launch (plan_batch)
+    if (!cached_one) { s = enqueue_grid_build(h, halves[0], nt_max); if (s) return s; }
+    grid_built = true;
+    IcpDev d1 = halves[0].d;
+    d1.fused = 0; d1.fused_nabo = 0;
+    int groups = batch.one_groups;
+    void* args[] = {&d1, &groups};
+    if (hipLaunchCooperativeKernel(reinterpret_cast<const void*>(icp_one), dim3(batch.one_grid, npairs), dim3(kNnThreads), args, 0, h->stream) == hipSuccess) {
+      h->one_used = 1;
+      h->one_launches += 1;
+      h->last_npairs = npairs;
+      return SMHIP_OK;
     }
+    // the runtime refused the cooperative launch (it cannot place the grid): not an error of the Align -- the same iterations as
+    // separate launches below, and no further attempts on this handle
+    (void)hipGetLastError();
+    h->one_blocks = 0;
   }
   // one iteration of one part: FindClosests, the sums, finalize
   auto enqueue_iteration = [&](Half& f, int it) -> smhip_status {
-    f.d.fused = fused_iteration(h, f, ns_max, it) ? 1 : 0;     // every launch of this iteration and part sees the same flag
-    f.d.fused_nabo = f.d.fused && h->opts.nn_mode == SMHIP_NN_NABO ? 1 : 0;
-    if (f.d.fused && !f.d.fused_nabo) {
-      // A band needs two quantiles: the iteration after the first has none, so no pair's sums can come from the fused pass -- the
-      // plain accumulate launch for all of them (fused = 0 for the sums only would change what finalize expects: keep the flag,
-      // it reads spec_ok = 0).  The next `sums_long_for` fused iterations most predictions still miss (the quantile moves by more
-      // than a bin): long blocks; after that short ones (iteration_sums).
-      f.first_fused = f.first_fused < 0 ? it : f.first_fused;
-      // (short blocks only while their record segments -- four per block -- fit finalize's table: clouds of up to a million points)
-      const bool short_fits = ceil_div(ns_max, kAccThreads * kAccItemsSmall) * (kAccThreads / 64) <= kFinalizeMaxSeg;
-      f.d.sums_items = (f.d.acc_items == kAccItemsBatch && (it - f.first_fused < h->sums_long_for || !short_fits)) ? kAccItemsBatch : kAccItemsSmall;
-      if (it < 2) f.d.sums_items = f.d.acc_items;
-    }
-    smhip_status r = enqueue_find_closests_half(h, f, ns_max, it);
-    if (r) return r;
-    {
-      Bracket br(h, 2, f.stream, f.np);
-      const int nblk = ceil_div(ns_max, kAccThreads * f.d.acc_items);
-      if (f.d.fused && !f.d.fused_nabo && it >= 2) {
-        // fused iteration: only the pairs whose prediction missed need `accumulate`, the others the sums of their listed matches --
-        // one fixed grid that takes both kinds of work (iteration_sums) instead of nblk workgroups per pair that look at a flag
-        if (f.d.sums_items == kAccItemsBatch) hipLaunchKernelGGL(iteration_sums<kAccItemsBatch>, dim3(h->sums_blocks), dim3(kAccThreads), 0, f.stream, f.d);
-        else hipLaunchKernelGGL(iteration_sums<kAccItemsSmall>, dim3(h->sums_blocks), dim3(kAccThreads), 0, f.stream, f.d);
-      } else if (f.d.acc_items == kAccItemsBatch) hipLaunchKernelGGL(accumulate<kAccItemsBatch>, dim3(nblk * 8 * ceil_div(f.np, 8)), dim3(kAccThreads), 0, f.stream, f.d, nblk);
-      else hipLaunchKernelGGL(accumulate<kAccItemsSmall>, dim3(nblk * 8 * ceil_div(f.np, 8)), dim3(kAccThreads), 0, f.stream, f.d, nblk);
-    }
-    { Bracket br(h, 3, f.stream); hipLaunchKernelGGL(finalize, dim3(f.np), dim3(256), 0, f.stream, f.d); }
-    return SMHIP_OK;
+    const plan::Iteration p = plan::plan_iteration(in, f.part, ns_max, it, f.first_fused);
+    f.first_fused = p.first_fused;
+    f.d.fused = p.fused; f.d.fused_nabo = p.fused_nabo; f.d.sums_items = p.sums_items;
+    return enqueue_launches(h, f, p);
   };
   // (The parts march in lock-step.  Tried in round 5: part k + 1 started two to five iterations behind part k, so that one part's
   // searching iterations -- bound by vector-instruction issue -- would run beside another's streaming ones -- bound by HBM: no gain
@@ -1362,15 +1207,13 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
   // the score of the iteration every pair left the loop with (icp_fast.cc:516-522), from that iteration's distances
   for (int k = 0; k < nh; ++k) {
     Half& f = halves[k];
-    Bracket br(h, 3, f.stream);
+    Bracket br(h, plan::kCatSolve, f.stream);
     hipLaunchKernelGGL(final_score, dim3(f.np * kScoreParts), dim3(kAccThreads), 0, f.stream, f.d);
     hipLaunchKernelGGL(score_fold, dim3(ceil_div(f.np, 256)), dim3(256), 0, f.stream, f.d, f.np);
   }
   s = join();
   if (s) return s;
-  // (only batches that ran the ball search with certificates say anything about where its two forms cross)
-  if (npairs >= 16 && h->dev.certify &&
-      ((h->opts.split_after == 0 && h->opts.nn_mode == SMHIP_NN_GRID && h->dev.use_ball && h->dev.lds_table) || h->opts.nn_mode == SMHIP_NN_NABO)) {
+  if (batch.record_history) {
     h->hist_mode = h->opts.nn_mode;
     HIPCHK(h, hipMemcpyAsync(h->hist_pinned, h->dev.search_hist + (size_t)first * kSearchHist, sizeof(uint32_t) * kSearchHist * (size_t)npairs,
                              hipMemcpyDeviceToHost, h->stream));
@@ -1389,7 +1232,7 @@ static smhip_status fetch_range(smhip_handle h, int first, int npairs, double* r
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipMemcpyAsync(h->state_pinned, h->dev.state + first, sizeof(PairState) * npairs, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->one_used && !std::getenv("SMHIP_ONE_NO_RETRY")) {
+  if (h->one_used && !h->one_no_retry) {
     // The cooperative launch stopped itself (its barrier watchdog or its workgroups' consistency check, icp_one.hip): never seen
     // on a single pair, but the protocol rests on the timing of agent-scope loads, not on fences -- so the Align is simply done
     // again as separate launches (whose result differs from the launch's in the sums' order: ~1e-15) and the handle keeps to them.

@@ -20,7 +20,7 @@ constexpr int kAccItemsBatch = 32;
 constexpr int kFinalizeKeyCap = 8192;     // band records whose keys finalize keeps in LDS between its radix-select passes
 constexpr int kFinalizeMaxSeg = 2048;     // record segments (one per producing wave) per pair finalize can index: 4 Mi source points at 32 per
                                           // accumulate thread; the fused path (kCertifyItems = 32 per thread, four segments per workgroup, + the listed search's
-                                          // kListedMaxItems = 129 items: fused_iteration() checks the sum) up to (2048 - 129) / 4 workgroups of 8 192 = 3.9 Mi points
+                                          // kListedMaxItems = 129 items: plan::fused_now() checks the sum) up to (2048 - 129) / 4 workgroups of 8 192 = 3.9 Mi points
 constexpr int kScoreParts = 16;          // workgroups per pair of final_score
 constexpr int kAccCols = 32;             // 21 (A upper) + 6 (b) + 1 (unused: the score is formed once, by final_score) + 1 (count) padded to 32
 constexpr int kMaxGridWords = 1 << 18;   // 32-cell words per pair (8 Mi cells)

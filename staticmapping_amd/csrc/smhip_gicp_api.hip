@@ -414,24 +414,18 @@ smhip_status gicp_round(smhip_context* h, int first, int K, const std::vector<Gi
       GicpSearchMode mode(h);
       bool cached = true;
       for (int p = first; p < first + K; ++p) cached = cached && grid_cached(h, p);
-      const Half f = whole_batch(h, K, first);
       if (cached) {
-        HIPCHK(h, hipMemcpyAsync(const_cast<PairInput*>(f.d.in) + first, h->in_pinned + first, sizeof(PairInput) * K, hipMemcpyHostToDevice, h->stream));
-        s = ensure_packed(h, first, K);
-        if (s) return s;
-        hipLaunchKernelGGL(reset_scratch_light, dim3(std::min(1024, 8 * K)), dim3(256), 0, h->stream, f.d, first, K);
-        hipLaunchKernelGGL(pose_setup, dim3(ceil_div(K, 64)), dim3(64), 0, h->stream, f.d, K);
-        h->cache_hits++;
+        s = enqueue_prepare_kept(h, first, K);
       } else {
         s = enqueue_resets(h, K, first);
-        if (s == SMHIP_OK) s = enqueue_grid_build(h, f, nt_max);
-        if (s) return s;
+        if (s == SMHIP_OK) s = enqueue_grid_build(h, whole_batch(h, K, first), nt_max);
       }
+      if (s) return s;
       h->dev.nn_cutoff2 = thr2;          // correspondences beyond the distance threshold are dropped anyway (gicp_corr)
       // with the row-occupancy bitmap a wide ring is cheap: let the ring search reach the correspondence distance (5 m)
       // instead of handing the far queries to the brute-force sweep over the whole 0.5 M-point target
       h->dev.max_ring = std::max(h->dev.max_ring, 32);
-      s = enqueue_find_closests_half(h, whole_batch(h, K, first), ns_max, 0);
+      s = enqueue_find_closests_half(h, whole_batch(h, K, first), ns_max);
       if (s) return s;
     }
     HIPCHK(h, hipMemsetAsync(h->dev.hist + (size_t)first * kHistBins, 0, sizeof(uint32_t) * kHistBins * (size_t)K, h->stream));
