@@ -328,6 +328,10 @@ smhip_status smhip_ndt_get_voxels(smhip_handle h, int capacity, int32_t* keys, i
                                   float* icovs, float* centroids);
 /* copy slot's current target (as uploaded / prepared) back to the host: xyz and normals, 3 floats each */
 smhip_status smhip_get_target_f32(smhip_handle h, int slot, float* xyz, float* normals, int n);
+/* copy slot's resident source back to the host in the order the device holds it (Morton order after smhip_set_source_f32 /
+ * smhip_set_sources_f32_batch): 4 floats per row, x y z and in .w the bits of the row's index in the cloud the caller uploaded.
+ * That order is the point index of the CalculateNormals calls that build from a source slot. */
+smhip_status smhip_get_source_f32(smhip_handle h, int slot, float* xyzw, int n);
 smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6], int compute_hessian,
                                            double* score, double grad[6], double hess[36]);
 /* measurement hook: `launches` back-to-back computeDerivatives launches (with Hessian) over slots first_slot .. + npairs - 1 at the

@@ -38,6 +38,8 @@ def lib():
         _LIB.smref_nn.restype = ctypes.c_int
         _LIB.smref_calculate_normals.argtypes = [dp, ctypes.c_int, dp, dp, ip]
         _LIB.smref_calculate_normals.restype = ctypes.c_int
+        _LIB.smref_normals_partition.argtypes = [dp, ctypes.c_int, ip, ip, ip]
+        _LIB.smref_normals_partition.restype = ctypes.c_int
     return _LIB
 
 
@@ -138,6 +140,17 @@ def calculate_normals(points):
                                       on.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                       sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
     return op[:m].copy(), on[:m].copy(), sz[:m].copy()
+
+
+def normals_partition(points):
+    """The kd-box partition of CalculateNormals alone: (indices[n], leaf ranges [L, 2]); leaf l holds the points
+    indices[first:last], leaves in depth-first order (left child first)."""
+    pts, pp = _d(points)
+    n = pts.shape[0]
+    ip = ctypes.POINTER(ctypes.c_int)
+    idx = np.zeros(n, dtype=np.int32); lf = np.zeros(n, dtype=np.int32); ll = np.zeros(n, dtype=np.int32)
+    nl = lib().smref_normals_partition(pp, n, idx.ctypes.data_as(ip), lf.ctypes.data_as(ip), ll.ctypes.data_as(ip))
+    return idx, np.stack([lf[:nl], ll[:nl]], axis=1)
 
 
 # ------------------------------------------------------------------------------------------------------------

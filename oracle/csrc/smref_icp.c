@@ -541,7 +541,8 @@ int smref_nn(const double* tgt, int nt, const double* qry, int nq, int* ids, dou
 /* ------------------------------------------------------------------ */
 /* EigenPointCloud::CalculateNormals  (cloud_types.cc:73-144, 347-368) */
 /* ------------------------------------------------------------------ */
-typedef struct { const double* pts; int* indices; double* out_p; double* out_n; int* out_k; int* out_sz; int m; } NormCtx;
+typedef struct { const double* pts; int* indices; double* out_p; double* out_n; int* out_k; int* out_sz; int m;
+                 int* leaf_first; int* leaf_last; int nl; /* partition only (smref_normals_partition) */ } NormCtx;
 
 static int rank3_sym(const double C[9]) {
   double E[9], V[9], w[3];
@@ -556,6 +557,7 @@ static int rank3_sym(const double C[9]) {
 static void normals_leaf(NormCtx* c, int first, int last) {                            /* :73-103 */
   int n = last - first;
   if (n <= 0) return;
+  if (c->leaf_first) { c->leaf_first[c->nl] = first; c->leaf_last[c->nl] = last; c->nl++; return; }
   double M[9] = {0}, b[3] = {0};
   int kmin = c->indices[first];
   for (int i = first; i < last; ++i) {
@@ -605,6 +607,7 @@ int smref_calculate_normals(const double* pts, int n, double* out_pts, double* o
   if (n <= 0) return 0;
   NormCtx c;
   c.pts = pts; c.m = 0;
+  c.leaf_first = NULL; c.leaf_last = NULL; c.nl = 0;
   c.indices = (int*)malloc(sizeof(int) * (size_t)n);
   int cap = n;
   c.out_p = (double*)malloc(sizeof(double) * 3 * (size_t)cap);
@@ -629,4 +632,20 @@ int smref_calculate_normals(const double* pts, int n, double* out_pts, double* o
   int m = c.m;
   free(order); free(c.indices); free(c.out_p); free(c.out_n); free(c.out_k); free(c.out_sz);
   return m;
+}
+
+/* the kd-box partition alone (:105-144), for tests that compare leaf MEMBERSHIP: indices[n] = the permutation nth_element left,
+ * leaf l = indices[leaf_first[l] .. leaf_last[l]) in depth-first order, left child first; returns the number of leaves (<= n) */
+int smref_normals_partition(const double* pts, int n, int* indices, int* leaf_first, int* leaf_last) {
+  if (n <= 0) return 0;
+  NormCtx c;
+  memset(&c, 0, sizeof(c));
+  c.pts = pts; c.indices = indices; c.leaf_first = leaf_first; c.leaf_last = leaf_last;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int i = 0; i < n; ++i) {
+    indices[i] = i;
+    for (int d = 0; d < 3; ++d) { if (pts[3 * i + d] < lo[d]) lo[d] = pts[3 * i + d]; if (pts[3 * i + d] > hi[d]) hi[d] = pts[3 * i + d]; }
+  }
+  normals_rec(&c, 0, n, lo, hi);
+  return c.nl;
 }

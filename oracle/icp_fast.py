@@ -59,12 +59,9 @@ def _inverse3_cofactor(M: np.ndarray) -> np.ndarray:
     return inv / det
 
 
-def calculate_normals(points: np.ndarray):
-    """builder/data/cloud_types.cc:347-368 + BuildNormals :105-144 + leaf :73-103.
-
-    Returns (kept_points[M,3], kept_normals[M,3], leaf_sizes[M]) ordered by the
-    smallest original index of each surviving leaf.
-    """
+def normals_partition(points: np.ndarray):
+    """The kd-box partition of BuildNormals alone (cloud_types.cc:105-144): (indices[n], [(first, last), ...]); leaf l holds the
+    points indices[first:last], leaves in depth-first order (left child first)."""
     pts = np.asarray(points, dtype=np.float64)
     n = pts.shape[0]
     indices = np.arange(n)
@@ -87,6 +84,17 @@ def calculate_normals(points: np.ndarray):
         right_lo = lo.copy(); right_lo[cut_dim] = cut_val        # :135-136
         stack.append((first + left, last, right_lo, hi))
         stack.append((first, first + left, lo, left_hi))
+    return indices, leaves
+
+
+def calculate_normals(points: np.ndarray):
+    """builder/data/cloud_types.cc:347-368 + BuildNormals :105-144 + leaf :73-103.
+
+    Returns (kept_points[M,3], kept_normals[M,3], leaf_sizes[M]) ordered by the
+    smallest original index of each surviving leaf.
+    """
+    pts = np.asarray(points, dtype=np.float64)
+    indices, leaves = normals_partition(pts)
     keep_idx, keep_pts, keep_nrm, keep_sz = [], [], [], []
     for first, last in leaves:
         ids = indices[first:last]

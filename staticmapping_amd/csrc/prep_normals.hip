@@ -12,6 +12,10 @@
 // segment along its own axis; the split index count - count / 2 and the cut value are then read off.
 // Exact medians, so the partition equals nth_element's up to ties in the cut coordinate (which
 // std::nth_element leaves unspecified as well).
+//
+// The rule both builders follow, and the tests hold them to (tests/normals_ref.py): coordinates compare by ordered_bits / kd_key,
+// so -0.0 sorts before +0.0; of the points ON the median value those with the smallest index go left, the index being the
+// point's position in its scan as `raw` holds it; the cut value is the coordinate of the element at rank `left`.
 #include <cstring>
 #include <string.h>
 

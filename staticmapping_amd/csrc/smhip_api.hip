@@ -1072,6 +1072,18 @@ smhip_status smhip_get_target_f32(smhip_handle h, int slot, float* xyz, float* n
   return SMHIP_OK;
 }
 
+smhip_status smhip_get_source_f32(smhip_handle h, int slot, float* xyzw, int n) {
+  smhip_status s = check_slot(h, slot);
+  if (s) return s;
+  if (!xyzw || n != h->ns[slot] || n <= 0) { h->err = "n must equal the slot's source size"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->stage, h->dev.src + (size_t)slot * h->dev.ns_cap, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::memcpy(xyzw, h->stage, sizeof(float4) * (size_t)n);
+  return SMHIP_OK;
+}
+
 smhip_status smhip_copy_slot(smhip_handle h, int from, int to) {
   smhip_status s = check_slot(h, from);
   if (s) return s;

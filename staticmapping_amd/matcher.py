@@ -155,6 +155,15 @@ class IcpFastHip:
         self._check(self._lib.smhip_get_target_f32(self._h, slot, p.ctypes.data_as(_capi.c_float_p), nr.ctypes.data_as(_capi.c_float_p), n))
         return p, nr
 
+    def get_source(self, slot: int = 0):
+        """The slot's resident source in the order the device holds it (smhip_get_source_f32): float32 [n, 3] points and the
+        int32 [n] index of every row in the cloud the caller uploaded."""
+        ns = ctypes.c_int32()
+        self._check(self._lib.smhip_get_cloud_sizes(self._h, slot, ctypes.byref(ns), None, None))
+        rows = np.zeros((ns.value, 4), np.float32)
+        self._check(self._lib.smhip_get_source_f32(self._h, slot, rows.ctypes.data_as(_capi.c_float_p), ns.value))
+        return np.ascontiguousarray(rows[:, :3]), rows[:, 3].copy().view(np.int32)
+
     def set_target_cache(self, enable: bool = True):
         """Keep the target-side structures (ICP search grid, NDT voxel table) across single-pair calls while the target is
         unchanged (default on); off = rebuild on every Align like the reference.  Results are identical either way."""

@@ -6,6 +6,8 @@ import time
 import numpy as np
 import pytest
 
+import normals_ref as nr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,6 +41,8 @@ def test_device_calculate_normals_matches_oracle(n_points):
     # the unconstrained-LS normal is ill-conditioned on near-collinear leaves; the bulk must agree
     agree = np.abs(n_dev[good] - n_ref[good]).max(axis=1) < 1e-2
     assert agree.mean() > 0.97
+    # and leaf by leaf against the exact reference: membership, bit-equal means, normals within the measured spread
+    print(nr.compare(nr.LeafReference(a[:, :3]), p_dev, n_dev))
     print(f"device CalculateNormals {n_points} pts -> {M}: {dt*1e3:.1f} ms (first call, incl. workspace allocation)")
     m.close()
 
@@ -125,6 +129,8 @@ def test_large_batch_forest_equals_single_calls_and_the_oracle(cfg2, capsys):
     assert abs(len(pb) - ok.sum()) <= 2
     d, _ = _match_sets(pb.astype(np.float64), nb, q[ok], n[ok])
     assert (d < 1e-4).mean() > 0.995
+    p_res, _ = m.get_source(31)                                                # the scan in the order the forest indexed it
+    nr.compare(nr.LeafReference(p_res), pb, nb)
     with capsys.disabled():
         print(f"\n[forest] 32 scans ({sum(len(s) for s in scans)} points) prepared in {dt * 1e3:.2f} ms = {dt * 1e3 / 32:.3f} ms per scan")
     m.close()
