@@ -219,7 +219,12 @@ smhip_status smhip_icp_fetch_batch(smhip_handle h, int npairs, double* results, 
 
 /* Device-resident copy of the last results: writes npairs * 18 doubles to device memory at
  * dev_out (16 column-major transform + score + iterations) on the handle's stream, so a collective
- * (RCCL gather of the poses) can consume them without a host round trip. */
+ * (RCCL gather of the poses) can consume them without a host round trip.
+ * The row has no status column: a pair that smhip_icp_fetch_batch would answer with a status other than
+ * SMHIP_OK (no finite correspondence -- also when it was lost after the first iteration --, a non-finite target,
+ * a single launch that stopped itself) exports iterations = 0 whatever count it reached, with the transform and
+ * score it was left with (the guess and 0 for "no finite correspondence").  Every finished pair exports
+ * iterations >= 1, so `row[17] >= 1` is the test for "this pair has a result". */
 smhip_status smhip_icp_export_results_device(smhip_handle h, int npairs, void* dev_out);
 
 /* ---- target preparation (host) -------------------------------------------

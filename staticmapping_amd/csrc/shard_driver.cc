@@ -344,6 +344,13 @@ int RunRank(const Args& a, int rank, int world, int device) {
   int n_pairs = static_cast<int>(files.size()) - 1;
   if (a.max_pairs > 0) n_pairs = std::min(n_pairs, a.max_pairs);
   const int per = (n_pairs + world - 1) / world;                         // padded pairs per rank
+  // a scan without a point (an empty or cut-off file; the upload refuses n <= 0 without knowing the file) ends the run by name,
+  // before any device work
+  for (int k = 0; k <= n_pairs; ++k) {
+    struct stat sb;
+    if (stat(files[k].c_str(), &sb) == 0 && sb.st_size < 16)
+      Die(files[k] + " holds no point (" + std::to_string(static_cast<long long>(sb.st_size)) + " bytes; a row is 16)");
+  }
 
   HIPOK(hipSetDevice(device));
   ncclComm_t comm;
@@ -466,6 +473,14 @@ int RunRank(const Args& a, int rank, int world, int device) {
     const float* rows = scans.Next(n, &fi);
     if (!rows || fi != expect) Die("prefetcher out of step with the batch loop");
     if (*n < 0) Die("cannot read " + files[fi]);
+    if (*n == 0) Die(files[fi] + " holds no point");
+    // A scan without one finite point has no target and no correspondence: CalculateNormals would drop every leaf ("produced no
+    // target points") after building a tree over one run of equal keys.  Ended here by name instead; an ordinary scan leaves the
+    // loop at its first row.
+    bool finite = false;
+    for (int i = 0; i < *n && !finite; ++i)
+      finite = std::isfinite(rows[4 * static_cast<size_t>(i)]) && std::isfinite(rows[4 * static_cast<size_t>(i) + 1]) && std::isfinite(rows[4 * static_cast<size_t>(i) + 2]);
+    if (!finite) Die(files[fi] + " holds no finite point");
     return rows;
   };
   double upload_s = 0.0, wait_s = 0.0, set_s = 0.0, prep_s = 0.0;   // rank 0's host-side split: blocked on the readers / uploads / target preparation
@@ -558,7 +573,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
       const double* row = &all[static_cast<size_t>(kPoseDoubles) * (static_cast<size_t>(pair % world) * per + pair / world)];
       double T[16];
       for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = row[4 * c + r];   // column-major -> row-major
-      if (!(row[17] >= 1.0)) ++bad;                                      // a pair that never ran left zeros
+      if (!(row[17] >= 1.0)) ++bad;                                      // a pair that never ran left zeros; one that failed exports 0 iterations (smhip.h)
       Mul4(pose, T, pose);
       write_pose();
       score_sum += row[16]; iter_sum += row[17];

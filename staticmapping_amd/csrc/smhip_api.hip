@@ -1430,7 +1430,11 @@ __global__ void export_results(IcpDev b, int npairs, double* out) {
   const PairState* st = &b.state[p];
   for (int k = 0; k < 16; ++k) out[18 * p + k] = st->result[k];
   out[18 * p + 16] = st->score;
-  out[18 * p + 17] = (double)st->iter;
+  // The row has no status column, and its reader (the sequence driver) takes iterations >= 1 for "this pair finished".  A pair that
+  // failed after its first iteration keeps the count it reached (finalize's no-correspondence branch and icp_one's bail leave
+  // `iter` alone), so a pair that smhip_icp_fetch_batch would answer with a status other than OK exports 0 iterations.
+  const bool ok = st->done && st->status == 0 && !st->score_mismatch;
+  out[18 * p + 17] = ok ? (double)st->iter : 0.0;
 }
 
 smhip_status smhip_icp_export_results_device(smhip_handle h, int npairs, void* dev_out) {
