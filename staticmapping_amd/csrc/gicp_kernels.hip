@@ -7,8 +7,13 @@
 //   gicp_corr      correspondence filter + Mahalanobis     :441-463
 //   gicp_fdf       OptimizationFunctorWithIndices f/df/fdf :250-377 (the sums; the 6-vector tail is host code)
 // The BFGS minimiser (pcl/registration/bfgs.h) and the outer loop run on the host in smhip_gicp_api.hip.
+//
+// A fragment of the NDT / NdtWithGicp unit (smhip_ndt_gicp.hip): ndt_kernels.hip must precede it, for jacobi_eig3
+// (gicp_knn_cov_one regularises a covariance through the eigen-decomposition the voxel statistics use).
 #pragma once
 #include "smhip_device.h"
+#include "kd_median_tree.h"
+#include "grid_lookup.h"
 
 namespace smhip {
 

@@ -39,6 +39,9 @@
 // of lower-bounded queries over all workgroups, which then write other workgroups' matches).
 // Barrier: one returning arrival per workgroup on a monotonic counter; the last arrival publishes the epoch in a second word, the
 // others spin on that word (not on the counter the arrivals queue on).
+//
+// A fragment of the ICP unit (smhip_api.hip), not a translation unit: it is made of icp_kernels.hip's bodies (the list above,
+// ListedCtx, TailOpts, ...), so icp_kernels.hip must precede it.
 #include <cstddef>
 #include "smhip_device.h"
 

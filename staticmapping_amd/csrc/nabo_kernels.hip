@@ -22,28 +22,16 @@
 // visiting order (deepest pending sibling first) with an explicit stack of root paths.
 // Arithmetic: float32 on the centred target / transformed query, like every other search here (libnabo: float64): a
 // pruning test within one float ulp of its threshold can fall the other way -- tests/test_nabo_gpu.py counts how often.
+//
+// A fragment of the ICP unit (smhip_api.hip), not a translation unit: its searches are icp_kernels.hip's certificate, list and
+// match bookkeeping around a different walk (Pot, ld_src, centre_point, xcd_block, ...), so icp_kernels.hip must precede it.
 #pragma once
 #include "smhip_device.h"
 #include "kd_median_tree.h"
+#include "nabo_tree.h"
 
 namespace smhip {
 
-constexpr int kKdBucket = 8;              // libnabo's default bucketSize
-constexpr int kKdStack = 18;              // pending siblings per query: at most one per tree level (18 levels: > 1 M target points; node < 2^23)
-constexpr int kNaboListedBlocks = 96;     // workgroups per pair striding over the lists of queries to walk again (32: -2 %, 64: -1 %, 128: equal)
-constexpr int kKdTopNodes = 511;          // tree levels 0..8 staged in LDS by the search kernel (4 KiB)
-
-struct KdDev {
-  uint2* nodes;        // [slots][kd_node_cap]  inner: {cut value bits, (left child << 2) | dim}; leaf: {first, (count << 2) | 3}
-  KdSeg* segs;         // [slots][2][kd_seg_cap]
-  float4* alt;         // [slots][nt_cap]       second working order (ping-pong with tq)
-  uint32_t* cnt;       // [slots][2 * seg_cap]  left / right fill counters of a level with more segments than LDS holds
-  float* leaf;         // [slots][leaf_cap][24]  the buckets again, as the search scans them: x[8] y[8] z[8] of the bucket that starts at
-                       //                        tq position `first` in block first >> 2 (a bucket of a split cloud holds >= 4 points, so
-                       //                        blocks are unique), unused entries = +inf (their distance is +inf: never a candidate)
-  int32_t node_cap, seg_cap, leaf_cap;
-  float max_error2;    // (1 + epsilon)^2
-};
 // rd of a sibling: the squared distance to its half-space box, updated exactly as recurseKnn does (no contraction, so
 // that the pre-filter at push time and the test at pop time see the same number)
 __device__ __forceinline__ float kd_rd_step(float rd, float old_off, float new_off) {

@@ -6,6 +6,11 @@
 // `slots` independent scan pairs.  The IcpFast loop (icp_fast.cc:455-529) stays resident on
 // the device; the host only enqueues launches and, when early exit is on, polls one word
 // every `check_every` iterations.
+//
+// This file is the ICP translation unit of libsmhip.so: it defines the kernels of icp_kernels.hip and of the two fragments
+// that reuse their bodies (icp_one.hip, nabo_kernels.hip), in that order, and the entry points of IcpFast and of the clouds
+// every matcher shares.  The other host units (smhip_ndt_gicp.hip, smhip_filter_api.hip) reach the handle and the functions of
+// namespace smhip_host below through smhip_context.h.
 #include "icp_kernels.hip"
 #include "icp_one.hip"
 #include "nabo_kernels.hip"
@@ -21,121 +26,17 @@
 #include <string>
 #include <vector>
 
-#include "../../include/smhip.h"
-#include "prep_normals.h"
-#include "cloud_filters.h"
-#include "icp_plan.h"
+#include "smhip_context.h"
 
-using namespace smhip;
+using namespace smhip_host;
 using plan::ceil_div;
 
 static_assert(plan::kRingCoopLanes == kCoopLanes && plan::kNaboBucket == kKdBucket && plan::kNaboShallowLevels <= kKdStack,
               "icp_plan.h restates kernel constants");
 
-struct smhip_ndt_state;
-struct smhip_gicp_state;
-
-struct smhip_context {
-  smhip_ndt_state* ndt = nullptr;
-  smhip_gicp_state* gicp = nullptr;
-  PrepWorkspace* prep = nullptr;          // device CalculateNormals workspace (allocated on first use)
-  PrepWorkspace* prep_batch = nullptr;    // the same sized for every slot at once (batched target preparation)
-  FilterWorkspace* filt = nullptr;        // device pre-filters (allocated on first use)
-  float4* prep_raw = nullptr;             // raw scan staging on the device
-  float4* raw_batch = nullptr;            // the same for a whole batch of scans (smhip_set_sources_f32_batch; allocated on first use)
-  hipStream_t copy_stream = nullptr;      // host-to-device copies of a batch of page-locked scans (overlap the handle's stream)
-  hipEvent_t ev_copied = nullptr, ev_raw_free = nullptr;
-  bool raw_in_use = false;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipStream_t side[plan::kMaxParts - 1] = {};      // the streams of a batch's parts beyond the first (icp_plan.h)
-  hipEvent_t ev_fork = nullptr, ev_join[plan::kMaxParts - 1] = {};
-  int n_side = 0;
-  IcpDev dev{};
-  KdDev kd{};                    // SMHIP_NN_NABO: tree arrays, allocated on first use
-  bool kd_allocated = false;
-  smhip_icp_options opts{};
-  std::vector<int> ns, nt, has_normals;
-  // Target-side structures are kept across calls while a slot's target is unchanged (single-pair calls only: the front end
-  // aligns scan after scan against one key frame, map_builder.cc:379-392).  tgt_gen[slot] changes whenever the slot's target
-  // does; grid_gen / grid_cell / grid_sorted describe the search structure currently resident in the slot.
-  std::vector<unsigned long long> tgt_gen, grid_gen;
-  std::vector<unsigned long long> src_gen, src3_gen;   // same idea for the packed 12-byte copy of a slot's source (pack_source)
-  std::vector<float> grid_cell_built;
-  std::vector<int> grid_sorted, grid_rows, grid_mode;   // grid_rows: row-occupancy bitmap built too; grid_mode: nn_mode of the structure
-  unsigned long long gen_counter = 0;
-  int nabo_listed_blocks = kNaboListedBlocks;   // workgroups per pair of the list walk (SMHIP_NABO_LISTED_BLOCKS overrides, tuning only)
-  int target_cache = 1;             // smhip_set_target_cache
-  unsigned long long cache_hits = 0;
-  PairInput* in_pinned = nullptr;
-  PairState* state_pinned = nullptr;
-  int hist_mode = 0;             // nn_mode of the batch whose searched-query history is waiting in hist_pinned
-  int nabo_fused_from = 6;       // reference-search mode: the first iteration of a batch that runs the fused certificate pass (plan::fused_now)
-  float split_share = 0.2f;      // auto split: the first iteration whose median searched share falls below this runs certify + listed search
-  int sums_blocks = kSumsBlocks;  // workgroups of iteration_sums (SMHIP_SUMS_BLOCKS)
-  int sums_long_for = 3;         // fused iterations of a batch whose missed pairs iteration_sums cuts into long blocks (SMHIP_SUMS_LONG_FOR)
-  int use_shadow = 1;            // fused certificate pass reads the 4-byte shadow of (bound, match) where every target is small enough (SMHIP_SHADOW)
-  int one_blocks = 0;            // workgroups of the single-pair persistent kernel the device holds at once (0: not available)
-  int one_used = 0;              // the last single-pair enqueue went through it
-  int one_blocks_allowed = 1;    // 0: fine-grained memory could not be had at smhip_create
-  long long one_launches = 0;    // enqueues that went through it (smhip_icp_single_launch_counts)
-  int one_fallbacks = 0;         // Aligns done again as separate launches because the launch stopped itself (see fetch_range)
-  int one_enabled = 1;           // SMHIP_ONE_PAIR=0: single pairs through the separate launches (measurement aid)
-  int one_groups_want = 0;       // SMHIP_ONE_GROUPS: groups of its barrier (tuning)
-  int one_blocks_want = 0;       // SMHIP_ONE_BLOCKS: its grid (tuning; 0 = as many as a round each needs, at most what is resident)
-  int one_pairs_max = kOnePairs; // SMHIP_ONE_PAIRS: pairs one launch of it may hold (1 = single pairs only)
-  int one_idle = 0;              // SMHIP_ONE_IDLE: with SMHIP_ONE_BLOCKS, keep a grid of mostly idle workgroups on small clouds (tests)
-  int one_no_retry = 0;          // SMHIP_ONE_NO_RETRY: a launch that stopped itself is reported, not done again (fetch_range)
-  int wave_search = 0;           // batches: the every-query-searches iterations through nn_ball_lds (0, default: 5-25 % faster on the bench scans)
-                                 // or nn_ball_wave (1; SMHIP_WAVE_SEARCH=1) -- same results
-  float4* stage = nullptr;       // pinned staging for uploads, 2 * max(ns_cap, nt_cap)
-  uint32_t* done_pinned = nullptr;
-  // split_after = 0: where the batched iterations switch from the fused search to certify + listed search follows the
-  // previous batch (the share of queries that needed a search per iteration, search_hist): a front end's guesses are
-  // alike from call to call.  Results do not depend on it, only the time.
-  uint32_t* hist_pinned = nullptr;
-  int hist_first = 0;
-  int hist_pairs = 0;                  // pairs whose rows the last enqueue copied to hist_pinned (0 = none)
-  std::vector<int> hist_ns;            // their sources' sizes at that enqueue (the slots may hold other clouds by the time the rows are read)
-  int hist_iters = 0;                  // iterations that enqueue ran
-  int auto_split = 2;
-  int32_t* ids_pinned = nullptr;
-  float* d2_pinned = nullptr;
-  int32_t* ids_dev = nullptr;    // scratch for exported matches
-  float* d2_dev = nullptr;
-  std::vector<void*> allocs;
-  std::string err;
-  int last_npairs = 0;
-  // profiling
-  int profile = 0;               // 0 off, 1 every launch, 2 the dominant NN kernel only
-  struct Ev { hipEvent_t a, b; int cat; int np; };
-  std::vector<Ev> ev_pool;
-  size_t ev_used = 0;
-  smhip_icp_profile prof{};
-};
-
 namespace {
 
 thread_local std::string g_create_error;
-
-#define HIPCHK(h, expr)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                       \
-      return SMHIP_ERR_HIP;                                                               \
-    }                                                                                     \
-  } while (0)
-
-template <typename T>
-smhip_status dev_alloc(smhip_context* h, T** p, size_t count) {
-  void* v = nullptr;
-  HIPCHK(h, hipMalloc(&v, count * sizeof(T)));
-  h->allocs.push_back(v);
-  *p = reinterpret_cast<T*>(v);
-  return SMHIP_OK;
-}
 
 // profiling brackets around launches of one category (plan::Category)
 struct Bracket {
@@ -186,11 +87,10 @@ void collect_profile(smhip_context* h) {
   h->ev_used = 0;
 }
 
-inline void touch_target(smhip_context* h, int slot) { h->tgt_gen[slot] = ++h->gen_counter; }
-inline void touch_source(smhip_context* h, int slot) { h->src_gen[slot] = ++h->gen_counter; }
-inline void touch_grid(smhip_context* h, int first, int np) {        // the slots' search structures are (re)built / overwritten
-  for (int p = first; p < first + np; ++p) { h->grid_gen[p] = 0; h->grid_cell_built[p] = 0.f; h->grid_sorted[p] = 0; h->grid_rows[p] = 0; h->grid_mode[p] = -1; }
-}
+}  // namespace
+
+// What the other host units call is declared in smhip_context.h; the helpers marked static are this file's own.
+namespace smhip_host {
 
 smhip_status check_slot(smhip_context* h, int slot) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
@@ -198,19 +98,9 @@ smhip_status check_slot(smhip_context* h, int slot) {
   return SMHIP_OK;
 }
 
-// One half of a batch: a by-value copy of the device view restricted to pairs [pair_base, pair_base + np)
-// and the stream its launches go to.
-struct Half {
-  IcpDev d;
-  hipStream_t stream;
-  int np;
-  plan::Part part;         // how its launches size themselves (enqueue_range)
-  int first_fused = -1;    // the first iteration of this Align that ran the fused path
-};
-
 // the ICP iteration kernels stream the 12-byte copy of the sources: repacked here (main stream, the PairInput rows already
 // on their way) for launches that cover a slot whose source changed since it was last packed
-smhip_status ensure_packed(smhip_context* h, int first, int np) {
+static smhip_status ensure_packed(smhip_context* h, int first, int np) {
   bool stale = false;
   for (int p = first; p < first + np; ++p) stale = stale || h->src3_gen[p] != h->src_gen[p];
   if (!stale) return SMHIP_OK;
@@ -221,7 +111,7 @@ smhip_status ensure_packed(smhip_context* h, int first, int np) {
 }
 
 // per-call resets for pairs [0, np) (main stream, before the halves fork)
-smhip_status enqueue_resets(smhip_context* h, int np, int first = 0) {
+smhip_status enqueue_resets(smhip_context* h, int np, int first) {
   IcpDev& d = h->dev;
   touch_grid(h, first, np);               // bits / ccount are zeroed below: whatever structure was resident is gone
   HIPCHK(h, hipMemcpyAsync(const_cast<PairInput*>(d.in) + first, h->in_pinned + first, sizeof(PairInput) * np, hipMemcpyHostToDevice, h->stream));
@@ -230,7 +120,7 @@ smhip_status enqueue_resets(smhip_context* h, int np, int first = 0) {
 }
 
 // target centring + search-structure build for one half
-smhip_status kd_ensure(smhip_context* h) {
+static smhip_status kd_ensure(smhip_context* h) {
   if (h->kd_allocated) return SMHIP_OK;
   const size_t B = h->dev.slots, NT = h->dev.nt_cap;
   h->kd.node_cap = (int32_t)(NT / 2 + 8);       // a split node has >= 9 points and gives each child >= 4: <= nt / 4 leaves, 2 leaves - 1 nodes
@@ -289,8 +179,6 @@ smhip_status enqueue_grid_build(smhip_context* h, const Half& f, int nt_max) {
   return SMHIP_OK;
 }
 
-Half whole_batch(smhip_context* h, int np, int first);
-
 // is the search structure resident in `slot` the one a build with the current settings would produce?
 bool grid_cached(smhip_context* h, int slot) {
   const int want_mode = h->opts.nn_mode == SMHIP_NN_NABO ? SMHIP_NN_NABO : SMHIP_NN_GRID;   // which structure: kd-tree or grid
@@ -314,7 +202,7 @@ smhip_status enqueue_prepare_kept(smhip_context* h, int first, int K) {
 }
 
 // single-pair form of enqueue_resets + enqueue_grid_build that skips the build when the slot's target is unchanged
-smhip_status enqueue_prepare_one(smhip_context* h, int slot, int nt_max) {
+static smhip_status enqueue_prepare_one(smhip_context* h, int slot, int nt_max) {
   if (grid_cached(h, slot)) return enqueue_prepare_kept(h, slot, 1);
   smhip_status s = enqueue_resets(h, 1, slot);
   if (s) return s;
@@ -330,21 +218,21 @@ Half whole_batch(smhip_context* h, int np, int first) {
 }
 
 // single-stream convenience used by find_closests / the NDT fitness pass
-smhip_status enqueue_prepare(smhip_context* h, int np, int nt_max) {
+static smhip_status enqueue_prepare(smhip_context* h, int np, int nt_max) {
   if (np == 1) return enqueue_prepare_one(h, 0, nt_max);
   smhip_status s = enqueue_resets(h, np);
   if (s) return s;
   return enqueue_grid_build(h, whole_batch(h, np, 0), nt_max);
 }
 
-inline int nt_max_of(const smhip_context* h, int first, int np) {
+static inline int nt_max_of(const smhip_context* h, int first, int np) {
   int m = 0;
   for (int p = first; p < first + np; ++p) m = std::max(m, h->nt[p]);
   return m;
 }
 
 // the settings the plan reads, as they stand now (callers that patch h->dev or h->opts around a search patch the plan's inputs)
-plan::Inputs plan_inputs(const smhip_context* h) {
+static plan::Inputs plan_inputs(const smhip_context* h) {
   plan::Inputs in;
   in.nn_mode = h->opts.nn_mode;
   in.use_ball = h->dev.use_ball; in.lds_table = h->dev.lds_table; in.certify = h->dev.certify; in.exact_all = h->dev.exact_all;
@@ -362,7 +250,7 @@ plan::Inputs plan_inputs(const smhip_context* h) {
 }
 
 // launches what a plan names, in its order, on the part's stream
-smhip_status enqueue_launches(smhip_context* h, const Half& f, const plan::Iteration& it) {
+static smhip_status enqueue_launches(smhip_context* h, const Half& f, const plan::Iteration& it) {
   using K = plan::Kernel;
   const IcpDev& d = f.d;
   hipStream_t st = f.stream;
@@ -424,11 +312,11 @@ smhip_status enqueue_find_closests_half(smhip_context* h, const Half& f, int ns_
   return enqueue_launches(h, f, plan::plan_search_only(plan_inputs(h), plan::whole_part(f.np, nt_max_of(h, f.d.pair_base, f.np)), ns_max));
 }
 
-smhip_status enqueue_find_closests(smhip_context* h, int np, int ns_max) {
+static smhip_status enqueue_find_closests(smhip_context* h, int np, int ns_max) {
   return enqueue_find_closests_half(h, whole_batch(h, np, 0), ns_max);
 }
 
-smhip_status fill_inputs(smhip_context* h, int np, const double* guesses, int* ns_max, int* nt_max, int first = 0) {
+smhip_status fill_inputs(smhip_context* h, int np, const double* guesses, int* ns_max, int* nt_max, int first) {
   *ns_max = 0; *nt_max = 0;
   for (int p = first; p < first + np; ++p) {
     if (h->ns[p] <= 0 || h->nt[p] <= 0) { h->err = "Align before SetInputSource/SetInputTarget"; return SMHIP_ERR_NOT_READY; }
@@ -443,7 +331,16 @@ smhip_status fill_inputs(smhip_context* h, int np, const double* guesses, int* n
   return SMHIP_OK;
 }
 
-void sync_options(smhip_context* h) {
+// the single-cloud CalculateNormals / Morton-order workspace and the raw staging array: allocated on first use
+smhip_status prep_ensure(smhip_context* h) {
+  if (h->prep) return SMHIP_OK;
+  const int cap = std::max(h->dev.ns_cap, h->dev.nt_cap);
+  h->prep = prep_create(cap);
+  if (!h->prep) { h->err = "device CalculateNormals workspace allocation failed"; return SMHIP_ERR_HIP; }
+  return dev_alloc(h, &h->prep_raw, (size_t)cap);
+}
+
+static void sync_options(smhip_context* h) {
   h->dev.max_iteration = std::max(1, h->opts.max_iteration);
   h->dev.early_exit = h->opts.early_exit;
   h->dev.max_ring = std::max(1, h->opts.grid_max_ring);
@@ -493,6 +390,10 @@ void sync_options(smhip_context* h) {
   { const char* e = std::getenv("SMHIP_BAND_GAIN"); if (e && std::atof(e) >= 0.0) h->dev.band_gain = (float)std::atof(e); }
   { const char* e = std::getenv("SMHIP_NABO_LISTED_BLOCKS"); if (e && std::atoi(e) > 0) h->nabo_listed_blocks = std::max(8, std::min(4096, std::atoi(e))); }   // >= 8: a workgroup's 16-bit histogram bins
 }
+
+}  // namespace smhip_host
+
+namespace {
 
 // FindClosests output in the caller's order: source i was uploaded from caller index src.w,
 // target position j holds caller index tq.w.
@@ -747,7 +648,6 @@ smhip_status smhip_synchronize(smhip_handle h) {
 }
 
 // ---- uploads ---------------------------------------------------------------------------
-static smhip_status prep_ensure(smhip_handle h);
 
 // staged source -> device, Morton-ordered there (spatially coherent wavefronts; w = caller index)
 static smhip_status upload_source(smhip_handle h, int slot, int n) {
@@ -929,14 +829,6 @@ smhip_status smhip_set_target_f32(smhip_handle h, int slot, const float* xyz, in
   h->has_normals[slot] = nrm != nullptr;
   touch_target(h, slot);
   return SMHIP_OK;
-}
-
-static smhip_status prep_ensure(smhip_handle h) {
-  if (h->prep) return SMHIP_OK;
-  const int cap = std::max(h->dev.ns_cap, h->dev.nt_cap);
-  h->prep = prep_create(cap);
-  if (!h->prep) { h->err = "device CalculateNormals workspace allocation failed"; return SMHIP_ERR_HIP; }
-  return dev_alloc(h, &h->prep_raw, (size_t)cap);
 }
 
 static smhip_status prep_run(smhip_handle h, const float4* raw_dev, int n, int slot, int* n_out) {
@@ -1507,45 +1399,3 @@ smhip_status smhip_icp_get_profile(smhip_handle h, smhip_icp_profile* out) {
 }
 
 }  // extern "C"
-
-// ---- registrators::Ndt --------------------------------------------------------------------------
-#include "smhip_ndt_api.hip"
-
-namespace {
-NdtHost& ndt_of(smhip_context* h) {
-  if (!h->ndt) { h->ndt = new smhip_ndt_state(); smhip_ndt_default_options(&h->ndt->n.opts); }
-  return h->ndt->n;
-}
-}  // namespace
-
-extern "C" void smhip_internal_free_ndt(smhip_context* h) {
-  if (!h || !h->ndt) return;
-  ndt_release(h->ndt->n);
-  delete h->ndt;
-  h->ndt = nullptr;
-}
-
-// ---- pre_processers::filter -----------------------------------------------------------------------
-#include "smhip_filter_api.hip"
-
-// ---- registrators::NdtWithGicp ------------------------------------------------------------------
-#include "smhip_gicp_api.hip"
-
-struct smhip_gicp_state { GicpHost g; };
-
-namespace {
-GicpHost& gicp_of(smhip_context* h) {
-  if (!h->gicp) { h->gicp = new smhip_gicp_state(); smhip_ndt_gicp_default_options(&h->gicp->g.opts); }
-  return h->gicp->g;
-}
-}  // namespace
-
-extern "C" void smhip_internal_free_gicp(smhip_context* h) {
-  if (!h || !h->gicp) return;
-  GicpHost& g = h->gicp->g;
-  if (g.out_pinned) (void)hipHostFree(g.out_pinned);
-  if (g.count_pinned) (void)hipHostFree(g.count_pinned);
-  if (g.prep_avg) prep_destroy(g.prep_avg);
-  delete h->gicp;
-  h->gicp = nullptr;
-}

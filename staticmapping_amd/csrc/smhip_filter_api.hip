@@ -1,8 +1,17 @@
-// smhip_filter_api.hip -- C ABI of the device pre-filters (included by smhip_api.hip); kernels in cloud_filters.hip.
+// smhip_filter_api.hip -- C ABI of the device pre-filters: a translation unit of its own that launches no kernel (the kernels
+// are in cloud_filters.hip, behind cloud_filters.h); the handle and check_slot / prep_ensure come from smhip_context.h.
 // Mirrors pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, GroundRemoval, GroundRemoval2,
 // RangeImage, Factory} (the reference's pre_processors/filter_*.cc): constructor defaults, ConfigsValid() and Filter().
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "smhip_context.h"
+
+using namespace smhip_host;
 
 extern "C" {
 

@@ -1,4 +1,6 @@
-// smhip_gicp_api.hip -- host side of registrators::NdtWithGicp on the C ABI (included by smhip_api.hip).
+// smhip_gicp_api.hip -- host side of registrators::NdtWithGicp on the C ABI.  A fragment of the NDT / NdtWithGicp unit
+// (smhip_ndt_gicp.hip): it drives the NDT engine of smhip_ndt_api.hip directly (ndt_ensure, ndt_align_slots, fitness_scores),
+// so that file and gicp_kernels.hip must precede it.
 //
 // NdtWithGicp::Align (/root/reference/registrators/ndt_gicp.cc:55-112) = pcl::ApproximateVoxelGrid on both clouds
 // -> stock pcl NDT -> (fitness <= 1) stock pcl GICP -> score exp(-fitness).  All three live in PCL (1.8.1 pinned,
@@ -16,7 +18,6 @@
 #include <cstdlib>
 #include <cstdio>
 #include <ucontext.h>
-#include "gicp_kernels.hip"
 
 namespace {
 
@@ -53,7 +54,16 @@ struct GicpHost {
   unsigned long long seq = 0;         // evaluation rounds launched so far: the number gicp_fdf stores after the last job's sums
 };
 
-GicpHost& gicp_of(smhip_context* h);
+}  // namespace
+
+struct smhip_gicp_state { GicpHost g; };
+
+namespace {
+
+GicpHost& gicp_of(smhip_context* h) {
+  if (!h->gicp) { h->gicp = new smhip_gicp_state(); smhip_ndt_gicp_default_options(&h->gicp->g.opts); }
+  return h->gicp->g;
+}
 inline int gicp_scratch_slot(const smhip_context* h, int job) { return h->dev.slots / 2 + job; }
 
 smhip_status gicp_ensure(smhip_context* h) {
@@ -1092,3 +1102,14 @@ smhip_status smhip_gicp_get_covariances(smhip_handle h, int which, double* cov, 
 }
 
 }  // extern "C"
+
+// smhip_destroy's hook (smhip_api.hip)
+extern "C" void smhip_internal_free_gicp(smhip_context* h) {
+  if (!h || !h->gicp) return;
+  GicpHost& g = h->gicp->g;
+  if (g.out_pinned) (void)hipHostFree(g.out_pinned);
+  if (g.count_pinned) (void)hipHostFree(g.count_pinned);
+  if (g.prep_avg) prep_destroy(g.prep_avg);
+  delete h->gicp;
+  h->gicp = nullptr;
+}

@@ -1,4 +1,5 @@
-// smhip_ndt_api.hip -- host side of registrators::Ndt on the C ABI (included by smhip_api.hip).
+// smhip_ndt_api.hip -- host side of registrators::Ndt on the C ABI.  A fragment of the NDT / NdtWithGicp unit
+// (smhip_ndt_gicp.hip): smhip_context.h and ndt_kernels.hip must precede it.
 //
 // Ndt::Align (/root/reference/registrators/ndt.cc:38-64) = convert clouds, setInputTarget (voxel grid
 // build, every call), pclomp NDT align, getFitnessScore.  The whole Align is ONE submission: table build, the rounds of the
@@ -8,7 +9,6 @@
 // pass; the jobs' flags in page-locked memory say whether that was enough -- if not, more rounds and the fitness pass again.
 // K Aligns (smhip_ndt_align_batch; smhip_ndt_align is the batch of one) share every launch (grid.y = job): each job's
 // evaluation sequence is exactly the one the reference walks, and a batch returns the single calls' bits.
-#include "ndt_kernels.hip"
 
 namespace {
 
@@ -88,7 +88,10 @@ struct smhip_ndt_state { NdtHost n; };
 
 namespace {
 
-NdtHost& ndt_of(smhip_context* h);
+NdtHost& ndt_of(smhip_context* h) {
+  if (!h->ndt) { h->ndt = new smhip_ndt_state(); smhip_ndt_default_options(&h->ndt->n.opts); }
+  return h->ndt->n;
+}
 
 void ndt_release(NdtHost& n) {
   for (void* p : n.dev_allocs) (void)hipFree(p);
@@ -600,3 +603,11 @@ smhip_status smhip_ndt_debug_rows(smhip_handle h, unsigned long long* out, int m
 }
 
 }  // extern "C"
+
+// smhip_destroy's hook (smhip_api.hip): the handle's NDT state is this unit's alone
+extern "C" void smhip_internal_free_ndt(smhip_context* h) {
+  if (!h || !h->ndt) return;
+  ndt_release(h->ndt->n);
+  delete h->ndt;
+  h->ndt = nullptr;
+}

@@ -29,7 +29,7 @@ if calib_path and os.path.exists(calib_path):
                f"writing one float per element (the shape of nn_certify / accumulate): FETCH_SIZE x {ff:.4f}, WRITE_SIZE x {wf:.4f}")
 # the record is dated with the kernel sources it was measured on: bench.py uses it only while they are unchanged
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["staticmapping_amd/csrc/icp_kernels.hip", "staticmapping_amd/csrc/smhip_device.h"]
+SOURCES = ["staticmapping_amd/csrc/icp_kernels.hip", "staticmapping_amd/csrc/grid_lookup.h", "staticmapping_amd/csrc/smhip_device.h"]
 _h = hashlib.sha256()
 for _f in sorted(SOURCES):
     with open(os.path.join(ROOT, _f), "rb") as _fh:
