@@ -473,6 +473,32 @@ int smhip_filter_config_valid_ex(const smhip_filter_desc_ex* f);
 smhip_status smhip_filter_chain_ex_f32(smhip_handle h, const float* points, int stride_floats, int n,
                                        const smhip_filter_desc_ex* chain, int n_filters, int* n_out);
 
+/* ---- Submap::InsertFrame for a full submap (builder/submap.cc:98-158) ---------------------------
+ * Frame k = n[k] rows of `stride_floats` floats at rows[k] (4: x y z intensity, factor = i / n[k] of its own frame as the
+ * collector sets it; 5: InnerPointType) and the column-major 4x4 local_poses + 16 k.  One kernel launch moves every frame into
+ * the first frame's coordinates with the reference's TransformPoint (cloud_types.cc:167-178: the pose cast to float, x' = ((m00 x
+ * + m01 y) + m02 z) + m03, every product and sum rounded to float), carries intensity and factor unchanged, concatenates the
+ * frames in order and writes each row's VoxelGrid key; with voxel_size > 0 the VoxelGrid of the filters above follows (double
+ * sums per voxel in frame order, then point order; output in the packed key's order), with voxel_size == 0
+ * (enable_voxel_filter = false) the result is the plain concatenation.  The result becomes the filter workspace's current
+ * cloud, on the device: smhip_filter_get_output and smhip_filter_output_to_source read it as they read a filter chain's
+ * (source_index = the row in the concatenated input, -1 after the voxel filter), smhip_filter_output_to_target makes it a target.
+ * Refused before anything is touched (the resident cloud stays as it was): n_frames < 1, a null table, a null frame of n[k] > 0, a
+ * negative n[k], a stride other than 4 or 5, a non-finite pose, a voxel_size that is negative, not finite or in (0, 1e-6]
+ * (VoxelGrid::ConfigsValid), every frame empty -- SMHIP_ERR_INVALID_ARGUMENT; more rows together than max(max_source_points,
+ * max_target_points) -- SMHIP_ERR_CAPACITY.  Single empty frames among others are allowed.
+ * Voxel indices beyond +-2^20 and non-finite rows are treated as smhip_filter_chain_f32's VoxelGrid treats them (the same key
+ * function): a transformed row with an index beyond +-2^20, which includes an infinite coordinate, makes the call return
+ * SMHIP_ERR_INVALID_ARGUMENT AFTER the rows were written, and the unfiltered concatenation is then the resident cloud, as the
+ * chain leaves its input there; a NaN coordinate is not detected and enters the average of whatever voxel the rounding of NaN
+ * selects.  With voxel_size == 0 no index is formed and every row is carried. */
+smhip_status smhip_submap_build_f32(smhip_handle h, int n_frames, const float* const* rows, int stride_floats, const int* n,
+                                    const double* local_poses, float voxel_size, int* n_out);
+/* device CalculateNormals of the filter workspace's current cloud (a filter chain's output or a built submap) -> target of
+ * `slot`, without a download (submap.cc:160-161); *n_out = the target's size.  SMHIP_ERR_NOT_READY when no cloud is there;
+ * otherwise as smhip_prepare_target_f32 on the same rows. */
+smhip_status smhip_filter_output_to_target(smhip_handle h, int slot, int* n_out);
+
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one
  * InsertPointCloud per frame, builder/map_builder.cc:832-900), on the device.  Results equal the reference's insert loop

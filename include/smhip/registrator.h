@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <iomanip>
 #include <iostream>
 #include <memory>
@@ -358,6 +359,30 @@ class IcpFastHip : public Interface {
   int CapacitySource() const { return arena_.cap_source; }
   int CapacityTarget() const { return arena_.cap_target; }
 
+  // A cloud that `build` leaves in the filter workspace of this matcher's handle (smhip_submap_build_f32 for a submap,
+  // include/smhip/submap.h; a filter chain) becomes the source / the CalculateNormals target without a download.  `rows` = the
+  // largest cloud `build` handles (its input): the handle is sized for it first, on the source and the target side alike, so that
+  // the other cloud of the pair arrives in a handle that already has room.  Returns the points the matcher then holds, 0 when the
+  // device refused.  No host copy exists, so a later re-size of the handle (a cloud more than 1.5 times larger arriving) cannot
+  // restore a resident cloud: the matcher is then without it and Align fails loudly -- hand over the larger cloud first.
+  int SetInputSourceResident(int rows, const std::function<bool(smhip_handle)>& build) {
+    source_ok_ = false; source_keep_ = nullptr;
+    if (!EnsureHandle(rows, rows, false, true) || !build(arena_.handle)) return 0;
+    if (!Ok(smhip_filter_output_to_source(arena_.handle, 0), "smhip_filter_output_to_source")) return 0;
+    int ns = 0;
+    if (!Ok(smhip_get_cloud_sizes(arena_.handle, 0, &ns, nullptr, nullptr), "smhip_get_cloud_sizes")) return 0;
+    source_ok_ = true;
+    return ns;
+  }
+  int SetInputTargetResident(int rows, const std::function<bool(smhip_handle)>& build) {
+    target_ok_ = false; target_keep_ = nullptr; target_kind_ = kNoTarget;
+    if (!EnsureHandle(rows, rows, true, false) || !build(arena_.handle)) return 0;
+    int n_out = 0;
+    if (!Ok(smhip_filter_output_to_target(arena_.handle, 0, &n_out), "smhip_filter_output_to_target")) return 0;
+    prepared_points_ = n_out; target_ok_ = true;
+    return n_out;
+  }
+
   // K independent (source, target) pairs in ONE launch sequence through K pair slots of a second handle that this
   // matcher keeps between calls -- the six concurrent SubmapPairMatch tasks of the back end (map_builder.cc:655,
   // 706-708) as one batch instead of six matchers with an arena each.  Targets must carry normals.
@@ -463,6 +488,8 @@ class IcpFastHip : public Interface {
     }
     if (!ApplyOptions(arena_.handle)) return false;
     if (recreated) {
+      if (!source_keep_) source_ok_ = false;          // a resident cloud without a host copy went with the old handle
+      if (!target_keep_) target_ok_ = false;
       if (restore_source && source_keep_ && !UploadSource(*source_keep_)) { source_ok_ = false; return false; }
       if (restore_target && target_keep_ && target_kind_ != kNoTarget && !UploadTarget(*target_keep_, target_kind_)) { target_ok_ = false; return false; }
     }

@@ -11,3 +11,4 @@ from . import synth  # noqa: F401
 from .matcher import (IcpFastHip, IcpPointMatcherHip, NdtGicpHip, NdtHip, SmhipError, se3_error, calculate_normals,  # noqa: F401
                       NN_BRUTE, NN_GRID, NN_NABO)
 from .mrvm import MultiResolutionVoxelMapHip  # noqa: F401
+from .submap import SubmapBuilder, build_submap, output_to_target  # noqa: F401

@@ -162,6 +162,9 @@ SIGNATURES = {
     "smhip_filter_config_valid_ex": (ctypes.c_int, [ctypes.POINTER(FilterDescEx)]),
     "smhip_filter_chain_ex_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FilterDescEx),
                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_submap_build_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(c_float_p), ctypes.c_int, c_int32_p, c_double_p,
+                                              ctypes.c_float, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_filter_output_to_target": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -31,6 +31,7 @@
 
 #include "../../include/smhip.h"
 #include "cloud_filters.h"
+#include "voxel_key.h"
 
 namespace smhip {
 
@@ -98,14 +99,6 @@ __global__ void filt_scatter(const float4* pts, const float* fac, const int32_t*
 }
 
 // ---- VoxelGrid ---------------------------------------------------------------------------------
-constexpr long kVoxBias = 1l << 20;            // 21 bits per axis
-__device__ __forceinline__ bool voxel_key(const float4 p, float size, unsigned long long& key) {
-  const long ix = lroundf(p.x / size), iy = lroundf(p.y / size), iz = lroundf(p.z / size);   // filter_voxel_grid.cc:51-53
-  const long a = ix + kVoxBias, b = iy + kVoxBias, c = iz + kVoxBias;
-  const bool ok = a >= 0 && a < 2 * kVoxBias && b >= 0 && b < 2 * kVoxBias && c >= 0 && c < 2 * kVoxBias;
-  key = ok ? (((unsigned long long)a << 42) | ((unsigned long long)b << 21) | (unsigned long long)c) : ~0ull;
-  return ok;
-}
 __global__ void filt_voxel_keys(const float4* pts, int n, float size, unsigned long long* keys, int32_t* idx, int32_t* bad) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -338,6 +331,27 @@ static hipError_t run_range_image(FilterWorkspace* w, hipStream_t st, const smhi
   return compact(w, st);
 }
 
+// VoxelGrid from the keys on: keys[0] / idx[0] hold the current cloud's packed voxel keys and row numbers, counts[1] is non-zero
+// when a voxel index left +-2^20.  Stable radix sort -> voxel heads -> starts -> one thread per voxel averaging in arrival order.
+static hipError_t voxel_tail(FilterWorkspace* w, hipStream_t st) {
+  const int n = w->n, gp = (n + 255) / 256, c = w->cur, o = 1 - c;
+  size_t bytes = w->tmp_bytes;
+  FCHK(rocprim::radix_sort_pairs(w->tmp, bytes, w->keys[0], w->keys[1], w->idx[0], w->idx[1], (unsigned)n, 0, 64, st));
+  hipLaunchKernelGGL(filt_voxel_heads, dim3(gp), dim3(256), 0, st, w->keys[1], n, w->flag);
+  bytes = w->tmp_bytes;
+  FCHK(rocprim::inclusive_scan(w->tmp, bytes, w->flag, w->pos, (size_t)n, rocprim::plus<int32_t>(), st));
+  hipLaunchKernelGGL(filt_voxel_starts, dim3(gp), dim3(256), 0, st, w->flag, w->pos, n, w->start, w->counts);
+  hipLaunchKernelGGL(filt_voxel_average, dim3(gp), dim3(256), 0, st, w->pts[c], w->idx[1], w->start, w->counts, n,
+                     w->pts[o], w->fac[o], w->src[o]);
+  FCHK(hipMemcpyAsync(w->host_pinned, w->counts, 8, hipMemcpyDeviceToHost, st));
+  FCHK(hipStreamSynchronize(st));
+  if (w->host_pinned[1] != 0) return hipErrorInvalidValue;             // a voxel index beyond +-2^20
+  w->n = w->host_pinned[0];
+  w->cur = o;
+  w->has_index = false;
+  return hipSuccess;
+}
+
 static bool is_predicate(int t) { return t == SMHIP_FILTER_RANGE || t == SMHIP_FILTER_AXIS_RANGE || t == SMHIP_FILTER_BOUNDING_BOX_REMOVAL; }
 
 hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex* chain, int nf, int* n_out) {
@@ -363,23 +377,10 @@ hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter
       FCHK(compact(w, st));
     } else if (f.type == SMHIP_FILTER_VOXEL_GRID) {
       ++k;
-      const int c = w->cur, o = 1 - c;
+      const int c = w->cur;
       FCHK(hipMemsetAsync(w->counts + 1, 0, 4, st));
       hipLaunchKernelGGL(filt_voxel_keys, dim3(gp), dim3(256), 0, st, w->pts[c], n, f.p[0], w->keys[0], w->idx[0], w->counts + 1);
-      size_t bytes = w->tmp_bytes;
-      FCHK(rocprim::radix_sort_pairs(w->tmp, bytes, w->keys[0], w->keys[1], w->idx[0], w->idx[1], (unsigned)n, 0, 64, st));
-      hipLaunchKernelGGL(filt_voxel_heads, dim3(gp), dim3(256), 0, st, w->keys[1], n, w->flag);
-      bytes = w->tmp_bytes;
-      FCHK(rocprim::inclusive_scan(w->tmp, bytes, w->flag, w->pos, (size_t)n, rocprim::plus<int32_t>(), st));
-      hipLaunchKernelGGL(filt_voxel_starts, dim3(gp), dim3(256), 0, st, w->flag, w->pos, n, w->start, w->counts);
-      hipLaunchKernelGGL(filt_voxel_average, dim3(gp), dim3(256), 0, st, w->pts[c], w->idx[1], w->start, w->counts, n,
-                         w->pts[o], w->fac[o], w->src[o]);
-      FCHK(hipMemcpyAsync(w->host_pinned, w->counts, 8, hipMemcpyDeviceToHost, st));
-      FCHK(hipStreamSynchronize(st));
-      if (w->host_pinned[1] != 0) return hipErrorInvalidValue;             // a voxel index beyond +-2^20
-      w->n = w->host_pinned[0];
-      w->cur = o;
-      w->has_index = false;
+      FCHK(voxel_tail(w, st));
     } else if (f.type == SMHIP_FILTER_GROUND_REMOVAL) {
       ++k;
       FCHK(run_ground_removal(w, st, f));
@@ -393,6 +394,23 @@ hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter
       return hipErrorInvalidValue;
     }
   }
+  if (n_out) *n_out = w->n;
+  return hipGetLastError();
+}
+
+// ---- a cloud written by a kernel of another unit (smhip_submap.hip) -----------------------------
+FilterBuild filt_build_begin(FilterWorkspace* w, hipStream_t st) {
+  FilterBuild b{};
+  if (!w || hipMemsetAsync(w->counts + 1, 0, 4, st) != hipSuccess) return b;
+  b.pts = w->pts[0]; b.fac = w->fac[0]; b.src = w->src[0]; b.keys = w->keys[0]; b.idx = w->idx[0]; b.bad = w->counts + 1;
+  return b;
+}
+
+hipError_t filt_build_commit(FilterWorkspace* w, hipStream_t st, int n, bool keyed, int* n_out) {
+  if (!w || n <= 0 || n > w->cap) return hipErrorInvalidValue;
+  w->cur = 0; w->n = n; w->has_index = true;
+  if (keyed) FCHK(voxel_tail(w, st));
+  else FCHK(hipStreamSynchronize(st));
   if (n_out) *n_out = w->n;
   return hipGetLastError();
 }

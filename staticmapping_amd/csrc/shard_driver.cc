@@ -21,6 +21,15 @@
 // file with rows in voxel-key order.  The poses are the ones AS WRITTEN to the pose file (8 significant digits, parsed back),
 // so the map is a function of that file: --map-poses FILE builds the same map, byte for byte, with no alignment, no RCCL and
 // one process -- also from poses that came from elsewhere.
+//
+// --submap-edges PATH: the submaps of the sequence and the match of every pair of consecutive ones (Submap::InsertFrame,
+// builder/submap.cc:76-163; MapBuilder::SubmapPairMatch, builder/map_builder.cc:399-446).  Like --map, rank 0 works from the poses
+// AS WRITTEN to the pose file once the matchers are gone.  Frames [kN, (k + 1)N) form submap k (--submap-frames N); a trailing
+// group that is not full has no cloud (submap.cc:98) and is dropped.  Each submap is built on the device from its raw scans
+// (smhip_submap_build_f32: local pose = first pose^-1 * pose, VoxelGrid of --submap-voxel, 0 = none) and never leaves it: it
+// becomes the source against the previous submap's CalculateNormals target, then the target of the next.  IcpFast runs under
+// --iterations and --early-exit.  PATH holds one line per edge: `k k+1 accepted score` and the twelve numbers of
+// transform_to_next in the pose writer's format -- the match when score >= --submap-min-score, else the guess (:436-444).
 #include <dirent.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -49,6 +58,7 @@
 #include "../../include/smhip.h"
 #include "../../include/smhip/kitti_scans.h"
 #include "../../include/smhip/pcd.h"
+#include "../../include/smhip/back_end.h"
 
 namespace {
 
@@ -68,6 +78,10 @@ struct Args {
   int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
   float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
   bool map_average = false, map_rgb = false;
+  // consecutive submaps (--submap-edges); defaults: builder/submap_options.h:30-38 and accepted_min_score of the configs
+  std::string submap_edges;
+  int submap_frames = 5;
+  float submap_voxel = 0.1f, submap_min_score = 0.7f;
 };
 
 [[noreturn]] void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -131,17 +145,25 @@ Args Parse(int argc, char** argv) {
     else if (k == "--map-average") a.map_average = true;
     else if (k == "--map-rgb") a.map_rgb = true;
     else if (k == "--map-max-table-log2") a.map_max_table_log2 = std::atoi(val().c_str());
+    else if (k == "--submap-edges") a.submap_edges = val();
+    else if (k == "--submap-frames") a.submap_frames = std::atoi(val().c_str());
+    else if (k == "--submap-voxel") a.submap_voxel = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--submap-min-score") a.submap_min_score = static_cast<float>(std::atof(val().c_str()));
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
              "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
              "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
-             "[--map-max-table-log2 28]");
+             "[--map-max-table-log2 28]\n"
+             "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
   if (!a.map_poses.empty() && a.map_path.empty()) Die("--map-poses needs --map PATH");
   if (a.map_every < 1 || a.map_part_every < 0 || a.map_points_per_cell < 1 || a.map_max_table_log2 < 10 || a.map_max_table_log2 > 28 ||
       !(a.map_resolution > 0.f))
     Die("bad map setting (--map-every >= 1, --map-part-every >= 0, --map-points-per-cell >= 1, --map-max-table-log2 10..28, --map-resolution > 0)");
+  if (a.submap_frames < 1 || !(a.submap_voxel >= 0.f) || !std::isfinite(a.submap_voxel))
+    Die("bad submap setting (--submap-frames >= 1, --submap-voxel >= 0)");
+  if (!a.submap_edges.empty() && !a.map_poses.empty()) Die("--submap-edges needs the alignment run (not --map-poses)");
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
   if (a.world < 0 && std::getenv("WORLD_SIZE")) a.world = std::atoi(std::getenv("WORLD_SIZE"));
   if (a.local_rank < 0 && std::getenv("LOCAL_RANK")) a.local_rank = std::atoi(std::getenv("LOCAL_RANK"));
@@ -313,6 +335,126 @@ int BuildMap(const Args& a, const std::vector<std::string>& files, const std::ve
     for (const auto& f : written) std::remove(f.c_str());
   }
   smhip_mrvm_destroy(h);
+  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+// ---- --submap-edges -------------------------------------------------------------------------------------------------------
+// inverse of an affine 4x4 (column-major), what Eigen's inverse() gives for a pose: the 3x3 block by its adjugate
+Pose AffineInverse(const Pose& p) {
+  auto m = [&](int r, int c) { return p[4 * c + r]; };
+  const double c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1), c01 = m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2), c02 = m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0);
+  const double det = m(0, 0) * c00 + m(0, 1) * c01 + m(0, 2) * c02;
+  double inv[3][3] = {{c00 / det, (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) / det, (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) / det},
+                      {c01 / det, (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) / det, (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) / det},
+                      {c02 / det, (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) / det, (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) / det}};
+  Pose out{};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) out[4 * c + r] = inv[r][c];
+    out[12 + r] = -(inv[r][0] * m(0, 3) + inv[r][1] * m(1, 3) + inv[r][2] * m(2, 3));
+  }
+  out[15] = 1.0;
+  return out;
+}
+Pose MulPose(const Pose& a, const Pose& b) {                              // column-major a * b
+  Pose out{};
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) { double s = 0; for (int k = 0; k < 4; ++k) s += a[4 * k + r] * b[4 * c + k]; out[4 * c + r] = s; }
+  return out;
+}
+
+struct SubmapResult { int submaps = 0, edges = 0, accepted = 0; double seconds = 0.0, score_sum = 0.0; };
+
+std::string SubmapJsonFields(const Args& a, const SubmapResult& m) {
+  return Fmt(", \"submap_edges_file\": \"%s\", \"submaps\": %d, \"submap_edges\": %d, \"submap_edges_accepted\": %d, \"submap_mean_score\": %.6f, "
+             "\"submap_seconds\": %.4f", a.submap_edges.c_str(), m.submaps, m.edges, m.accepted, m.edges > 0 ? m.score_sum / m.edges : 0.0, m.seconds);
+}
+
+// The submaps of frames [0, n_frames) under `poses` and the match of consecutive ones; one line per edge to --submap-edges.
+// Returns 0, or 3 when the device refused a submap (the file is then removed).
+int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, SubmapResult* res) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
+  std::ofstream out(a.submap_edges);
+  if (!out) Die("cannot write " + a.submap_edges);
+  out.precision(8);
+  res->submaps = S;
+  if (S < 2) { res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); return 0; }
+  // capacity: the largest submap's rows together (every scan of a group is read whole)
+  long long cap = 16;
+  size_t max_bytes = 16;
+  for (int k = 0; k < S; ++k) {
+    long long rows = 0;
+    for (int f = k * N; f < (k + 1) * N; ++f) {
+      struct stat sb;
+      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+    }
+    cap = std::max(cap, rows);
+  }
+  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
+  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
+  smhip_handle h = nullptr;
+  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
+  if (st != SMHIP_OK) Die(std::string("smhip_create (submaps): ") + smhip_status_string(st));
+  smhip_icp_options o;
+  smhip_icp_default_options(&o);
+  o.max_iteration = a.iterations;
+  o.early_exit = a.early_exit;
+  if (smhip_icp_set_options(h, &o) != SMHIP_OK) Die(smhip_last_error(h));
+  // the six-decimal trip of the voxel size through the filter's text (submap.cc:148-154)
+  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
+
+  std::vector<int> order(static_cast<size_t>(S) * N);
+  for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
+  smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
+  int rc = 0;
+  for (int k = 0; k < S && rc == 0; ++k) {
+    std::vector<const float*> rows(N);
+    std::vector<int> n(N);
+    std::vector<double> local(16 * static_cast<size_t>(N));
+    const Pose first_inv = AffineInverse(poses[k * N]);
+    for (int f = 0; f < N; ++f) {
+      int fi = -1;
+      rows[f] = scans.Next(&n[f], &fi);
+      if (!rows[f] || fi != k * N + f) Die("submaps: prefetcher out of step");
+      if (n[f] < 0) Die("cannot read " + files[fi]);
+      const Pose lp = f == 0 ? Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} : MulPose(first_inv, poses[k * N + f]);   // submap.cc:83-87
+      std::memcpy(&local[16 * static_cast<size_t>(f)], lp.data(), sizeof(double) * 16);
+    }
+    int m = 0;
+    st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
+    scans.ReleaseHeld();                                                  // the call returned: the rows have left the host buffers
+    if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+    if (k > 0) {
+      // SubmapPairMatch(source = submap k, target = submap k - 1), map_builder.cc:399-446
+      if (smhip_filter_output_to_source(h, 0) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as source: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+      const Pose guess = MulPose(AffineInverse(poses[(k - 1) * N]), poses[k * N]);                  // :426-428
+      double result[16], score = 0.0;
+      smhip_icp_stats stats;
+      st = smhip_icp_align(h, guess.data(), result, &score, &stats);
+      if (st != SMHIP_OK) {                                              // no correspondence: an edge that keeps the guess
+        std::fprintf(stderr, "smhip_shard: submaps %d -> %d: %s (%s)\n", k - 1, k, smhip_status_string(st), smhip_last_error(h));
+        score = 0.0;
+      }
+      smhip::registrator::Matrix4d T;
+      std::memcpy(T.data(), result, sizeof(result));
+      smhip::back_end::NormalizeRotation(T);                             // :434
+      const bool accepted = st == SMHIP_OK && score >= a.submap_min_score;                           // :436-444
+      const double* e = accepted ? T.data() : guess.data();
+      out << (k - 1) << " " << k << " " << (accepted ? 1 : 0) << " " << score;
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out << " " << e[4 * c + r];
+      out << "\n";
+      ++res->edges; res->accepted += accepted ? 1 : 0; res->score_sum += score;
+    }
+    // the cloud is still resident: it becomes the target of the next pair (Submap::Cloud() carries normals, submap.cc:160-161)
+    if (k + 1 < S && smhip_filter_output_to_target(h, 0, &m) != SMHIP_OK) {
+      std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h));
+      rc = 3;
+    }
+  }
+  out.close();
+  smhip_destroy(h);
+  if (rc != 0) std::remove(a.submap_edges.c_str());
   res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
@@ -586,7 +728,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
                   "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
-      if (a.map_path.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
+      if (a.map_path.empty() && a.submap_edges.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;
   }
@@ -595,15 +737,23 @@ int RunRank(const Args& a, int rank, int world, int device) {
   if (pinned) for (float* b : ring_buffers) (void)hipHostFree(b);
   NCCLOK(ncclCommDestroy(comm));
   for (int k = 0; k < NH; ++k) (void)hipStreamDestroy(streams[k]);
-  if (rank == 0 && !a.map_path.empty()) {
-    // the static map from the poses as written: the pose file read back (--map-poses on that file builds the same map)
-    MapResult m;
-    if (rc == 0) {
-      std::vector<Pose> poses;
-      if (!ReadPoses(a.out_path, &poses) || static_cast<int>(poses.size()) != n_pairs + 1) Die("cannot read back " + a.out_path);
+  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty())) {
+    // the static map and the submap edges from the poses as written: the pose file read back (--map-poses on that file builds
+    // the same map)
+    std::string fields;
+    std::vector<Pose> poses;
+    if (rc == 0 && (!ReadPoses(a.out_path, &poses) || static_cast<int>(poses.size()) != n_pairs + 1)) Die("cannot read back " + a.out_path);
+    if (rc == 0 && !a.map_path.empty()) {
+      MapResult m;
       rc = BuildMap(a, files, MapFrames(a, n_pairs + 1), poses, device, &m);
+      if (rc == 0) fields += MapJsonFields(a, m);
     }
-    if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? MapJsonFields(a, m).c_str() : "");
+    if (rc == 0 && !a.submap_edges.empty()) {
+      SubmapResult m;
+      rc = BuildSubmapEdges(a, files, n_pairs + 1, poses, device, &m);
+      if (rc == 0) fields += SubmapJsonFields(a, m);
+    }
+    if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? fields.c_str() : "");
   }
   return rc;
 }

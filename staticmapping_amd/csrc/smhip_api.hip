@@ -391,6 +391,27 @@ static void sync_options(smhip_context* h) {
   { const char* e = std::getenv("SMHIP_NABO_LISTED_BLOCKS"); if (e && std::atoi(e) > 0) h->nabo_listed_blocks = std::max(8, std::min(4096, std::atoi(e))); }   // >= 8: a workgroup's 16-bit histogram bins
 }
 
+// device CalculateNormals of n device rows (xyz in .x .y .z) into the target of `slot`; the workspace is there (prep_ensure)
+smhip_status prep_run(smhip_context* h, const float4* raw_dev, int n, int slot, int* n_out) {
+  // the leaf count is only known afterwards: run into the scratch halves of the staging-sized device buffer
+  // when the slot's arrays could overflow, i.e. require nt_cap >= n / 4 + 8 (every leaf holds >= 4 points)
+  if (h->dev.nt_cap < n / 4 + 8) { h->err = "max_target_points too small for the prepared target (need n / 4 + 8)"; return SMHIP_ERR_CAPACITY; }
+  int m = 0;
+  const hipError_t e = prep_calculate_normals(h->prep, h->stream, raw_dev, n,
+                                              const_cast<float4*>(h->dev.tgt_p) + (size_t)slot * h->dev.nt_cap,
+                                              const_cast<float4*>(h->dev.tgt_n) + (size_t)slot * h->dev.nt_cap, &m);
+  // from here on the slot's target arrays have been written: whatever target it held is gone, also on the error paths
+  touch_target(h, slot);
+  h->nt[slot] = 0; h->has_normals[slot] = 0;
+  if (e != hipSuccess) { h->err = std::string("prep_calculate_normals: ") + hipGetErrorString(e); return SMHIP_ERR_HIP; }
+  if (m <= 0) { h->err = "CalculateNormals produced no target points"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  h->nt[slot] = m;
+  h->has_normals[slot] = 1;
+  touch_target(h, slot);
+  if (n_out) *n_out = m;
+  return SMHIP_OK;
+}
+
 }  // namespace smhip_host
 
 namespace {
@@ -828,26 +849,6 @@ smhip_status smhip_set_target_f32(smhip_handle h, int slot, const float* xyz, in
   h->nt[slot] = n;
   h->has_normals[slot] = nrm != nullptr;
   touch_target(h, slot);
-  return SMHIP_OK;
-}
-
-static smhip_status prep_run(smhip_handle h, const float4* raw_dev, int n, int slot, int* n_out) {
-  // the leaf count is only known afterwards: run into the scratch halves of the staging-sized device buffer
-  // when the slot's arrays could overflow, i.e. require nt_cap >= n / 4 + 8 (every leaf holds >= 4 points)
-  if (h->dev.nt_cap < n / 4 + 8) { h->err = "max_target_points too small for the prepared target (need n / 4 + 8)"; return SMHIP_ERR_CAPACITY; }
-  int m = 0;
-  const hipError_t e = prep_calculate_normals(h->prep, h->stream, raw_dev, n,
-                                              const_cast<float4*>(h->dev.tgt_p) + (size_t)slot * h->dev.nt_cap,
-                                              const_cast<float4*>(h->dev.tgt_n) + (size_t)slot * h->dev.nt_cap, &m);
-  // from here on the slot's target arrays have been written: whatever target it held is gone, also on the error paths
-  touch_target(h, slot);
-  h->nt[slot] = 0; h->has_normals[slot] = 0;
-  if (e != hipSuccess) { h->err = std::string("prep_calculate_normals: ") + hipGetErrorString(e); return SMHIP_ERR_HIP; }
-  if (m <= 0) { h->err = "CalculateNormals produced no target points"; return SMHIP_ERR_INVALID_ARGUMENT; }
-  h->nt[slot] = m;
-  h->has_normals[slot] = 1;
-  touch_target(h, slot);
-  if (n_out) *n_out = m;
   return SMHIP_OK;
 }
 

@@ -1,7 +1,7 @@
 // smhip_context.h -- what the host translation units of libsmhip.so share: the handle behind smhip_handle, the error and
 // allocation helpers every entry point uses, and the handful of functions of the ICP unit (smhip_api.hip) that the NDT /
-// NdtWithGicp unit (smhip_ndt_gicp.hip) and the filter unit (smhip_filter_api.hip) call.  Internal: not installed, not part
-// of the C ABI (include/smhip.h).  Everything else in those units is file-local.
+// NdtWithGicp unit (smhip_ndt_gicp.hip), the filter unit (smhip_filter_api.hip) and the submap unit (smhip_submap.hip) call.
+// Internal: not installed, not part of the C ABI (include/smhip.h).  Everything else in those units is file-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +27,9 @@ struct smhip_context {
   PrepWorkspace* prep_batch = nullptr;    // the same sized for every slot at once (batched target preparation)
   FilterWorkspace* filt = nullptr;        // device pre-filters (allocated on first use)
   float4* prep_raw = nullptr;             // raw scan staging on the device
+  float* submap_raw = nullptr;            // smhip_submap_build_f32: the frames' raw rows (5 floats per point of the filter workspace)
+  void* submap_frames = nullptr;          // and its per-frame table (offset, n, pose), room for submap_frames_cap frames
+  int submap_frames_cap = 0;
   float4* raw_batch = nullptr;            // the same for a whole batch of scans (smhip_set_sources_f32_batch; allocated on first use)
   hipStream_t copy_stream = nullptr;      // host-to-device copies of a batch of page-locked scans (overlap the handle's stream)
   hipEvent_t ev_copied = nullptr, ev_raw_free = nullptr;
@@ -137,9 +140,12 @@ struct Half {
   int first_fused = -1;    // the first iteration of this Align that ran the fused path
 };
 
+// Defined in smhip_filter_api.hip: the filter workspace (and prep_ensure's), allocated on first use.
+smhip_status filter_ensure(smhip_context* h);
 // Defined in smhip_api.hip (the ICP unit), where each is described.
 smhip_status check_slot(smhip_context* h, int slot);
 smhip_status prep_ensure(smhip_context* h);
+smhip_status prep_run(smhip_context* h, const float4* raw_dev, int n, int slot, int* n_out);
 smhip_status enqueue_resets(smhip_context* h, int np, int first = 0);
 smhip_status enqueue_grid_build(smhip_context* h, const Half& f, int nt_max);
 bool grid_cached(smhip_context* h, int slot);

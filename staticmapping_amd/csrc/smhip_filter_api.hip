@@ -13,6 +13,17 @@
 
 using namespace smhip_host;
 
+namespace smhip_host {
+smhip_status filter_ensure(smhip_context* h) {
+  smhip_status s = prep_ensure(h);
+  if (s) return s;
+  if (h->filt) return SMHIP_OK;
+  h->filt = filt_create(std::max(h->dev.ns_cap, h->dev.nt_cap));
+  if (!h->filt) { h->err = "filter workspace allocation failed"; return SMHIP_ERR_HIP; }
+  return SMHIP_OK;
+}
+}  // namespace smhip_host
+
 extern "C" {
 
 void smhip_filter_default(int type, smhip_filter_desc* f) {
@@ -40,15 +51,6 @@ int smhip_filter_config_valid(const smhip_filter_desc* f) {
     case SMHIP_FILTER_BOUNDING_BOX_REMOVAL: return f->p[0] < f->p[3] && f->p[1] < f->p[4] && f->p[2] < f->p[5];   // filter_bounding_box.cc:49-51
   }
   return 0;
-}
-
-static smhip_status filter_ensure(smhip_handle h) {
-  smhip_status s = prep_ensure(h);
-  if (s) return s;
-  if (h->filt) return SMHIP_OK;
-  h->filt = filt_create(std::max(h->dev.ns_cap, h->dev.nt_cap));
-  if (!h->filt) { h->err = "filter workspace allocation failed"; return SMHIP_ERR_HIP; }
-  return SMHIP_OK;
 }
 
 static smhip_filter_desc_ex widen(const smhip_filter_desc& f) {
