@@ -446,6 +446,21 @@ smhip_status smhip_filter_chain_f32(smhip_handle h, const float* points, int str
 smhip_status smhip_filter_get_output(smhip_handle h, float* points5, int32_t* source_index, int n);
 /* the filtered cloud becomes SetInputSource of `slot` without leaving the device */
 smhip_status smhip_filter_output_to_source(smhip_handle h, int slot);
+/* MotionCompensation (builder/map_builder.cc:232-257) of the filter workspace's current cloud by `delta` (column-major 4x4)
+ * -> source of `slot`, on the device.  The workspace is left as it was, so the call can be repeated with another delta (the
+ * front end compensates with the guess before Align and with the result after it).  points5_out (may be NULL): the compensated
+ * cloud as InnerPointType rows in the workspace's row order.
+ * Row i moves by common::InterpolateTransform(I, delta, factor_i) (common/math.h:199-211): Eigen's slerp from the identity to
+ * delta's rotation (not normalised) and delta's translation times the factor, the product in double, each coordinate cast to
+ * float; intensity and factor are carried.  The raw cloud gets into the workspace as for smhip_filter_output_to_source: a filter
+ * chain (n_filters = 0 for an unfiltered scan; stride 4 rows get factor = i / n, stride 5 rows carry their own) or a built submap.
+ * Refused before anything is touched: a bad slot, a null or non-finite delta, an empty cloud -- SMHIP_ERR_INVALID_ARGUMENT; no
+ * cloud in the workspace -- SMHIP_ERR_NOT_READY; more rows than max_source_points -- SMHIP_ERR_CAPACITY.
+ * A factor outside [0, 1] or NaN (the reference CHECK-aborts, math.h:202) is found by the kernel and reported through a flag:
+ * SMHIP_ERR_INVALID_ARGUMENT AFTER the slot's source array was written.  The slot then has NO source (smhip_get_cloud_sizes
+ * gives 0 and Align answers SMHIP_ERR_NOT_READY until a source is set again), points5_out is not written, and the workspace
+ * still holds the cloud. */
+smhip_status smhip_filter_output_to_source_compensated(smhip_handle h, int slot, const double delta[16], float* points5_out);
 
 /* ---- the extended descriptor: every filter above plus GroundRemoval / GroundRemoval2 / RangeImage ------------
  * (pre_processors/filter_ground_removal.cc, filter_ground_removal2.cc, filter_range_image.cc Filter()).  Slots:

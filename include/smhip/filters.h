@@ -27,14 +27,6 @@
 #include "smhip/registrator.h"
 
 namespace smhip {
-namespace data {
-struct InnerCloudType {                     // cloud_types.h:60-77 (the stamp is carried through FilterPrepare)
-  int64_t stamp = 0;
-  std::vector<InnerPointType> points;
-  using Ptr = std::shared_ptr<InnerCloudType>;
-};
-}  // namespace data
-
 namespace pre_processers {
 namespace filter {
 

@@ -47,6 +47,12 @@ namespace data {
 struct InnerPointType {
   float x = 0.f, y = 0.f, z = 0.f, intensity = 0.f, factor = 0.f;
 };
+static_assert(sizeof(InnerPointType) == 5 * sizeof(float), "InnerPointType rows go to the C ABI as 5 floats");
+struct InnerCloudType {                     // cloud_types.h:60-77 (the stamp is carried through the filters and the motion compensation)
+  int64_t stamp = 0;
+  std::vector<InnerPointType> points;
+  using Ptr = std::shared_ptr<InnerCloudType>;
+};
 
 // The parts of data::EigenPointCloud (cloud_types.h:121-147) the registrators use:
 // 3xN column-major double points / normals (xyzxyz...).
@@ -83,6 +89,12 @@ class InnerPointCloudData {
  public:
   using Ptr = std::shared_ptr<InnerPointCloudData>;
   explicit InnerPointCloudData(const std::vector<InnerPointType>& cloud) : inner_cloud_(cloud) {
+    eigen_cloud_.reset(new EigenPointCloud);
+    if (!cloud.empty()) eigen_cloud_->FromPointCloud(cloud);
+  }
+  // cloud_types.cc:412-424: the points are replaced and the eigen cloud is built again from them (its normals are gone)
+  void SetInnerCloud(const std::vector<InnerPointType>& cloud) {
+    inner_cloud_ = cloud;
     eigen_cloud_.reset(new EigenPointCloud);
     if (!cloud.empty()) eigen_cloud_->FromPointCloud(cloud);
   }
@@ -305,6 +317,7 @@ class IcpFastHip : public Interface {
     SMHIP_CHECK(cloud->GetEigenCloud() != nullptr, "CHECK(cloud->GetEigenCloud())");
     // the cloud the device holds changes only when the upload succeeds; a refused cloud leaves the matcher without a
     // source (Align then fails loudly instead of matching the previous scan)
+    compensated_source_ = false;
     source_ok_ = EnsureHandle(cloud->GetEigenCloud()->size(), 0, false, true) && UploadSource(*cloud);
     source_keep_ = source_ok_ ? cloud : nullptr;
   }
@@ -366,7 +379,7 @@ class IcpFastHip : public Interface {
   // device refused.  No host copy exists, so a later re-size of the handle (a cloud more than 1.5 times larger arriving) cannot
   // restore a resident cloud: the matcher is then without it and Align fails loudly -- hand over the larger cloud first.
   int SetInputSourceResident(int rows, const std::function<bool(smhip_handle)>& build) {
-    source_ok_ = false; source_keep_ = nullptr;
+    source_ok_ = false; source_keep_ = nullptr; compensated_source_ = false;
     if (!EnsureHandle(rows, rows, false, true) || !build(arena_.handle)) return 0;
     if (!Ok(smhip_filter_output_to_source(arena_.handle, 0), "smhip_filter_output_to_source")) return 0;
     int ns = 0;
@@ -374,6 +387,34 @@ class IcpFastHip : public Interface {
     source_ok_ = true;
     return ns;
   }
+  // The front end's motion compensation on the device (front_end.h; MotionCompensation, map_builder.cc:232-257, called before and
+  // after Align, :320-352).  LoadScan sends the scan's uncompensated rows up ONCE, into the handle's filter workspace, and sizes the
+  // handle for the scan as a source and as a promoted target, so that nothing between here and PromoteSourceToTarget re-sizes it.
+  // Each SetInputSourceCompensated then makes the scan, de-skewed by `delta`, the source (smhip_filter_output_to_source_compensated).
+  // With `hand_back` the compensated rows come back and replace that cloud's points (SetInnerCloud, :351): the host cloud then
+  // holds what the device's source holds, which is what PromoteSourceToTarget and a re-size of the handle need (source_keep_).
+  // Without it no host copy exists; the rows and the delta are kept instead, and a re-created handle de-skews them again.
+  bool LoadScan(std::shared_ptr<const std::vector<data::InnerPointType>> rows) {
+    scan_ = nullptr; scan_resident_ = false;
+    if (!rows || rows->empty()) { std::fprintf(stderr, "[WARNING] cloud is empty.\n"); return false; }
+    const int n = static_cast<int>(rows->size());
+    if (!EnsureHandle(n, n / 4 + 8, true, true)) return false;
+    scan_ = std::move(rows);
+    return UploadScan();
+  }
+  bool SetInputSourceCompensated(const Matrix4d& delta, InnerCloudPtr hand_back = nullptr) {
+    source_ok_ = false; source_keep_ = nullptr; compensated_source_ = false;
+    if (!scan_ || !EnsureHandle(0, 0, false, true)) return false;
+    if (!scan_resident_ && !UploadScan()) return false;
+    std::vector<data::InnerPointType> rows(hand_back ? scan_->size() : 0);
+    if (!Ok(smhip_filter_output_to_source_compensated(arena_.handle, 0, delta.data(), hand_back ? &rows[0].x : nullptr),
+            "smhip_filter_output_to_source_compensated")) return false;
+    source_ok_ = true;
+    if (hand_back) { hand_back->SetInnerCloud(rows); source_keep_ = hand_back; }
+    else { compensated_source_ = true; compensated_delta_ = delta; }
+    return true;
+  }
+
   int SetInputTargetResident(int rows, const std::function<bool(smhip_handle)>& build) {
     target_ok_ = false; target_keep_ = nullptr; target_kind_ = kNoTarget;
     if (!EnsureHandle(rows, rows, true, false) || !build(arena_.handle)) return 0;
@@ -455,6 +496,12 @@ class IcpFastHip : public Interface {
     const auto& e = *cloud.GetEigenCloud();
     return Ok(smhip_set_source_f64(arena_.handle, 0, e.points.data(), e.size()), "smhip_set_source_f64");
   }
+  bool UploadScan() {                                  // an unfiltered chain: the rows become the filter workspace's cloud
+    int n_out = 0;
+    scan_resident_ = Ok(smhip_filter_chain_f32(arena_.handle, &(*scan_)[0].x, 5, static_cast<int>(scan_->size()), nullptr, 0, &n_out),
+                        "smhip_filter_chain_f32");
+    return scan_resident_;
+  }
   bool UploadTarget(const data::InnerPointCloudData& cloud, TargetKind kind) {
     const auto& e = *cloud.GetEigenCloud();
     if (kind == kTargetWithNormals)
@@ -488,7 +535,12 @@ class IcpFastHip : public Interface {
     }
     if (!ApplyOptions(arena_.handle)) return false;
     if (recreated) {
-      if (!source_keep_) source_ok_ = false;          // a resident cloud without a host copy went with the old handle
+      scan_resident_ = false;                         // the filter workspace went with the old handle
+      if (!source_keep_ && source_ok_ && compensated_source_ && restore_source && scan_) {   // de-skew the kept rows again
+        source_ok_ = UploadScan() && Ok(smhip_filter_output_to_source_compensated(arena_.handle, 0, compensated_delta_.data(), nullptr),
+                                        "smhip_filter_output_to_source_compensated");
+        if (!source_ok_) return false;
+      } else if (!source_keep_) source_ok_ = false;   // a resident cloud without a host copy went with the old handle
       if (!target_keep_) target_ok_ = false;
       if (restore_source && source_keep_ && !UploadSource(*source_keep_)) { source_ok_ = false; return false; }
       if (restore_target && target_keep_ && target_kind_ != kNoTarget && !UploadTarget(*target_keep_, target_kind_)) { target_ok_ = false; return false; }
@@ -510,6 +562,10 @@ class IcpFastHip : public Interface {
   int32_t max_points_;
   DeviceArena arena_;
   DeviceArena batch_arena_;                    // AlignBatch's K-slot handle
+  std::shared_ptr<const std::vector<data::InnerPointType>> scan_;   // LoadScan's rows (to send up again after a re-size)
+  bool scan_resident_ = false;                 // the filter workspace holds them
+  bool compensated_source_ = false;            // the source is scan_ de-skewed by compensated_delta_, and no host copy exists
+  Matrix4d compensated_delta_ = Matrix4d::Identity();
   InnerCloudPtr source_keep_, target_keep_;   // what the device holds (icp_fast.cc:424,431 deep-copies; here: to re-upload after a re-size)
   TargetKind target_kind_ = kNoTarget;
   int prepared_points_ = 0;

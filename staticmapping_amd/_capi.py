@@ -158,6 +158,7 @@ SIGNATURES = {
                                               ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_filter_get_output": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, ctypes.c_int]),
     "smhip_filter_output_to_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "smhip_filter_output_to_source_compensated": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_float_p]),
     "smhip_filter_default_ex": (None, [ctypes.c_int, ctypes.POINTER(FilterDescEx)]),
     "smhip_filter_config_valid_ex": (ctypes.c_int, [ctypes.POINTER(FilterDescEx)]),
     "smhip_filter_chain_ex_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FilterDescEx),

@@ -30,6 +30,45 @@ const int32_t* filt_source_index(const FilterWorkspace* w);  // row of the ORIGI
 int filt_count(const FilterWorkspace* w);
 bool filt_has_index(const FilterWorkspace* w);
 
+// MotionCompensation (builder/map_builder.cc:232-257) of the current cloud, motion_comp.hip.  What InterpolateTransform
+// (common/math.h:199-211) derives from delta alone, once per call: q_b = Eigen's Quaternion(Matrix3) of delta's rotation block
+// (trace branch / largest-diagonal branch, w may come out negative in the second), d = q_a . q_b = q_b.w for q_a = (1, 0, 0, 0),
+// the branch of Eigen's slerp (|d| >= 1 - DBL_EPSILON: linear scales), theta = acos(|d|), sin(theta), and whether the second
+// scale is negated (d < 0).
+struct MotionCompArgs {
+  double bx, by, bz, bw;        // q_b
+  double theta, sin_theta;      // unused when `linear`
+  double tx, ty, tz;            // delta's translation
+  int32_t linear, negate;
+};
+inline MotionCompArgs motion_comp_args(const double m[16] /* column-major 4x4 */) {
+  auto R = [&](int r, int c) { return m[4 * c + r]; };
+  MotionCompArgs a{};
+  double q[3], w, t = R(0, 0) + R(1, 1) + R(2, 2);
+  if (t > 0) {
+    t = std::sqrt(t + 1.0); w = 0.5 * t; t = 0.5 / t;
+    q[0] = (R(2, 1) - R(1, 2)) * t; q[1] = (R(0, 2) - R(2, 0)) * t; q[2] = (R(1, 0) - R(0, 1)) * t;
+  } else {
+    int i = 0; if (R(1, 1) > R(0, 0)) i = 1; if (R(2, 2) > R(i, i)) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0); q[i] = 0.5 * t; t = 0.5 / t;
+    w = (R(k, j) - R(j, k)) * t; q[j] = (R(j, i) + R(i, j)) * t; q[k] = (R(k, i) + R(i, k)) * t;
+  }
+  a.bx = q[0]; a.by = q[1]; a.bz = q[2]; a.bw = w;
+  const double d = 1.0 * w + 0.0 * q[0] + 0.0 * q[1] + 0.0 * q[2], abs_d = std::fabs(d);
+  a.linear = abs_d >= 1.0 - 2.220446049250313e-16 ? 1 : 0;
+  if (!a.linear) { a.theta = std::acos(abs_d); a.sin_theta = std::sin(a.theta); }
+  a.negate = d < 0 ? 1 : 0;
+  a.tx = m[12]; a.ty = m[13]; a.tz = m[14];
+  return a;
+}
+// writes the compensated rows (x y z intensity, the workspace's row order) to `out` (room for filt_count rows) and leaves the
+// workspace as it was.  A row whose factor is outside [0, 1] or NaN sets a device flag by a plain store (the row is copied
+// unchanged); the flag travels to pinned memory behind the kernel: once `st` has been synchronised, filt_motion_bad_factor says
+// whether the last call met such a row.  Asynchronous on `st`.
+hipError_t filt_motion_compensate(FilterWorkspace* w, hipStream_t st, const MotionCompArgs& a, float4* out);
+bool filt_motion_bad_factor(const FilterWorkspace* w);
+
 // GroundRemoval2::ClusterGround, filter_ground_removal2.cc:318-320: search_angle_ / 180. * M_PI / delta_alpha in double with
 // delta_alpha = (float)(M_PI * 2 / segment_num_), truncated as x86 does (INT_MIN outside the int range)
 inline int gr2_search_step(float search_angle, int segment_num) {

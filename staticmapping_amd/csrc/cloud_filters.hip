@@ -10,6 +10,7 @@
 //   filter_ground_removal2.cc       GroundRemoval2      drop points near fitted ground lines   } what is and is not pinned:
 //   filter_range_image.cc           RangeImage          keep the first point of every pixel    } DESIGN.md §6, "Pre-filters"
 //   filter_factory.cc:83-106       Factory::Filter     the filters of <filters> applied in order
+//   builder/map_builder.cc:232-257  MotionCompensation  the front end's de-skew of the filtered cloud (kernel in motion_comp.hip)
 // They run on every scan right before the registrator (builder/data/data_collector.h, config/lidar_only_kitti.xml:18-41).
 // All but VoxelGrid are order-preserving compactions: flag -> exclusive scan (rocPRIM building block) -> scatter;
 // consecutive predicate filters share one pass.  VoxelGrid is a stable radix sort on the packed voxel index and one
@@ -132,6 +133,7 @@ __global__ void filt_voxel_average(const float4* pts, const int32_t* idx, const 
 }
 
 #include "ground_filters.hip"
+#include "motion_comp.hip"
 
 __global__ void filt_init(const float4* in, int n, int stride5, const float* fac_in, float4* pts, float* fac, int32_t* src) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -414,6 +416,17 @@ hipError_t filt_build_commit(FilterWorkspace* w, hipStream_t st, int n, bool key
   if (n_out) *n_out = w->n;
   return hipGetLastError();
 }
+
+// ---- MotionCompensation of the current cloud (kernel: motion_comp.hip) ---------------------------
+hipError_t filt_motion_compensate(FilterWorkspace* w, hipStream_t st, const MotionCompArgs& a, float4* out) {
+  if (!w || !out || w->n <= 0 || w->n > w->cap) return hipErrorInvalidValue;
+  const int n = w->n, c = w->cur;
+  FCHK(hipMemsetAsync(w->counts + 2, 0, 4, st));
+  hipLaunchKernelGGL(filt_motion_comp, dim3((n + 255) / 256), dim3(256), 0, st, w->pts[c], w->fac[c], n, a, out, w->counts + 2);
+  FCHK(hipGetLastError());
+  return hipMemcpyAsync(w->host_pinned + 3, w->counts + 2, 4, hipMemcpyDeviceToHost, st);
+}
+bool filt_motion_bad_factor(const FilterWorkspace* w) { return w->host_pinned[3] != 0; }
 
 const float4* filt_points(const FilterWorkspace* w) { return w->pts[w->cur]; }
 const float* filt_factors(const FilterWorkspace* w) { return w->fac[w->cur]; }

@@ -195,4 +195,45 @@ smhip_status smhip_filter_output_to_source(smhip_handle h, int slot) {
   return SMHIP_OK;
 }
 
+// MotionCompensation (map_builder.cc:232-257) of the filtered cloud -> SetInputSource of `slot`, on the device: the compensated
+// rows go to the raw-scan staging array, from where prep_morton_sort orders them into the slot as it orders an uploaded scan
+smhip_status smhip_filter_output_to_source_compensated(smhip_handle h, int slot, const double delta[16], float* points5_out) {
+  smhip_status s = check_slot(h, slot);
+  if (s) return s;
+  if (!delta) { h->err = "null delta"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(delta[k])) { h->err = "delta is not finite"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (!h->filt) { h->err = "no filter chain has run"; return SMHIP_ERR_NOT_READY; }
+  const int n = filt_count(h->filt);
+  if (n <= 0) { h->err = "the filtered cloud is empty"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (n > h->dev.ns_cap) { h->err = "filtered cloud larger than max_source_points"; return SMHIP_ERR_CAPACITY; }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipError_t e = filt_motion_compensate(h->filt, h->stream, motion_comp_args(delta), h->prep_raw);
+  if (e != hipSuccess) { h->err = std::string("filt_motion_compensate: ") + hipGetErrorString(e); return SMHIP_ERR_HIP; }
+  // from here on the slot's source array is written: whatever source it held is gone, also when a factor is refused below
+  h->ns[slot] = 0;
+  touch_source(h, slot);
+  e = prep_morton_sort(h->prep, h->stream, h->prep_raw, n, const_cast<float4*>(h->dev.src) + (size_t)slot * h->dev.ns_cap);
+  if (e != hipSuccess) { h->err = std::string("prep_morton_sort: ") + hipGetErrorString(e); return SMHIP_ERR_HIP; }
+  float* fac = reinterpret_cast<float*>(h->stage + std::max(h->dev.ns_cap, h->dev.nt_cap));
+  if (points5_out) {
+    HIPCHK(h, hipMemcpyAsync(h->stage, h->prep_raw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(fac, filt_factors(h->filt), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (filt_motion_bad_factor(h->filt)) {
+    h->err = "a row's factor is outside [0, 1] or NaN (CHECK(factor >= 0. && factor <= 1.), common/math.h:202)";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  if (points5_out)
+    for (int i = 0; i < n; ++i) {
+      const float4 p = h->stage[i];
+      float* o = points5_out + 5 * (size_t)i;
+      o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.w; o[4] = fac[i];
+    }
+  h->ns[slot] = n;
+  touch_source(h, slot);
+  return SMHIP_OK;
+}
+
 }  // extern "C"

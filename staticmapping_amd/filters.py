@@ -130,4 +130,25 @@ def run_chain_resident(matcher, points, chain) -> int:
 
 
 def output_to_source(matcher, slot: int = 0):
+    """The filtered cloud becomes the source of `slot` on the device (output_to_source_compensated de-skews it on the way)."""
     matcher._check(matcher._lib.smhip_filter_output_to_source(matcher._h, slot))
+
+
+def output_to_source_compensated(matcher, delta, slot: int = 0, download: bool = False):
+    """MotionCompensation (builder/map_builder.cc:232-257) of the filtered cloud by the 4x4 `delta` -> source of `slot`, on the
+    device; the filter workspace keeps its cloud, so the call can be repeated with another delta.  download=True returns the
+    compensated cloud as [M,5] float32 rows in the workspace's row order."""
+    d = np.asarray(delta, dtype=np.float64)
+    if d.shape != (4, 4):
+        raise ValueError("delta must be a 4x4 matrix")
+    d = np.ascontiguousarray(d.T)                      # column-major for the C ABI
+    if not download:
+        matcher._check(matcher._lib.smhip_filter_output_to_source_compensated(matcher._h, slot, d.ctypes.data_as(_capi.c_double_p), None))
+        return None
+    cap, m = ctypes.c_int(), ctypes.c_int()            # the filtered size is at most max_source_points, or the call refuses
+    matcher._check(matcher._lib.smhip_get_capacity(matcher._h, None, ctypes.byref(cap), None))
+    out = np.empty((cap.value, 5), np.float32)
+    matcher._check(matcher._lib.smhip_filter_output_to_source_compensated(matcher._h, slot, d.ctypes.data_as(_capi.c_double_p),
+                                                                         out.ctypes.data_as(_capi.c_float_p)))
+    matcher._check(matcher._lib.smhip_get_cloud_sizes(matcher._h, slot, ctypes.byref(m), None, None))
+    return out[:m.value].copy()
