@@ -462,8 +462,9 @@ smhip_status smhip_filter_output_to_source(smhip_handle h, int slot);
  * still holds the cloud. */
 smhip_status smhip_filter_output_to_source_compensated(smhip_handle h, int slot, const double delta[16], float* points5_out);
 
-/* ---- the extended descriptor: every filter above plus GroundRemoval / GroundRemoval2 / RangeImage ------------
- * (pre_processors/filter_ground_removal.cc, filter_ground_removal2.cc, filter_range_image.cc Filter()).  Slots:
+/* ---- the extended descriptor: every filter above plus GroundRemoval / GroundRemoval2 / RangeImage / StatisticRemoval ------
+ * (pre_processors/filter_ground_removal.cc, filter_ground_removal2.cc, filter_range_image.cc Filter(); filter_statistic_removal.cc
+ * gives StatisticRemoval's parameters only, what it computes is defined in DESIGN.md §6).  Slots:
  *   RANGE .. BOUNDING_BOX_REMOVAL  p[0..5] as in smhip_filter_desc, i[0] axis_index; seed as there
  *   GROUND_REMOVAL   p[0] leaf_size, p[1] height_threshold; i[0] min_point_num_in_voxel
  *   GROUND_REMOVAL2  p[0] r_max, p[1] r_min, p[2] start_ground_height, p[3] long_line_threshold, p[4] max_long_line_height,
@@ -471,10 +472,15 @@ smhip_status smhip_filter_output_to_source_compensated(smhip_handle h, int slot,
  *                    p[9] max_dist_to_line, p[10] search_angle; i[0] bin_num, i[1] segment_num, i[2] thread_num (ignored)
  *   RANGE_IMAGE      p[0] top_angle, p[1] btm_angle, p[2] offset_x, p[3] offset_y, p[4] offset_z;
  *                    i[0] vertical_line_num, i[1] horizontal_line_num
+ *   STATISTIC_REMOVAL  p[0] std_mul; i[0] point_num_meank
  * Device limits (refused with SMHIP_ERR_INVALID_ARGUMENT): bin_num <= 4096, bin_num * segment_num <= 2^22, the search
  * of neighbouring segments within one turn, vertical_line_num * horizontal_line_num <= 2^22, voxel indices within +-2^20.
- * Rows with a non-finite x, y or z are kept by both ground filters and dropped by RangeImage. */
-enum { SMHIP_FILTER_GROUND_REMOVAL = 6, SMHIP_FILTER_GROUND_REMOVAL2 = 7, SMHIP_FILTER_RANGE_IMAGE = 8 };
+ * 1 <= point_num_meank <= 64 (a query's best-k set lives in LDS); std_mul must be finite.
+ * Rows with a non-finite x, y or z are kept by both ground filters and by StatisticRemoval and dropped by RangeImage.
+ * StatisticRemoval has NO coordinate range: it searches the cloud sorted along one axis, not a grid, so any finite coordinates are
+ * answered exactly.  When no more than point_num_meank rows are finite it keeps every row, returns SMHIP_OK and leaves a
+ * "warning: ..." in smhip_last_error.  smhip_filter_chain_f32 does not take the extended ids 6-9. */
+enum { SMHIP_FILTER_GROUND_REMOVAL = 6, SMHIP_FILTER_GROUND_REMOVAL2 = 7, SMHIP_FILTER_RANGE_IMAGE = 8, SMHIP_FILTER_STATISTIC_REMOVAL = 9 };
 typedef struct smhip_filter_desc_ex {
   int32_t type;
   uint32_t seed;
@@ -487,6 +493,11 @@ int smhip_filter_config_valid_ex(const smhip_filter_desc_ex* f);
 /* smhip_filter_chain_f32 for extended descriptors; smhip_filter_get_output / _output_to_source read its result */
 smhip_status smhip_filter_chain_ex_f32(smhip_handle h, const float* points, int stride_floats, int n,
                                        const smhip_filter_desc_ex* chain, int n_filters, int* n_out);
+/* parity-test hook: what the last StatisticRemoval of the last filter chain computed.  distance (n floats, or NULL): the mean
+ * distance to the point_num_meank nearest neighbours per row, in the row order that filter saw (n = its input size; 0 for a
+ * non-finite row); stats (or NULL): sum and sum of squares of the finite rows' distances, their number V, and the threshold
+ * mean + std_mul * stddev.  SMHIP_ERR_NOT_READY when no such filter ran in the last chain or it kept every row for V <= k. */
+smhip_status smhip_filter_statistic_last(smhip_handle h, float* distance, int n, double stats[4]);
 
 /* ---- Submap::InsertFrame for a full submap (builder/submap.cc:98-158) ---------------------------
  * Frame k = n[k] rows of `stride_floats` floats at rows[k] (4: x y z intensity, factor = i / n[k] of its own frame as the

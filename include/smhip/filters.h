@@ -6,11 +6,12 @@
 //   /root/reference/pre_processors/filter_interface.h:38-64      filter::Interface (InitFromXmlText, ConfigsValid, Filter)
 //   /root/reference/pre_processors/filter_{range,axis_range,bounding_box,random_sample,voxel_grid}.{h,cc}
 //   (the reference's) pre_processors/filter_{ground_removal,ground_removal2,range_image}.{h,cc}   (Filter only)
+//   (the reference's) pre_processors/filter_statistic_removal.{h,cc}   (name and parameters; its Filter is a stub there)
 //   /root/reference/pre_processors/filter_factory.{h,cc}         Factory: the <filters> chain
 // free of glog / pugixml / pcl.  Every filter runs on the GPU through smhip_filter_chain_f32 (GroundRemoval, GroundRemoval2 and
 // RangeImage through smhip_filter_chain_ex_f32); a Factory runs its whole chain in one call and can hand the result to a matcher
 // slot without a host round trip (FilterToSource).  The default Factory registers the first five only; Factory(true) or
-// EnableGroundFilters() adds the other three.
+// EnableGroundFilters() adds GroundRemoval, GroundRemoval2 and RangeImage, EnableStatisticRemoval() adds StatisticRemoval.
 // Header-only; link with -lsmhip.
 #ifndef SMHIP_FILTERS_H_
 #define SMHIP_FILTERS_H_
@@ -237,6 +238,17 @@ class RangeImage : public ExInterface {
   std::string GetName() const override { return "RangeImage"; }
 };
 
+// filter_statistic_removal.cc:31-37 (the two parameters and their defaults).  The reference's Filter (:44-59) is a commented-out
+// pcl::StatisticalOutlierRemoval call and leaves its output cloud empty; this one runs that algorithm on the device as
+// DESIGN.md §6 ("StatisticRemoval") defines it: rows whose mean distance to their point_num_meank nearest neighbours exceeds
+// mean + std_mul * stddev are dropped.
+class StatisticRemoval : public ExInterface {
+ public:
+  StatisticRemoval() : ExInterface(SMHIP_FILTER_STATISTIC_REMOVAL, {{"std_mul", 0}, {"point_num_meank", -1}}) {}
+  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<StatisticRemoval>(); }
+  std::string GetName() const override { return "StatisticRemoval"; }
+};
+
 // filter_factory.cc:47-106
 class Factory : public Interface {
  public:
@@ -256,7 +268,17 @@ class Factory : public Interface {
     supported_filters_.emplace("GroundRemoval2", std::make_shared<GroundRemoval2>());
     supported_filters_.emplace("RangeImage", std::make_shared<RangeImage>());
   }
-  std::shared_ptr<Interface> CreateNewInstance() override { return std::make_shared<Factory>(ground_filters_); }
+  // opt-in: registers StatisticRemoval (filter_factory.cc:49, 117-118 register it too, but around a Filter() that writes no
+  // output, so a chain holding it ends empty there; here it filters)
+  void EnableStatisticRemoval() {
+    statistic_removal_ = true;
+    supported_filters_.emplace("StatisticRemoval", std::make_shared<StatisticRemoval>());
+  }
+  std::shared_ptr<Interface> CreateNewInstance() override {
+    auto f = std::make_shared<Factory>(ground_filters_);
+    if (statistic_removal_) f->EnableStatisticRemoval();
+    return f;
+  }
   std::string GetName() const override { return ""; }
   bool ConfigsValid() const override { return true; }
 
@@ -331,6 +353,7 @@ class Factory : public Interface {
   std::vector<std::shared_ptr<Interface>> filters_;
   std::map<std::string, std::shared_ptr<Interface>> supported_filters_;
   bool ground_filters_ = false;
+  bool statistic_removal_ = false;
 };
 
 }  // namespace filter

@@ -163,6 +163,7 @@ SIGNATURES = {
     "smhip_filter_config_valid_ex": (ctypes.c_int, [ctypes.POINTER(FilterDescEx)]),
     "smhip_filter_chain_ex_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FilterDescEx),
                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_filter_statistic_last": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, c_double_p]),
     "smhip_submap_build_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(c_float_p), ctypes.c_int, c_int32_p, c_double_p,
                                               ctypes.c_float, ctypes.POINTER(ctypes.c_int)]),
     "smhip_filter_output_to_target": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),

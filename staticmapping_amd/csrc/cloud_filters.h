@@ -29,6 +29,13 @@ const float* filt_factors(const FilterWorkspace* w);
 const int32_t* filt_source_index(const FilterWorkspace* w);  // row of the ORIGINAL input each point came from (-1 after VoxelGrid)
 int filt_count(const FilterWorkspace* w);
 bool filt_has_index(const FilterWorkspace* w);
+// a warning the last filt_run_chain left ("" = none): a condition that is no error, for the handle's last-error text
+const char* filt_note(const FilterWorkspace* w);
+// the last StatisticRemoval of the last filt_run_chain: the rows it saw (-1: none ran, -2: it kept every row because no more than
+// point_num_meank of them were finite), and on the device its distance[] in that row order and sum, sq_sum, V, threshold
+int filt_statistic_rows(const FilterWorkspace* w);
+const float* filt_statistic_distance(const FilterWorkspace* w);
+const double* filt_statistic_stats(const FilterWorkspace* w);
 
 // MotionCompensation (builder/map_builder.cc:232-257) of the current cloud, motion_comp.hip.  What InterpolateTransform
 // (common/math.h:199-211) derives from delta alone, once per call: q_b = Eigen's Quaternion(Matrix3) of delta's rotation block

@@ -9,6 +9,8 @@
 //   filter_ground_removal.cc        GroundRemoval       drop small voxels and flat low ones    } kernels in ground_filters.hip;
 //   filter_ground_removal2.cc       GroundRemoval2      drop points near fitted ground lines   } what is and is not pinned:
 //   filter_range_image.cc           RangeImage          keep the first point of every pixel    } DESIGN.md §6, "Pre-filters"
+//   filter_statistic_removal.cc     StatisticRemoval    drop rows far from their k nearest neighbours (kernels in
+//                                                       statistic_removal.hip; the definition: DESIGN.md §6, "StatisticRemoval")
 //   filter_factory.cc:83-106       Factory::Filter     the filters of <filters> applied in order
 //   builder/map_builder.cc:232-257  MotionCompensation  the front end's de-skew of the filtered cloud (kernel in motion_comp.hip)
 // They run on every scan right before the registrator (builder/data/data_collector.h, config/lidar_only_kitti.xml:18-41).
@@ -20,6 +22,7 @@
 // emits voxel by voxel in the reference, in std::map order of the voxel index; GroundRemoval2 and RangeImage keep input order).
 // Every chain runs on smhip_filter_desc_ex; smhip_filter_chain_f32 widens its descriptors first.
 #include <cstring>
+#include <string>
 #include <string.h>
 
 #include <hip/hip_runtime.h>
@@ -134,6 +137,7 @@ __global__ void filt_voxel_average(const float4* pts, const int32_t* idx, const 
 
 #include "ground_filters.hip"
 #include "motion_comp.hip"
+#include "statistic_removal.hip"
 
 __global__ void filt_init(const float4* in, int n, int stride5, const float* fac_in, float4* pts, float* fac, int32_t* src) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,6 +173,13 @@ struct FilterWorkspace {
   int seg_cap = 0;
   int pix_cap = 0;                                         // RangeImage: V * H pixels
   int32_t* pix = nullptr;
+  // StatisticRemoval: allocated on first use for the workspace's capacity
+  float4* sr_pts = nullptr;                                // the finite rows sorted along the search axis
+  float* sr_dist = nullptr;                                // distance[] of the last StatisticRemoval, in its input row order
+  double *sr_csum = nullptr, *sr_csq = nullptr, *sr_stat = nullptr;   // sums per 64 rows; sum, sq_sum, V, threshold
+  uint32_t* sr_meta = nullptr;                             // bounding box of the finite rows and their number
+  int sr_rows = -1;                                        // rows that filter saw in the last chain; -1 none ran, -2 it passed the cloud through
+  std::string note;                                        // a warning the last chain leaves for the handle's last-error text
 };
 
 FilterWorkspace* filt_create(int max_points) {
@@ -205,6 +216,8 @@ void filt_destroy(FilterWorkspace* w) {
   (void)hipFree(w->tmp);
   (void)hipFree(w->gd); (void)hipFree(w->gz); (void)hipFree(w->runmin); (void)hipFree(w->vmin); (void)hipFree(w->vmax);
   (void)hipFree(w->gend); (void)hipFree(w->gfirst); (void)hipFree(w->nlines); (void)hipFree(w->lines); (void)hipFree(w->pix);
+  (void)hipFree(w->sr_pts); (void)hipFree(w->sr_dist); (void)hipFree(w->sr_csum); (void)hipFree(w->sr_csq); (void)hipFree(w->sr_stat);
+  (void)hipFree(w->sr_meta);
   if (w->host_pinned) (void)hipHostFree(w->host_pinned);
   delete w;
 }
@@ -354,11 +367,63 @@ static hipError_t voxel_tail(FilterWorkspace* w, hipStream_t st) {
   return hipSuccess;
 }
 
+static hipError_t ensure_statistic(FilterWorkspace* w) {
+  if (w->sr_meta) return hipSuccess;
+  const size_t N = (size_t)std::max(w->cap, 1), C = N / 64 + 1;
+  FCHK(hipMalloc((void**)&w->sr_pts, N * sizeof(float4))); FCHK(hipMalloc((void**)&w->sr_dist, N * 4));
+  FCHK(hipMalloc((void**)&w->sr_csum, C * 8)); FCHK(hipMalloc((void**)&w->sr_csq, C * 8)); FCHK(hipMalloc((void**)&w->sr_stat, 4 * 8));
+  return hipMalloc((void**)&w->sr_meta, 8 * 4);
+}
+
+static double sr_unordered(uint32_t o) {                 // the float behind an sr_ordered word
+  const uint32_t u = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return (double)f;
+}
+
+// StatisticRemoval on the current cloud: bounding box and V -> sort along the longest side -> k-NN mean distances -> the two
+// sums and the threshold -> flags -> compact.  V <= k keeps every row and leaves a warning.
+static hipError_t run_statistic_removal(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex& f) {
+  const int n = w->n, gp = (n + 255) / 256, c = w->cur, k = f.i[0];
+  FCHK(ensure_statistic(w));
+  FCHK(hipMemsetD32Async((hipDeviceptr_t)w->sr_meta, -1, 3, st));
+  FCHK(hipMemsetAsync(w->sr_meta + 3, 0, 4 * 4, st));
+  hipLaunchKernelGGL(sr_extent, dim3(std::min(gp, 64)), dim3(256), 0, st, w->pts[c], n, w->sr_meta);
+  FCHK(hipMemcpyAsync(w->host_pinned + 4, w->sr_meta, 7 * 4, hipMemcpyDeviceToHost, st));
+  FCHK(hipStreamSynchronize(st));
+  const uint32_t* meta = reinterpret_cast<const uint32_t*>(w->host_pinned + 4);
+  const int V = (int)meta[6];
+  if (V <= k) {
+    w->sr_rows = -2;
+    w->note = "warning: StatisticRemoval kept every row: " + std::to_string(V) + " finite row(s) for point_num_meank = " + std::to_string(k);
+    return hipSuccess;
+  }
+  double ext[3];
+  for (int a = 0; a < 3; ++a) ext[a] = sr_unordered(meta[3 + a]) - sr_unordered(meta[a]);
+  const int axis = (ext[0] >= ext[1] && ext[0] >= ext[2]) ? 0 : (ext[1] >= ext[2] ? 1 : 2);
+  hipLaunchKernelGGL(sr_keys, dim3(gp), dim3(256), 0, st, w->pts[c], n, axis, w->keys[0], w->idx[0]);
+  size_t bytes = w->tmp_bytes;
+  FCHK(rocprim::radix_sort_pairs(w->tmp, bytes, w->keys[0], w->keys[1], w->idx[0], w->idx[1], (unsigned)n, 0, 32, st));
+  hipLaunchKernelGGL(sr_gather, dim3((V + 255) / 256), dim3(256), 0, st, w->pts[c], w->idx[1], V, axis, w->sr_pts);
+  const dim3 gk((n + kSrThreads - 1) / kSrThreads), bk(kSrThreads);
+  if (k <= 16) hipLaunchKernelGGL(sr_knn<16>, gk, bk, 0, st, w->sr_pts, w->idx[1], V, n, k, w->sr_dist);
+  else if (k <= 32) hipLaunchKernelGGL(sr_knn<32>, gk, bk, 0, st, w->sr_pts, w->idx[1], V, n, k, w->sr_dist);
+  else hipLaunchKernelGGL(sr_knn<kSrMaxK>, gk, bk, 0, st, w->sr_pts, w->idx[1], V, n, k, w->sr_dist);
+  hipLaunchKernelGGL(sr_chunk_sums, dim3(gp), dim3(256), 0, st, w->sr_dist, n, w->sr_csum, w->sr_csq);
+  hipLaunchKernelGGL(sr_stats, dim3(1), dim3(64), 0, st, w->sr_csum, w->sr_csq, (n + 63) / 64, V, f.p[0], w->sr_stat);
+  hipLaunchKernelGGL(sr_flags, dim3(gp), dim3(256), 0, st, w->pts[c], w->sr_dist, n, w->sr_stat, w->flag);
+  w->sr_rows = n;
+  return compact(w, st);
+}
+
 static bool is_predicate(int t) { return t == SMHIP_FILTER_RANGE || t == SMHIP_FILTER_AXIS_RANGE || t == SMHIP_FILTER_BOUNDING_BOX_REMOVAL; }
 
 hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter_desc_ex* chain, int nf, int* n_out) {
   if (!w || (nf > 0 && !chain)) return hipErrorInvalidValue;
   int k = 0;
+  w->sr_rows = -1;
+  w->note.clear();
   while (k < nf && w->n > 0) {
     const smhip_filter_desc_ex& f = chain[k];
     const int n = w->n, gp = (n + 255) / 256;
@@ -392,6 +457,9 @@ hipError_t filt_run_chain(FilterWorkspace* w, hipStream_t st, const smhip_filter
     } else if (f.type == SMHIP_FILTER_RANGE_IMAGE) {
       ++k;
       FCHK(run_range_image(w, st, f));
+    } else if (f.type == SMHIP_FILTER_STATISTIC_REMOVAL) {
+      ++k;
+      FCHK(run_statistic_removal(w, st, f));
     } else {
       return hipErrorInvalidValue;
     }
@@ -433,5 +501,9 @@ const float* filt_factors(const FilterWorkspace* w) { return w->fac[w->cur]; }
 const int32_t* filt_source_index(const FilterWorkspace* w) { return w->src[w->cur]; }
 int filt_count(const FilterWorkspace* w) { return w->n; }
 bool filt_has_index(const FilterWorkspace* w) { return w->has_index; }
+const char* filt_note(const FilterWorkspace* w) { return w->note.c_str(); }
+int filt_statistic_rows(const FilterWorkspace* w) { return w->sr_rows; }
+const float* filt_statistic_distance(const FilterWorkspace* w) { return w->sr_dist; }
+const double* filt_statistic_stats(const FilterWorkspace* w) { return w->sr_stat; }
 
 }  // namespace smhip

@@ -1,7 +1,8 @@
 // smhip_filter_api.hip -- C ABI of the device pre-filters: a translation unit of its own that launches no kernel (the kernels
 // are in cloud_filters.hip, behind cloud_filters.h); the handle and check_slot / prep_ensure come from smhip_context.h.
 // Mirrors pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, GroundRemoval, GroundRemoval2,
-// RangeImage, Factory} (the reference's pre_processors/filter_*.cc): constructor defaults, ConfigsValid() and Filter().
+// RangeImage, StatisticRemoval, Factory} (the reference's pre_processors/filter_*.cc): constructor defaults, ConfigsValid() and
+// Filter().
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -81,6 +82,10 @@ static const char* config_problem_ex(const smhip_filter_desc_ex* f) {
       if (f->i[0] <= 0 || f->i[1] <= 0) return "RangeImage: vertical_line_num and horizontal_line_num must be positive";
       if ((long)f->i[0] * f->i[1] > kMaxFilterCells) return "RangeImage: image larger than the device limit of 2^22 pixels";
       return nullptr;
+    case SMHIP_FILTER_STATISTIC_REMOVAL:
+      if (f->i[0] < 1 || f->i[0] > 64) return "StatisticRemoval: point_num_meank must be between 1 and the device limit of 64";
+      if (!std::isfinite(f->p[0])) return "StatisticRemoval: std_mul must be finite";
+      return nullptr;
   }
   smhip_filter_desc d;
   std::memset(&d, 0, sizeof(d));
@@ -109,6 +114,7 @@ static smhip_status filter_chain(smhip_handle h, const float* points, int stride
   if (e != hipSuccess) { h->err = std::string("filter chain: ") + hipGetErrorString(e); return e == hipErrorInvalidValue ? SMHIP_ERR_INVALID_ARGUMENT : SMHIP_ERR_HIP; }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (n_out) *n_out = filt_count(h->filt);
+  if (*filt_note(h->filt)) h->err = filt_note(h->filt);      // a warning: the call succeeded
   return SMHIP_OK;
 }
 
@@ -138,6 +144,8 @@ void smhip_filter_default_ex(int type, smhip_filter_desc_ex* f) {
       f->i[0] = 200; f->i[1] = 180; f->i[2] = 4; break;
     case SMHIP_FILTER_RANGE_IMAGE:                                                            // filter_range_image.cc:28-52
       f->p[0] = 30.f; f->p[1] = -15.f; f->i[0] = 40; f->i[1] = 1800; break;
+    case SMHIP_FILTER_STATISTIC_REMOVAL:                                                      // filter_statistic_removal.cc:31-37
+      f->p[0] = 1.0f; f->i[0] = 30; break;
     default: {
       smhip_filter_desc d;
       smhip_filter_default(type, &d);
@@ -175,6 +183,23 @@ smhip_status smhip_filter_get_output(smhip_handle h, float* points5, int32_t* so
       points5[5 * (size_t)i] = p[i].x; points5[5 * (size_t)i + 1] = p[i].y; points5[5 * (size_t)i + 2] = p[i].z;
       points5[5 * (size_t)i + 3] = p[i].w; points5[5 * (size_t)i + 4] = f[i];
     }
+  return SMHIP_OK;
+}
+
+// parity hook: what the last StatisticRemoval of the last chain computed
+smhip_status smhip_filter_statistic_last(smhip_handle h, float* distance, int n, double stats[4]) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  const int rows = h->filt ? filt_statistic_rows(h->filt) : -1;
+  if (rows < 0) {
+    h->err = rows == -2 ? "the last StatisticRemoval kept every row without computing distances (no more finite rows than point_num_meank)"
+                        : "no StatisticRemoval ran in the last filter chain";
+    return SMHIP_ERR_NOT_READY;
+  }
+  if (n != rows) { h->err = "n must equal the rows that filter saw (" + std::to_string(rows) + ")"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (distance) HIPCHK(h, hipMemcpyAsync(distance, filt_statistic_distance(h->filt), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (stats) HIPCHK(h, hipMemcpyAsync(stats, filt_statistic_stats(h->filt), sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return SMHIP_OK;
 }
 

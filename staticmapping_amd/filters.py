@@ -1,7 +1,8 @@
 """ctypes view of the device pre-filters (include/smhip.h, `smhip_filter_*`): the Python mirror of
 pre_processers::filter::{Range, AxisRange, BoundingBoxRemoval, RandomSampler, VoxelGrid, GroundRemoval, GroundRemoval2,
-RangeImage, Factory} (the reference's pre_processors/filter_*.cc).  Filters are descriptors set by the reference's parameter
-names: `FilterDesc` for the first five, `FilterDescEx` for GroundRemoval, GroundRemoval2 and RangeImage."""
+RangeImage, StatisticRemoval, Factory} (the reference's pre_processors/filter_*.cc).  Filters are descriptors set by the
+reference's parameter names: `FilterDesc` for the first five, `FilterDescEx` for GroundRemoval, GroundRemoval2, RangeImage and
+StatisticRemoval (k-NN outlier removal; the reference ships only its parameters, the definition is in DESIGN.md §6)."""
 from __future__ import annotations
 
 import ctypes
@@ -13,9 +14,11 @@ from . import _capi
 
 RANGE, AXIS_RANGE, RANDOM_SAMPLER, VOXEL_GRID, BOUNDING_BOX_REMOVAL = 1, 2, 3, 4, 5
 GROUND_REMOVAL, GROUND_REMOVAL2, RANGE_IMAGE = 6, 7, 8
+STATISTIC_REMOVAL = 9
 NAMES = {"Range": RANGE, "AxisRange": AXIS_RANGE, "RandomSampler": RANDOM_SAMPLER, "VoxelGrid": VOXEL_GRID,
          "BoundingBoxRemoval": BOUNDING_BOX_REMOVAL}
 GROUND_NAMES = {"GroundRemoval": GROUND_REMOVAL, "GroundRemoval2": GROUND_REMOVAL2, "RangeImage": RANGE_IMAGE}
+STATISTIC_NAMES = {"StatisticRemoval": STATISTIC_REMOVAL}
 _PARAMS = {RANGE: ("min_range", "max_range"), AXIS_RANGE: ("min", "max"), RANDOM_SAMPLER: ("sampling_rate",),
            VOXEL_GRID: ("voxel_size",), BOUNDING_BOX_REMOVAL: ("min_x", "min_y", "min_z", "max_x", "max_y", "max_z")}
 # the FilterDescEx slots of the new filters (include/smhip.h): name -> ("p" | "i", index)
@@ -26,13 +29,14 @@ _PARAMS_EX = {
                       "max_b": ("p", 8), "max_dist_to_line": ("p", 9), "search_angle": ("p", 10), "bin_num": ("i", 0),
                       "segment_num": ("i", 1), "thread_num": ("i", 2)},
     RANGE_IMAGE: {"top_angle": ("p", 0), "btm_angle": ("p", 1), "offset_x": ("p", 2), "offset_y": ("p", 3), "offset_z": ("p", 4),
-                  "vertical_line_num": ("i", 0), "horizontal_line_num": ("i", 1)}}
+                  "vertical_line_num": ("i", 0), "horizontal_line_num": ("i", 1)},
+    STATISTIC_REMOVAL: {"std_mul": ("p", 0), "point_num_meank": ("i", 0)}}       # filter_statistic_removal.cc:33-36
 
 
 def make_filter(name_or_type, **params):
     """A filter with its constructor defaults, then `params` (reference names; plus `axis_index`, `seed`).
-    GroundRemoval, GroundRemoval2 and RangeImage give a FilterDescEx, the others a FilterDesc."""
-    t = {**NAMES, **GROUND_NAMES}[name_or_type] if isinstance(name_or_type, str) else int(name_or_type)
+    GroundRemoval, GroundRemoval2, RangeImage and StatisticRemoval give a FilterDescEx, the others a FilterDesc."""
+    t = {**NAMES, **GROUND_NAMES, **STATISTIC_NAMES}[name_or_type] if isinstance(name_or_type, str) else int(name_or_type)
     if t in _PARAMS_EX:
         d = _capi.FilterDescEx()
         _capi.load_library().smhip_filter_default_ex(t, ctypes.byref(d))
@@ -76,13 +80,17 @@ def widen(d) -> _capi.FilterDescEx:
     return e
 
 
-def chain_from_xml(text: str, seed: int = 0, ground_filters: bool = False) -> list:
+def chain_from_xml(text: str, seed: int = 0, ground_filters: bool = False, statistic_removal: bool = False) -> list:
     """The <filters> element of the reference's configs (filter_factory.cc:47-81): unsupported names are skipped.
     ground_filters=True also takes GroundRemoval, GroundRemoval2 and RangeImage, and skips <!-- ... --> comments as pugixml
-    does (the default keeps the historical parse, which reads filters inside comments too)."""
+    does (the default keeps the historical parse, which reads filters inside comments too).
+    statistic_removal=True also takes StatisticRemoval: opt-in because the reference's own Filter() for that name is a stub that
+    leaves its output cloud empty, so a port that lists it gets a different chain here than there."""
     if ground_filters:
         text = re.sub(r"<!--.*?-->", "", text, flags=re.S)
-    names = {**NAMES, **GROUND_NAMES} if ground_filters else NAMES
+    names = {**NAMES, **GROUND_NAMES} if ground_filters else dict(NAMES)
+    if statistic_removal:
+        names.update(STATISTIC_NAMES)
     out = []
     for m in re.finditer(r'<filter\s+name="([^"]+)"\s*(?:/>|>(.*?)</filter>)', text, flags=re.S):
         name, body = m.group(1), m.group(2) or ""
@@ -119,6 +127,17 @@ def run_chain(matcher, points, chain):
     matcher._check(matcher._lib.smhip_filter_get_output(matcher._h, out.ctypes.data_as(_capi.c_float_p),
                                                         src.ctypes.data_as(_capi.c_int32_p), n_out.value))
     return out, src
+
+
+def statistic_last(matcher, n: int):
+    """What the last StatisticRemoval of the last chain computed (smhip_filter_statistic_last).  n = the rows that filter saw
+    (the chain's input size when it is the first filter).  Returns (distance [n] float32 in that row order, 0 for a non-finite
+    row; {"sum", "sq_sum", "V", "threshold"})."""
+    dist = np.zeros(n, np.float32)
+    stats = np.zeros(4, np.float64)
+    matcher._check(matcher._lib.smhip_filter_statistic_last(matcher._h, dist.ctypes.data_as(_capi.c_float_p), n,
+                                                           stats.ctypes.data_as(_capi.c_double_p)))
+    return dist, {"sum": float(stats[0]), "sq_sum": float(stats[1]), "V": int(stats[2]), "threshold": float(stats[3])}
 
 
 def run_chain_resident(matcher, points, chain) -> int:

@@ -1,5 +1,6 @@
-"""Device time of GroundRemoval, GroundRemoval2 and RangeImage on one 120 000-point scan of the seed-5 drive, beside the CPU
-restatement's (tests/ground_filters_ref.py).
+"""Device time of GroundRemoval, GroundRemoval2, RangeImage and StatisticRemoval (defaults and point_num_meank = 10) on one
+120 000-point scan of the seed-5 drive, beside the CPU restatement's (tests/ground_filters_ref.py; for StatisticRemoval, with
+--statistic-cpu, tests/statistic_removal_ref.py -- brute force, about a minute -- and a scipy k-d tree query).
 
 Each call of smhip_filter_chain_ex_f32 stages the rows on the host, uploads them and runs the chain; the empty chain measures
 the staging and upload alone, and `filter_ms` is a chain's median minus the empty chain's median.  Medians over --repeats calls
@@ -22,6 +23,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu-repeats", type=int, default=1)
+    ap.add_argument("--statistic-cpu", action="store_true", help="also time StatisticRemoval's restatement and scipy's cKDTree")
+    ap.add_argument("--cpu-only", action="store_true", help="skip the device: the CPU times alone (no GPU needed)")
+    ap.add_argument("--only-statistic", action="store_true", help="the empty chain and the StatisticRemoval cases alone")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -51,10 +55,14 @@ def main():
         "kitti_inner_chain": [df.make_filter("GroundRemoval2", **kitti_inner), df.make_filter("RangeImage", **image60)],
         "kitti_pre_chain": [df.make_filter("Range", min_range=5.0), df.make_filter("AxisRange", min=-2.0),
                             df.make_filter("GroundRemoval2", **kitti_pre), df.make_filter("RandomSampler", sampling_rate=0.5, seed=1)],
+        "StatisticRemoval_defaults": [df.make_filter("StatisticRemoval")],
+        "StatisticRemoval_k10": [df.make_filter("StatisticRemoval", point_num_meank=10)],
     }
-    m = sm.IcpFastHip(pair_slots=1, max_source_points=131072, max_target_points=131072)
+    if a.only_statistic:
+        cases = {k: v for k, v in cases.items() if k == "empty_chain" or k.startswith("StatisticRemoval")}
+    m = None if a.cpu_only else sm.IcpFastHip(pair_slots=1, max_source_points=131072, max_target_points=131072)
     res = {"n_points": len(scan), "repeats": a.repeats, "device_ms": {}, "filter_ms": {}, "kept": {}, "cpu_ms": {}}
-    for name, chain in cases.items():
+    for name, chain in ({} if a.cpu_only else cases).items():
         # widen even the empty chain so every case goes through smhip_filter_chain_ex_f32
         chain_ex = [df.widen(d) for d in chain] if chain else [df.make_filter("Range")]
         for _ in range(a.warmup):
@@ -66,21 +74,29 @@ def main():
             t.append((time.perf_counter() - t0) * 1e3)
         res["device_ms"][name] = float(np.median(t))
         res["kept"][name] = int(k)
-    base = res["device_ms"]["empty_chain"]
+    base = res["device_ms"].get("empty_chain")
     for name in cases:
-        if name != "empty_chain":
+        if name != "empty_chain" and not a.cpu_only:
             res["filter_ms"][name] = round(res["device_ms"][name] - base, 4)
     rows5 = of.with_factor(scan)
-    for name, fn in (("GroundRemoval", lambda: gf.ground_removal(rows5)),
-                     ("GroundRemoval2_kitti_pre", lambda: gf.ground_removal2(rows5, **kitti_pre)),
-                     ("RangeImage_40x1800", lambda: gf.range_image(rows5))):
+    cpu = [] if a.only_statistic else [("GroundRemoval", lambda: gf.ground_removal(rows5)),
+                                       ("GroundRemoval2_kitti_pre", lambda: gf.ground_removal2(rows5, **kitti_pre)),
+                                       ("RangeImage_40x1800", lambda: gf.range_image(rows5))]
+    if a.statistic_cpu:
+        import statistic_removal_ref as sr
+        from scipy.spatial import cKDTree
+        xyz = rows5[:, :3].astype(np.float64)
+        cpu += [("StatisticRemoval_defaults", lambda: sr.statistic_removal(rows5)),
+                ("StatisticRemoval_defaults_scipy_ckdtree_query", lambda: cKDTree(xyz).query(xyz, k=31))]
+    for name, fn in cpu:
         t = []
         for _ in range(a.cpu_repeats):
             t0 = time.perf_counter()
             fn()
             t.append((time.perf_counter() - t0) * 1e3)
-        res["cpu_ms"][name + "_restatement"] = float(np.median(t))
-    m.close()
+        res["cpu_ms"][name + ("" if "scipy" in name else "_restatement")] = float(np.median(t))
+    if m is not None:
+        m.close()
     line = json.dumps(res)
     print(line)
     if a.out:
