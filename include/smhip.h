@@ -281,6 +281,15 @@ smhip_status smhip_get_cloud_sizes(smhip_handle h, int slot, int* n_source, int*
  * the trimmed-distance filter KEPT is exact; with use_ball = 1 and exact_matches = 0 a rejected match
  * may carry a certified lower bound (> the quantile) and the best target seen so far instead. */
 smhip_status smhip_icp_get_matches(smhip_handle h, int slot, int32_t* ids, float* d2, int n);
+/* Debugging / tests: the search grid resident in `slot` (the structure the last Align or find_closests on it built or kept), copied
+ * to host buffers after a synchronisation.  mu[3]: the target mean; cell_origin[4]: the cell edge h, then the grid's origin x y z
+ * (centred coordinates); dims[7]: nx, ny, nz, wx (32-cell words per row), nw (words), nocc (occupied cells), nt (points).
+ * words: nw pairs {occupancy bits, exclusive rank of the word's first cell}; cstart: nocc + 1 run starts of the cell-sorted target;
+ * tq / tn: nt rows of 4 floats -- the centred point with the caller's index as the bits of w, and its normal with w = 0 -- cells in
+ * linear order, a cell's points by caller index.  Any of the four may be NULL; a capacity (in words, entries, rows) below what
+ * the structure holds -- SMHIP_ERR_CAPACITY with the geometry already written; no grid in the slot -- SMHIP_ERR_NOT_READY. */
+smhip_status smhip_icp_debug_get_grid(smhip_handle h, int slot, double mu[3], float cell_origin[4], int32_t dims[7],
+                                      uint32_t* words, int words_cap, uint32_t* cstart, int cstart_cap, float* tq, float* tn, int points_cap);
 /* One FindClosests pass only: transform the slot's source by T (column-major 4x4, applied AFTER
  * centring exactly as Align does) and return ids / d2 without running ICP. */
 smhip_status smhip_icp_find_closests(smhip_handle h, int slot, const double T[16], int32_t* ids, float* d2, int n);

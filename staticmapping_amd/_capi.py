@@ -129,6 +129,9 @@ SIGNATURES = {
     "smhip_get_target_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, ctypes.c_int]),
     "smhip_get_source_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int]),
     "smhip_icp_get_matches": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int32_p, c_float_p, ctypes.c_int]),
+    "smhip_icp_debug_get_grid": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_float_p, c_int32_p,
+                                                ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+                                                c_float_p, c_float_p, ctypes.c_int]),
     "smhip_icp_find_closests": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_int32_p, c_float_p,
                                                ctypes.c_int]),
     "smhip_ndt_default_options": (None, [ctypes.POINTER(NdtOptions)]),

@@ -4,6 +4,9 @@
 //   tgt_reduce / grid_setup / grid_mark / grid_rank / grid_count / grid_cscan / grid_scatter_idx / grid_place
 //        target centring (icp_fast.cc:457-463) + the search structure that replaces the
 //        libnabo kd-tree rebuilt on every Align (icp_fast.cc:464-467)
+//   tgt_reduce / grid_sort_build (grid_sort_build.hip)
+//        the same structure, byte for byte, by one in-LDS stable sort per pair: the form the plan chooses for the
+//        sort_cells = 1 grid without row bitmap over targets of at most 32 768 points (plan::sorted_grid_build)
 //   nn_grid, nn_brute   [K1]  ApplyTransform + FindClosests      (icp_fast.cc:486-493, 169-180)
 //   accumulate          [K2/K3] GetDistsQuantile bin + ErrorElements + point-to-plane sums
 //                                                               (icp_fast.cc:65-90, 100-166, 256-303)
@@ -144,9 +147,9 @@ __global__ __launch_bounds__(256) void reset_scratch_light(IcpDev b, int first, 
   for (size_t k = tid; k < sizeof(PairState) / 4 * kOnePairs; k += nth) reinterpret_cast<uint32_t*>(b.one_ctr)[k] = 0;
 }
 
-__global__ void grid_setup(IcpDev b, int npairs) {
-  const int pair = b.pair_base + blockIdx.x * blockDim.x + threadIdx.x;
-  if (pair >= b.pair_base + npairs) return;
+// grid_setup's work for one pair, on one lane: the fold of tgt_reduce's rows in their fixed order, the geometry, the pose
+// chain and the loop state.  grid_setup runs it a thread per pair, grid_sort_build (grid_sort_build.hip) on its first lane.
+__device__ __forceinline__ void grid_setup_pair(const IcpDev& b, int pair) {
   PairState* st = &b.state[pair];
   const double* part = b.tpart + (size_t)pair * kTgtReduceBlocks * 16;
   double s[3] = {0, 0, 0};
@@ -221,6 +224,11 @@ __global__ void grid_setup(IcpDev b, int npairs) {
   st->rcap2 = b.ball_radius * b.ball_radius;
   st->kept = 0; st->limit_key = 0; st->score = 0; st->score_mismatch = 0; st->nocc = 0;
   st->band_lo = 0; st->band_hi = -1; st->spec_ok = 0; st->spec_hits = 0;
+}
+__global__ void grid_setup(IcpDev b, int npairs) {
+  const int pair = b.pair_base + blockIdx.x * blockDim.x + threadIdx.x;
+  if (pair >= b.pair_base + npairs) return;
+  grid_setup_pair(b, pair);
 }
 
 __device__ __forceinline__ float3 centre_point(const float4 p, const double* mu) {

@@ -37,6 +37,23 @@ constexpr int kNaboBucket = 8;           // kKdBucket
 constexpr int kNaboShallowLevels = 12;   // 12 stack levels (40 KiB of LDS) cover the target
 constexpr int kShadowMaxTarget = 0x7fff; // the 4-byte shadow of (bound, match) holds 15 bits of match
 
+// ---- the grid build ------------------------------------------------------------------------------------------------------
+// Which of the two forms builds the search grid of a launch's targets: true = grid_sort_build (grid_sort_build.hip: one in-LDS stable
+// sort per pair, a launch behind tgt_reduce), false = the mark / rank / count / cscan / scatter / place kernels over the zeroed bitmap.
+// Both make the same bytes; the sorted form exists for the sort_cells = 1 grid without the row bitmap that the ball search of IcpFast
+// walks, and holds a target in one workgroup's registers and LDS: at most 1 024 threads x 32 points, the bound of the shadow word's
+// 15-bit match as well.  Everything else -- the 500 k - 2 M-point NDT / GICP targets, sort_cells = 0, the ring-search contexts (row
+// bitmap), libnabo's tree -- keeps the kernels it had.  enabled: SMHIP_GRID_BUILD (0 = the old kernels for every launch).
+constexpr int kSortBuildMaxTarget = 32768;
+// pairs a launch needs for the sorted form.  One workgroup builds a pair whatever the launch holds, where grid_rank cuts a single
+// pair's words into 16 segments.  NOT MEASURED yet (profiles/README.md): reasoned from the launches -- two instead of eight on a
+// stream where a near-empty launch costs ~5 us, the one workgroup's 2 MiB of `words` about 15 us at a CU's store rate --, so one pair
+// takes the sorted form too; tools/small_batch_probe.py of both trees is what moves this number.
+constexpr int kSortBuildMinPairs = 1;
+inline bool sorted_grid_build(int enabled, int nn_mode, int sort_cells, int have_rowbits, int npairs, int nt_max) {
+  return enabled && nn_mode == SMHIP_NN_GRID && sort_cells && !have_rowbits && npairs >= kSortBuildMinPairs && nt_max <= kSortBuildMaxTarget;
+}
+
 // ---- capacities ----------------------------------------------------------------------------------------------------------
 // the strides smhip_create derives from max_source_points
 struct Capacities {

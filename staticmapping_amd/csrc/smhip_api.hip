@@ -7,11 +7,12 @@
 // the device; the host only enqueues launches and, when early exit is on, polls one word
 // every `check_every` iterations.
 //
-// This file is the ICP translation unit of libsmhip.so: it defines the kernels of icp_kernels.hip and of the two fragments
-// that reuse their bodies (icp_one.hip, nabo_kernels.hip), in that order, and the entry points of IcpFast and of the clouds
+// This file is the ICP translation unit of libsmhip.so: it defines the kernels of icp_kernels.hip and of the three fragments
+// that reuse their bodies (grid_sort_build.hip, icp_one.hip, nabo_kernels.hip), in that order, and the entry points of IcpFast and of the clouds
 // every matcher shares.  The other host units (smhip_ndt_gicp.hip, smhip_filter_api.hip) reach the handle and the functions of
 // namespace smhip_host below through smhip_context.h.
 #include "icp_kernels.hip"
+#include "grid_sort_build.hip"
 #include "icp_one.hip"
 #include "nabo_kernels.hip"
 
@@ -33,6 +34,7 @@ using plan::ceil_div;
 
 static_assert(plan::kRingCoopLanes == kCoopLanes && plan::kNaboBucket == kKdBucket && plan::kNaboShallowLevels <= kKdStack,
               "icp_plan.h restates kernel constants");
+static_assert(plan::kSortBuildMaxTarget == kGsMaxPoints, "icp_plan.h restates grid_sort_build's capacity");
 
 namespace {
 
@@ -110,12 +112,16 @@ static smhip_status ensure_packed(smhip_context* h, int first, int np) {
   return SMHIP_OK;
 }
 
-// per-call resets for pairs [0, np) (main stream, before the halves fork)
-smhip_status enqueue_resets(smhip_context* h, int np, int first) {
+// per-call resets for pairs [first, first + np) (main stream, before the halves fork).  nt_max >= 0: the largest target of the grid
+// build that follows, which decides here, once for all its parts, which form that build takes (plan::sorted_grid_build): the
+// sorted form needs neither `bits` nor `ccount` zeroed -- 1 MiB + nt_cap words per pair -- and gets the light reset.
+smhip_status enqueue_resets(smhip_context* h, int np, int first, int nt_max) {
   IcpDev& d = h->dev;
-  touch_grid(h, first, np);               // bits / ccount are zeroed below: whatever structure was resident is gone
+  touch_grid(h, first, np);               // the build that follows overwrites whatever structure was resident
   HIPCHK(h, hipMemcpyAsync(const_cast<PairInput*>(d.in) + first, h->in_pinned + first, sizeof(PairInput) * np, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(reset_scratch, dim3(std::min(4096, 256 * np)), dim3(256), 0, h->stream, d, first, np);
+  h->build_sorted = nt_max >= 0 && plan::sorted_grid_build(h->grid_sort_build, h->opts.nn_mode, d.sort_cells, d.use_ball ? 0 : 1, np, nt_max);
+  if (h->build_sorted) hipLaunchKernelGGL(reset_scratch_light, dim3(std::min(1024, 8 * np)), dim3(256), 0, h->stream, d, first, np);
+  else hipLaunchKernelGGL(reset_scratch, dim3(std::min(4096, 256 * np)), dim3(256), 0, h->stream, d, first, np);
   return ensure_packed(h, first, np);
 }
 
@@ -144,6 +150,19 @@ smhip_status enqueue_grid_build(smhip_context* h, const Half& f, int nt_max) {
   Bracket br(h, plan::kCatPrepare, f.stream);
   const dim3 gpts(ceil_div(nt_max, 256), np);
   hipLaunchKernelGGL(tgt_reduce, dim3(kTgtReduceBlocks, np), dim3(256), 0, f.stream, d);
+  if (h->build_sorted) {
+    // the form enqueue_resets chose for this call (and left `bits` / `ccount` unzeroed for): setup, sort and fill as one launch
+    if (h->opts.nn_mode == SMHIP_NN_NABO || !d.sort_cells || d.have_rowbits || nt_max > kGsMaxPoints) {
+      h->err = "grid build: the settings changed between the reset and the build"; return SMHIP_ERR_NOT_READY;
+    }
+    hipLaunchKernelGGL(grid_sort_build, dim3(np), dim3(kGsThreads), 0, f.stream, d);
+    HIPCHK(h, hipGetLastError());
+    for (int p = d.pair_base; p < d.pair_base + np; ++p) {
+      h->grid_gen[p] = h->tgt_gen[p]; h->grid_cell_built[p] = d.grid_cell; h->grid_sorted[p] = d.sort_cells; h->grid_rows[p] = d.have_rowbits;
+      h->grid_mode[p] = SMHIP_NN_GRID;
+    }
+    return SMHIP_OK;
+  }
   hipLaunchKernelGGL(grid_setup, dim3(ceil_div(np, 64)), dim3(64), 0, f.stream, d, np);
   if (h->opts.nn_mode == SMHIP_NN_NABO) {
     // the reference's own structure: libnabo's kd-tree over the centred target, rebuilt per Align (icp_fast.cc:464-467)
@@ -204,7 +223,7 @@ smhip_status enqueue_prepare_kept(smhip_context* h, int first, int K) {
 // single-pair form of enqueue_resets + enqueue_grid_build that skips the build when the slot's target is unchanged
 static smhip_status enqueue_prepare_one(smhip_context* h, int slot, int nt_max) {
   if (grid_cached(h, slot)) return enqueue_prepare_kept(h, slot, 1);
-  smhip_status s = enqueue_resets(h, 1, slot);
+  smhip_status s = enqueue_resets(h, 1, slot, nt_max);
   if (s) return s;
   return enqueue_grid_build(h, whole_batch(h, 1, slot), nt_max);
 }
@@ -220,7 +239,7 @@ Half whole_batch(smhip_context* h, int np, int first) {
 // single-stream convenience used by find_closests / the NDT fitness pass
 static smhip_status enqueue_prepare(smhip_context* h, int np, int nt_max) {
   if (np == 1) return enqueue_prepare_one(h, 0, nt_max);
-  smhip_status s = enqueue_resets(h, np);
+  smhip_status s = enqueue_resets(h, np, 0, nt_max);
   if (s) return s;
   return enqueue_grid_build(h, whole_batch(h, np, 0), nt_max);
 }
@@ -373,6 +392,8 @@ static void sync_options(smhip_context* h) {
   { const char* e = std::getenv("SMHIP_SUMS_LONG_FOR"); if (e) h->sums_long_for = std::atoi(e); }
   h->use_shadow = 1;
   { const char* e = std::getenv("SMHIP_SHADOW"); if (e) h->use_shadow = std::atoi(e); }
+  h->grid_sort_build = 1;
+  { const char* e = std::getenv("SMHIP_GRID_BUILD"); if (e) h->grid_sort_build = std::atoi(e); }
   h->wave_search = 0;
   { const char* e = std::getenv("SMHIP_WAVE_SEARCH"); if (e) h->wave_search = std::atoi(e); }
   h->one_enabled = 1; h->one_blocks_want = 0;
@@ -1026,7 +1047,7 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
   if (h->opts.split_after == 0) h->dev.split_after = h->auto_split;
   const bool cached_one = npairs == 1 && grid_cached(h, first);
   if (cached_one) s = enqueue_prepare_one(h, first, nt_max);     // target unchanged: pose + scratch reset only
-  else s = enqueue_resets(h, npairs, first);
+  else s = enqueue_resets(h, npairs, first, nt_max);
   if (s) return s;
   // Split the batch over several streams: the latency-bound launches of one part (finalize, validate, grid
   // build, near-empty refinement kernels) overlap the throughput-bound NN / accumulate of the others.
@@ -1344,6 +1365,40 @@ smhip_status smhip_icp_get_matches(smhip_handle h, int slot, int32_t* ids, float
   if (s) return s;
   HIPCHK(h, hipSetDevice(h->device));
   return fetch_matches(h, slot, ids, d2, n);
+}
+
+smhip_status smhip_icp_debug_get_grid(smhip_handle h, int slot, double mu[3], float cell_origin[4], int32_t dims[7],
+                                      uint32_t* words, int words_cap, uint32_t* cstart, int cstart_cap, float* tq, float* tn, int points_cap) {
+  smhip_status s = check_slot(h, slot);
+  if (s) return s;
+  if (!mu || !cell_origin || !dims) return SMHIP_ERR_INVALID_ARGUMENT;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->grid_mode[slot] != SMHIP_NN_GRID) { h->err = "debug_get_grid: no search grid is resident in the slot"; return SMHIP_ERR_NOT_READY; }
+  PairState st;
+  HIPCHK(h, hipMemcpy(&st, h->dev.state + slot, sizeof(PairState), hipMemcpyDeviceToHost));
+  for (int d = 0; d < 3; ++d) { mu[d] = st.mu[d]; cell_origin[1 + d] = st.origin[d]; }
+  cell_origin[0] = st.h;
+  const int32_t geo[7] = {st.nx, st.ny, st.nz, st.wx, st.nw, st.nocc, st.nt};
+  for (int k = 0; k < 7; ++k) dims[k] = geo[k];
+  if (st.nw < 0 || st.nw > kMaxGridWords || st.nocc < 0 || st.nocc > h->dev.nt_cap || st.nt < 0 || st.nt > h->dev.nt_cap) {
+    h->err = "debug_get_grid: the slot's geometry is out of range"; return SMHIP_ERR_NOT_READY;
+  }
+  const size_t nt_cap = (size_t)h->dev.nt_cap;
+  if (words) {
+    if (words_cap < st.nw) { h->err = "debug_get_grid: words_cap below nw"; return SMHIP_ERR_CAPACITY; }
+    HIPCHK(h, hipMemcpy(words, h->dev.words + (size_t)slot * kMaxGridWords, sizeof(uint2) * (size_t)st.nw, hipMemcpyDeviceToHost));
+  }
+  if (cstart) {
+    if (cstart_cap < st.nocc + 1) { h->err = "debug_get_grid: cstart_cap below nocc + 1"; return SMHIP_ERR_CAPACITY; }
+    HIPCHK(h, hipMemcpy(cstart, h->dev.cstart + (size_t)slot * (nt_cap + 1), sizeof(uint32_t) * ((size_t)st.nocc + 1), hipMemcpyDeviceToHost));
+  }
+  if (tq || tn) {
+    if (points_cap < st.nt) { h->err = "debug_get_grid: points_cap below nt"; return SMHIP_ERR_CAPACITY; }
+    if (tq) HIPCHK(h, hipMemcpy(tq, h->dev.tq + (size_t)slot * nt_cap, sizeof(float4) * (size_t)st.nt, hipMemcpyDeviceToHost));
+    if (tn) HIPCHK(h, hipMemcpy(tn, h->dev.tn + (size_t)slot * nt_cap, sizeof(float4) * (size_t)st.nt, hipMemcpyDeviceToHost));
+  }
+  return SMHIP_OK;
 }
 
 smhip_status smhip_icp_find_closests(smhip_handle h, int slot, const double T[16], int32_t* ids, float* d2, int n) {

@@ -75,6 +75,8 @@ struct smhip_context {
   int one_pairs_max = kOnePairs; // SMHIP_ONE_PAIRS: pairs one launch of it may hold (1 = single pairs only)
   int one_idle = 0;              // SMHIP_ONE_IDLE: with SMHIP_ONE_BLOCKS, keep a grid of mostly idle workgroups on small clouds (tests)
   int one_no_retry = 0;          // SMHIP_ONE_NO_RETRY: a launch that stopped itself is reported, not done again (fetch_range)
+  int grid_sort_build = 1;       // 0 (SMHIP_GRID_BUILD=0): every grid build through the mark / rank / count / place kernels (measurement aid)
+  bool build_sorted = false;     // what the last enqueue_resets chose for the grid build that follows it (plan::sorted_grid_build)
   int wave_search = 0;           // batches: the every-query-searches iterations through nn_ball_lds (0, default: 5-25 % faster on the bench scans)
                                  // or nn_ball_wave (1; SMHIP_WAVE_SEARCH=1) -- same results
   float4* stage = nullptr;       // pinned staging for uploads, 2 * max(ns_cap, nt_cap)
@@ -146,7 +148,7 @@ smhip_status filter_ensure(smhip_context* h);
 smhip_status check_slot(smhip_context* h, int slot);
 smhip_status prep_ensure(smhip_context* h);
 smhip_status prep_run(smhip_context* h, const float4* raw_dev, int n, int slot, int* n_out);
-smhip_status enqueue_resets(smhip_context* h, int np, int first = 0);
+smhip_status enqueue_resets(smhip_context* h, int np, int first = 0, int nt_max = -1);
 smhip_status enqueue_grid_build(smhip_context* h, const Half& f, int nt_max);
 bool grid_cached(smhip_context* h, int slot);
 smhip_status enqueue_prepare_kept(smhip_context* h, int first, int K);

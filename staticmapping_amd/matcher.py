@@ -245,6 +245,21 @@ class IcpFastHip:
                                                     d2.ctypes.data_as(_capi.c_float_p), n))
         return ids, d2
 
+    def debug_get_grid(self, slot: int = 0) -> dict:
+        """The search grid resident in `slot` (smhip_icp_debug_get_grid): mu, h, origin, nx, ny, nz, wx, nw, nocc, nt and the arrays
+        words [nw, 2] uint32, cstart [nocc + 1] uint32, tq / tn [nt, 4] float32 (tq[:, 3] holds the caller index as int32 bits)."""
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        mu = np.zeros(3); ho = np.zeros(4, np.float32); dims = np.zeros(7, np.int32)
+        geo = (mu.ctypes.data_as(_capi.c_double_p), ho.ctypes.data_as(_capi.c_float_p), dims.ctypes.data_as(_capi.c_int32_p))
+        self._check(self._lib.smhip_icp_debug_get_grid(self._h, slot, *geo, None, 0, None, 0, None, None, 0))
+        nx, ny, nz, wx, nw, nocc, nt = (int(v) for v in dims)
+        words = np.zeros((nw, 2), np.uint32); cstart = np.zeros(nocc + 1, np.uint32)
+        tq = np.zeros((nt, 4), np.float32); tn = np.zeros((nt, 4), np.float32)
+        self._check(self._lib.smhip_icp_debug_get_grid(self._h, slot, *geo, words.ctypes.data_as(u32p), nw, cstart.ctypes.data_as(u32p), nocc + 1,
+                                                       tq.ctypes.data_as(_capi.c_float_p), tn.ctypes.data_as(_capi.c_float_p), nt))
+        return dict(mu=mu, h=ho[0], origin=ho[1:].copy(), nx=nx, ny=ny, nz=nz, wx=wx, nw=nw, nocc=nocc, nt=nt,
+                    words=words, cstart=cstart, tq=tq, tn=tn)
+
     def search_counts(self, slot: int = 0):
         """Queries that went through a search in iterations 0..11 of the slot's last Align."""
         c = (ctypes.c_uint32 * 12)()
