@@ -348,6 +348,11 @@ smhip_status smhip_get_target_f32(smhip_handle h, int slot, float* xyz, float* n
 smhip_status smhip_get_source_f32(smhip_handle h, int slot, float* xyzw, int n);
 smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6], int compute_hessian,
                                            double* score, double grad[6], double hess[36]);
+/* the same evaluation in either arithmetic -- double_math = 0: pclomp's float per-pair math (Ndt), 1: stock PCL's double
+ * (the NDT stage of NdtWithGicp) -- for this call only, and with the number of (point, voxel) pairs that entered the sums
+ * (pairs may be NULL). */
+smhip_status smhip_ndt_compute_derivatives_ex(smhip_handle h, const double pose6[6], int compute_hessian, int double_math,
+                                              double* score, double grad[6], double hess[36], double* pairs);
 /* measurement hook: `launches` back-to-back computeDerivatives launches (with Hessian) over slots first_slot .. + npairs - 1 at the
  * poses their last Align ended with, HIP events around them on the handle's stream: *ms_per_launch = the average duration of
  * the kernel, *pairs_per_launch = the (point, voxel) pairs one launch works through (for its algorithmic bytes).  The slots'

@@ -643,6 +643,8 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtDev& d, const NdtP
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live) { const f32x4 v = ((gptr<f32x4>)d.src)[i]; s = make_float4(v.x, v.y, v.z, v.w); }
     live = live && isfinite(s.x) && isfinite(s.y) && isfinite(s.z);
+    // (a row that is not finite has no pairs, and phase C multiplies its sums -- zeros -- by the point: zero times NaN is NaN)
+    if (!live) s = make_float4(0.f, 0.f, 0.f, 0.f);
     // pcl::transformPointCloud with the float final_transformation_
     const float tx = P.T[0] * s.x + P.T[1] * s.y + P.T[2] * s.z + P.T[3];
     const float ty = P.T[4] * s.x + P.T[5] * s.y + P.T[6] * s.z + P.T[7];

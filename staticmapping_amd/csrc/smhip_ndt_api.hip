@@ -523,7 +523,10 @@ smhip_status smhip_ndt_get_voxels(smhip_handle h, int capacity, int32_t* keys, i
   return SMHIP_OK;
 }
 
-smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6], int compute_hessian, double* score, double grad[6], double hess[36]) {
+// One evaluation in either arithmetic (R = float: pclomp, R = double: stock PCL as NdtWithGicp runs it), with the pair count of
+// column 28.  double_math holds for this call only: the handle's own setting is put back before returning.
+smhip_status smhip_ndt_compute_derivatives_ex(smhip_handle h, const double pose6[6], int compute_hessian, int double_math, double* score, double grad[6],
+                                              double hess[36], double* pairs) {
   if (!h || !pose6 || !score || !grad || !hess) return SMHIP_ERR_INVALID_ARGUMENT;
   NdtHost& n = ndt_of(h);
   if (n.cap < 1 || !n.meta[0].valid) { h->err = "voxel grid not built"; return SMHIP_ERR_NOT_READY; }
@@ -531,21 +534,33 @@ smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6]
   HIPCHK(h, hipSetDevice(h->device));
   smhip_status s = ndt_push_devs(h, 0, 1);
   if (s) return s;
+  const bool was_double = n.double_math;
+  n.double_math = double_math != 0;
   // one round of the device driver with a job that only wants this evaluation
   const NdtCtlOpts o = ndt_ctl_opts(n);
   ndt_ctl_start(n, o, n.ctl_host[0], 0, nullptr, pose6, kNdtEvalOnly);
   n.ctl_host[0].pose.compute_hessian = compute_hessian != 0;
   n.flags_pinned[0] = 0;
-  HIPCHK(h, hipMemcpyAsync(n.ctl_dev, n.ctl_host, sizeof(NdtCtl), hipMemcpyHostToDevice, h->stream));
-  ndt_enqueue_round(h, 0, 1, std::max(1, ceil_div(h->ns[0], kNdtDerivThreads)), o, 0, n.out_pinned);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  hipError_t e = hipMemcpyAsync(n.ctl_dev, n.ctl_host, sizeof(NdtCtl), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    ndt_enqueue_round(h, 0, 1, std::max(1, ceil_div(h->ns[0], kNdtDerivThreads)), o, 0, n.out_pinned);
+    e = hipStreamSynchronize(h->stream);
+  }
+  n.double_math = was_double;
+  HIPCHK(h, e);
   HIPCHK(h, hipGetLastError());
   *score = n.out_pinned[0];
   for (int i = 0; i < 6; ++i) grad[i] = n.out_pinned[1 + i];
   for (int i = 0; i < 36; ++i) hess[i] = compute_hessian ? n.out_pinned[7 + i] : 0.0;
   n.last_pairs = n.out_pinned[43];
+  if (pairs) *pairs = n.out_pinned[43];
   n.deriv_calls++;
   return SMHIP_OK;
+}
+
+smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6], int compute_hessian, double* score, double grad[6], double hess[36]) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  return smhip_ndt_compute_derivatives_ex(h, pose6, compute_hessian, ndt_of(h).double_math ? 1 : 0, score, grad, hess, nullptr);
 }
 
 smhip_status smhip_ndt_time_derivatives(smhip_handle h, int first_slot, int npairs, int launches, double* ms_per_launch, double* pairs_per_launch) {

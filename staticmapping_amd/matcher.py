@@ -367,6 +367,16 @@ class NdtHip(IcpFastHip):
                                                             H.ctypes.data_as(_capi.c_double_p)))
         return score.value, g, H.reshape(6, 6)
 
+    def compute_derivatives_ex(self, pose6, compute_hessian: bool = True, double_math: bool = False):
+        """One computeDerivatives evaluation in pclomp's float arithmetic or (double_math) stock PCL's double, as NdtWithGicp
+        runs it (smhip_ndt_compute_derivatives_ex): (score, gradient[6], hessian[6, 6], (point, voxel) pairs summed)."""
+        p = _f64(pose6)
+        score = ctypes.c_double(); pairs = ctypes.c_double(); g = np.zeros(6); H = np.zeros(36)
+        self._check(self._lib.smhip_ndt_compute_derivatives_ex(self._h, p.ctypes.data_as(_capi.c_double_p), int(compute_hessian), int(double_math),
+                                                               ctypes.byref(score), g.ctypes.data_as(_capi.c_double_p),
+                                                               H.ctypes.data_as(_capi.c_double_p), ctypes.byref(pairs)))
+        return score.value, g, H.reshape(6, 6), int(pairs.value)
+
     def time_derivatives(self, npairs: int = 1, launches: int = 20, first_slot: int = 0):
         """HIP-event time of back-to-back computeDerivatives launches over the slots' last poses (smhip_ndt_time_derivatives):
         (ms per launch, (point, voxel) pairs per launch)."""
