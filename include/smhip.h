@@ -539,6 +539,44 @@ smhip_status smhip_submap_build_f32(smhip_handle h, int n_frames, const float* c
  * otherwise as smhip_prepare_target_f32 on the same rows. */
 smhip_status smhip_filter_output_to_target(smhip_handle h, int slot, int* n_out);
 
+/* ---- descriptor::M2dp (descriptor/m2dp.{h,cc}) -------------------------------------------------
+ * The submap descriptor behind the loop detector's candidate search (builder/frame_base.cc:107-112,
+ * back_end/loop_detector.cc:130-150), computed on the device in one submission: f64 moments of the rows, the PCA axes,
+ * preProcess (m2dp.cc:45-70), the p*q signature histograms of singleViewProcess (:72-120) by integer atomics, and the first
+ * singular pair of A (:140-147).  The descriptor is p*q + l*t floats, l = ceil(sqrt(max_distance / r)): the first left singular
+ * vector followed by the first right one.  Two things the reference leaves open are defined in DESIGN.md section 6 ("M2DP"):
+ * the PCA projection (mean and covariance / (N - 1) in double, eigenvalues descending, each of the first two axes signed so that
+ * its largest-magnitude component is positive, third = first x second) and the sign of the singular pair (sum(u1) >= 0).
+ * Same input, same bits: the moments are reduced in a fixed order and the histogram is integer.
+ * Device limits: p * q <= 64 views and l * t <= 8192 columns. */
+typedef struct smhip_m2dp_options {
+  double r;                      /* 0.1 */
+  double max_distance;           /* 100 */
+  int32_t t, p, q;               /* 16, 4, 16 */
+} smhip_m2dp_options;
+void smhip_m2dp_default_options(smhip_m2dp_options* o);                                  /* M2dp::M2dp, m2dp.h:48-49 */
+/* p*q + l*t, or -1 when the options are refused: null, r or max_distance not finite, r < 1e-6 (m2dp.cc:64), max_distance <= 0,
+ * t, p or q < 1, or beyond the device limits above */
+int smhip_m2dp_length(const smhip_m2dp_options* opts);
+/* setInputCloud + getFinalDescriptor for n uploaded rows of `stride_floats` floats (4: x y z intensity, 5: InnerPointType); len
+ * must equal smhip_m2dp_length(opts).  Nothing is allocated after a handle's first descriptor.
+ * Refused before anything is touched: a null pointer, a stride other than 4 or 5, refused options, n < 2, a wrong len --
+ * SMHIP_ERR_INVALID_ARGUMENT; n above max(max_source_points, max_target_points) -- SMHIP_ERR_CAPACITY.
+ * Found by the kernels, SMHIP_ERR_INVALID_ARGUMENT afterwards with `descriptor` not written: a row with a non-finite coordinate;
+ * no row within max_distance of the centroid (sigma1 = 0). */
+smhip_status smhip_m2dp_f32(smhip_handle h, const float* points, int stride_floats, int n, const smhip_m2dp_options* opts,
+                            float* descriptor, int len);
+/* the same for the filter workspace's current cloud (a filter chain's output or a built submap): no download, and the workspace
+ * is left as it was.  SMHIP_ERR_NOT_READY when no cloud is there. */
+smhip_status smhip_m2dp_from_filter_output(smhip_handle h, const smhip_m2dp_options* opts, float* descriptor, int len);
+/* parity-test hook: what the last descriptor call on the handle computed, for its n rows.  Any pointer may be NULL.  projected3:
+ * 3 n floats, the rows after the PCA projection; kept: n words, 1 = getLength <= max_distance; A: the a_len = p*q*l*t counters,
+ * row p*q_ + q, column l_index * t + t_index; n_kept: the kept rows.  SMHIP_ERR_NOT_READY when no call got as far as the
+ * histogram. */
+smhip_status smhip_m2dp_last(smhip_handle h, float* projected3, int32_t* kept, int32_t* A, int a_len, int* n_kept);
+/* matchTwoM2dpDescriptors, m2dp.cc:151-169, on the host in double: -1 for a null pointer or n < 10 */
+double smhip_m2dp_match(const float* P, const float* Q, int n);
+
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one
  * InsertPointCloud per frame, builder/map_builder.cc:832-900), on the device.  Results equal the reference's insert loop

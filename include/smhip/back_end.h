@@ -8,16 +8,24 @@
 //       matcher from the configured submap_matcher_options (:408-414), guess from the first frames' global poses
 //       (:427-429), NormalizeRotation(result) (:434), keep the result when score >= accepted_min_score else the guess
 //       (:435-444)
-// The scheduling around them (M2DP candidate search, threads, pose graph) is host control plane and stays out.
+//   LoopDetector::AddFrame         back_end/loop_detector.cc:48-271, with SetSearchWindow (:273-280) and CheckResult (:320-345)
+//       the distance gate, the descriptor gate (matchTwoM2dpDescriptors on the frames' M2DP descriptors, smhip/m2dp.h), the
+//       choice of candidate pairs, the five-state loop machine, CloseLoop per pair and CheckResult.  The candidate selection
+//       (SelectLoopCandidates), the state machine (NextLoopStatus) and CheckLoopResult are free functions that touch no device.
+// The scheduling around them (threads, pose graph) is host control plane and stays out.
 #ifndef SMHIP_BACK_END_H_
 #define SMHIP_BACK_END_H_
 
+#include <algorithm>
+#include <array>
 #include <cmath>
+#include <limits>
 #include <memory>
 #include <utility>
 #include <thread>
 #include <vector>
 
+#include "smhip/m2dp.h"
 #include "smhip/registrator.h"
 
 namespace smhip {
@@ -67,10 +75,19 @@ struct LoopEdge {
   double score = 0.0;
 };
 
-struct LoopDetectorSettings {                   // back_end/loop_detector_options.h:39
+struct LoopDetectorSettings {                   // back_end/loop_detector_options.h:29-40
   float accept_scan_match_score = 0.75f;
   int device = 0;
   int max_points = 1 << 18;          // initial arena size; the matcher grows it to fit the clouds
+  bool use_gps = false;              // (GPS in the guess is commented out in the reference, loop_detector.cc:291-300: carried, unused)
+  bool use_descriptor = false;
+  bool output_matched_cloud = false; // (the debug output of :232-266 is not restated: carried, unused)
+  int loop_ignore_threshold = 15;
+  int trying_detect_loop_count = 1;
+  int nearest_history_pos_num = 4;
+  float max_close_loop_distance = 25.f;
+  float max_close_loop_z_distance = 1.f;
+  float m2dp_match_score = 0.99f;
 };
 
 // LoopDetector::CloseLoop for one candidate pair of frames.  `scan_matcher` plays the stack matcher of :304; handing in
@@ -98,6 +115,247 @@ inline bool CloseLoop(const Matrix4d& target_global_pose, const InnerCloudPtr& t
   scan_matcher.InitWithOptions();
   return CloseLoop(target_global_pose, target_cloud, source_global_pose, source_cloud, settings, edge, &scan_matcher);
 }
+
+// ---- LoopDetector (back_end/loop_detector.{h,cc}) ------------------------------------------------------------------------
+
+enum class LoopStatus : uint8_t { kNoLoop, kTryingToCloseLoop, kEnteringLoop, kContinousLoop, kLeavingLoop };   // loop_detector.h:41-47
+
+struct DetectResult {                           // loop_detector.h:49-70
+  int current_frame_index = 0;
+  LoopStatus status = LoopStatus::kNoLoop;
+  bool close_succeed = false;                   // is it a good loop detection result
+  std::vector<LoopEdge> edges;
+};
+
+// What the detector reads of the reference's Submap: GlobalPose() / GlobalTranslation(), Cloud() and GetDescriptor().  Frames are
+// shared: the detector reads their poses again on every AddFrame, since they could have been changed (:52-57).
+struct LoopFrame {
+  Matrix4d global_pose = Matrix4d::Identity();
+  InnerCloudPtr cloud;                          // may stay empty until a CloseLoop needs it
+  descriptor::M2dp::Descriptor descriptor;      // read when use_descriptor is set
+};
+
+struct LoopCandidates {
+  int loop_detection = 0;                                   // :123-127
+  std::vector<std::pair<int, int>> maybe_close_pair;        // (target, source = current), :124-153
+  int closest_index = -1;                                   // after the 0.4 rule, :98-100
+  std::vector<int> indices_in_distance, indices_well_matched;
+};
+
+// loop_detector.cc:69-153 for the newest frame (index translations.size() - 1): the window, the xy / z gate, the closest index
+// dropped at 0.4 x the distance, the descriptor gate or the copy, the step rule for nearest_history_pos_num and the closest pair
+// appended.  descriptors[i] is read only when use_descriptor is set.  No device involved.
+inline LoopCandidates SelectLoopCandidates(const LoopDetectorSettings& settings, const std::vector<std::array<double, 3>>& translations,
+                                           const std::vector<const descriptor::M2dp::Descriptor*>& descriptors, int search_window_start,
+                                           int search_window_end) {
+  SMHIP_CHECK(settings.nearest_history_pos_num >= 1, "nearest_history_pos_num must be at least 1 (the step rule divides by it, :130-131)");
+  LoopCandidates out;
+  const int current_index = static_cast<int>(translations.size()) - 1;
+  const int max_index = current_index;                                                        // :69
+  const double cur_x = translations[current_index][0], cur_y = translations[current_index][1], cur_z = translations[current_index][2];
+  double min_distance = std::numeric_limits<double>::max();
+  int closest_index = -1;
+  auto clamp = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+  int start_index = 0;
+  int end_index = max_index - settings.loop_ignore_threshold;                                 // :80
+  if (search_window_end >= 0 && search_window_start >= 0) {                                   // :81-84
+    start_index = clamp(search_window_start, 0, max_index);
+    end_index = clamp(search_window_end, 0, max_index);
+  }
+  for (int i = start_index; i < end_index; ++i) {                                             // :85-97
+    const double dx = cur_x - translations[i][0], dy = cur_y - translations[i][1];
+    const double xy_distance = std::sqrt(dx * dx + dy * dy);
+    const double z_distance = std::fabs(cur_z - translations[i][2]);
+    if (xy_distance <= settings.max_close_loop_distance && z_distance <= settings.max_close_loop_z_distance) {
+      out.indices_in_distance.push_back(i);
+      if (xy_distance < min_distance) { closest_index = i; min_distance = xy_distance; }
+    }
+  }
+  if (min_distance >= settings.max_close_loop_distance * 0.4) closest_index = -1;             // :98-100
+  out.closest_index = closest_index;
+
+  std::vector<int>& indices_well_matched = out.indices_well_matched;
+  if (!out.indices_in_distance.empty()) {                                                     // :103-121
+    if (!settings.use_descriptor) {
+      indices_well_matched = out.indices_in_distance;
+    } else {
+      for (int i : out.indices_in_distance) {
+        SMHIP_CHECK(i != current_index, "CHECK_NE(i, current_index)");
+        if (descriptor::matchTwoM2dpDescriptors(*descriptors[current_index], *descriptors[i]) > settings.m2dp_match_score)
+          indices_well_matched.push_back(i);
+      }
+    }
+  }
+  if (!indices_well_matched.empty()) {                                                        // :126-153
+    out.loop_detection = 1;
+    std::sort(indices_well_matched.begin(), indices_well_matched.end());
+    const size_t num = static_cast<size_t>(settings.nearest_history_pos_num);
+    if (indices_well_matched.size() >= num * 2) {
+      const int step = static_cast<int>(indices_well_matched.size()) / settings.nearest_history_pos_num;
+      for (int i = 0; i < settings.nearest_history_pos_num; ++i) out.maybe_close_pair.push_back(std::make_pair(indices_well_matched[i * step], current_index));
+    } else {
+      const int size = indices_well_matched.size() > num ? settings.nearest_history_pos_num : static_cast<int>(indices_well_matched.size());
+      for (int i = 0; i < size; ++i) out.maybe_close_pair.push_back(std::make_pair(indices_well_matched[i], current_index));
+    }
+    if (closest_index >= 0) {
+      const auto closest_pair = std::make_pair(closest_index, current_index);
+      if (std::find(out.maybe_close_pair.begin(), out.maybe_close_pair.end(), closest_pair) == out.maybe_close_pair.end())
+        out.maybe_close_pair.push_back(closest_pair);
+    }
+  }
+  return out;
+}
+
+// the loop machine, loop_detector.cc:155-206: the status after a frame with (1) or without (0) a detection
+inline LoopStatus NextLoopStatus(LoopStatus current_status, int loop_detection, const LoopDetectorSettings& settings,
+                                 int* accumulate_loop_detected_count) {
+  switch (current_status) {
+    case LoopStatus::kNoLoop:
+      *accumulate_loop_detected_count = 0;
+      if (loop_detection == 1) {
+        current_status = LoopStatus::kTryingToCloseLoop;
+        ++*accumulate_loop_detected_count;
+        if (*accumulate_loop_detected_count >= settings.trying_detect_loop_count) current_status = LoopStatus::kEnteringLoop;
+      }
+      break;
+    case LoopStatus::kTryingToCloseLoop:
+      if (loop_detection == 1) {
+        ++*accumulate_loop_detected_count;
+        if (*accumulate_loop_detected_count >= settings.trying_detect_loop_count) current_status = LoopStatus::kEnteringLoop;
+      } else if (loop_detection == 0) {
+        current_status = LoopStatus::kNoLoop;
+      }
+      break;
+    case LoopStatus::kEnteringLoop:
+      if (loop_detection == 0) current_status = LoopStatus::kTryingToCloseLoop;
+      else if (loop_detection == 1) current_status = LoopStatus::kContinousLoop;
+      break;
+    case LoopStatus::kContinousLoop:
+      if (loop_detection == 0) { current_status = LoopStatus::kLeavingLoop; *accumulate_loop_detected_count = 0; }
+      break;
+    case LoopStatus::kLeavingLoop:
+      if (loop_detection == 0) current_status = LoopStatus::kNoLoop;
+      else if (loop_detection == 1) current_status = LoopStatus::kTryingToCloseLoop;
+      break;
+    default:
+      break;
+  }
+  return current_status;
+}
+
+// common::RotationMatrixToEulerAngles (common/math.h:108-127) of a transform's rotation block
+inline void RotationMatrixToEulerAngles(const Matrix4d& R, double eulers[3]) {
+  const double sy = std::sqrt(R(0, 0) * R(0, 0) + R(1, 0) * R(1, 0));
+  if (!(sy < 1e-6)) {
+    eulers[0] = std::atan2(R(2, 1), R(2, 2)); eulers[1] = std::atan2(-R(2, 0), sy); eulers[2] = std::atan2(R(1, 0), R(0, 0));
+  } else {
+    eulers[0] = std::atan2(-R(1, 2), R(1, 1)); eulers[1] = std::atan2(-R(2, 0), sy); eulers[2] = 0;
+  }
+}
+
+// LoopDetector::CheckResult, loop_detector.cc:320-345: more than one edge, and every edge puts the source within 0.25 m and
+// 0.02 rad (norm of the Euler angles) of where the first edge puts it.  target_poses[k] = GlobalPose() of edge k's target.
+inline bool CheckLoopResult(const std::vector<LoopEdge>& edges, const std::vector<Matrix4d>& target_poses) {
+  if (edges.size() <= 1) return false;
+  const Matrix4d first_source_pose = Multiply(target_poses[0], edges[0].transform);
+  for (size_t i = 1; i < edges.size(); ++i) {
+    const Matrix4d source_edge = Multiply(target_poses[i], edges[i].transform);
+    const Matrix4d diff = Multiply(RigidInverse(first_source_pose), source_edge);
+    const double trans_diff = std::sqrt(diff(0, 3) * diff(0, 3) + diff(1, 3) * diff(1, 3) + diff(2, 3) * diff(2, 3));
+    double e[3];
+    RotationMatrixToEulerAngles(diff, e);
+    const double rotation_diff = std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    if (trans_diff > 0.25 || rotation_diff > 0.02) return false;
+  }
+  return true;
+}
+
+class LoopDetector {
+ public:
+  explicit LoopDetector(const LoopDetectorSettings& l_d_settings) : settings_(l_d_settings) {}
+  LoopDetector(const LoopDetector&) = delete;
+  LoopDetector& operator=(const LoopDetector&) = delete;
+
+  // loop_detector.cc:48-271
+  DetectResult AddFrame(const std::shared_ptr<LoopFrame>& frame, bool do_loop_detect = true) {
+    SMHIP_CHECK(frame != nullptr, "null frame");
+    all_frames_.push_back(frame);
+    // Update all positions since they could have been changed.
+    all_frames_translation_.emplace_back();
+    for (size_t i = 0; i < all_frames_.size(); ++i)
+      all_frames_translation_[i] = {all_frames_[i]->global_pose(0, 3), all_frames_[i]->global_pose(1, 3), all_frames_[i]->global_pose(2, 3)};
+    const int current_index = static_cast<int>(all_frames_.size()) - 1;
+
+    DetectResult result;
+    result.status = current_status_;
+    result.current_frame_index = current_index;
+    if (!do_loop_detect || all_frames_.size() <= static_cast<size_t>(settings_.loop_ignore_threshold)) return result;   // :64-67
+
+    std::vector<const descriptor::M2dp::Descriptor*> descriptors(all_frames_.size());
+    for (size_t i = 0; i < all_frames_.size(); ++i) descriptors[i] = &all_frames_[i]->descriptor;
+    last_candidates_ = SelectLoopCandidates(settings_, all_frames_translation_, descriptors, search_window_start_, search_window_end_);
+    loop_detection_ = last_candidates_.loop_detection;
+    const std::vector<std::pair<int, int>>& maybe_close_pair = last_candidates_.maybe_close_pair;
+
+    current_status_ = NextLoopStatus(current_status_, loop_detection_, settings_, &accumulate_loop_detected_count_);
+
+    if (current_status_ == LoopStatus::kContinousLoop) {                                       // :213-268
+      SMHIP_CHECK(!maybe_close_pair.empty(), "CHECK(!maybe_close_pair.empty())");
+      // (the reference hands the pairs to a tbb::task_group and collects the edges in the order they finish; here they run one
+      // after the other through one matcher that keeps its device arena, and the edges come in the pairs' order)
+      for (const auto& p : maybe_close_pair) {
+        LoopEdge loop_edge;
+        loop_edge.close_pair_index = p;
+        if (CloseLoopPair(&loop_edge)) result.edges.push_back(loop_edge);
+      }
+      if (!result.edges.empty()) result.close_succeed = CheckResult(result);
+    }
+    return result;
+  }
+
+  void SetSearchWindow(const int start_index, const int end_index) {                           // :273-280
+    SMHIP_CHECK(start_index >= 0, "CHECK_GE(start_index, 0)");
+    SMHIP_CHECK(end_index >= 0, "CHECK_GE(end_index, 0)");
+    SMHIP_CHECK(end_index >= start_index, "CHECK_GE(end_index, start_index)");
+    search_window_start_ = start_index;
+    search_window_end_ = end_index;
+  }
+  const std::vector<std::shared_ptr<LoopFrame>>& GetFrames() const { return all_frames_; }
+  LoopStatus Status() const { return current_status_; }
+  // what the last AddFrame that searched selected (for inspection and tests)
+  const LoopCandidates& LastCandidates() const { return last_candidates_; }
+
+  bool CheckResult(const DetectResult& result) const {                                         // :320-345
+    std::vector<Matrix4d> target_poses;
+    for (const LoopEdge& e : result.edges) target_poses.push_back(all_frames_.at(static_cast<size_t>(e.close_pair_index.first))->global_pose);
+    return CheckLoopResult(result.edges, target_poses);
+  }
+
+ protected:
+  bool CloseLoopPair(LoopEdge* edge) {                                                         // :282-318
+    const size_t target_id = static_cast<size_t>(edge->close_pair_index.first), source_id = static_cast<size_t>(edge->close_pair_index.second);
+    SMHIP_CHECK(all_frames_.size() > target_id && all_frames_.size() > source_id, "CHECK(all_frames_.size() > target_id && ... > source_id)");
+    SMHIP_CHECK(all_frames_[target_id]->cloud && all_frames_[source_id]->cloud, "a frame of a candidate pair has no cloud");
+    if (!scan_matcher_) {
+      scan_matcher_.reset(new registrator::IcpPointMatcherHip(settings_.device, settings_.max_points));
+      scan_matcher_->InitWithOptions();
+    }
+    return CloseLoop(all_frames_[target_id]->global_pose, all_frames_[target_id]->cloud, all_frames_[source_id]->global_pose,
+                     all_frames_[source_id]->cloud, settings_, edge, scan_matcher_.get());
+  }
+
+ private:
+  std::vector<std::shared_ptr<LoopFrame>> all_frames_;
+  std::vector<std::array<double, 3>> all_frames_translation_;
+  int loop_detection_ = 0;
+  int accumulate_loop_detected_count_ = 0;
+  LoopStatus current_status_ = LoopStatus::kNoLoop;
+  LoopDetectorSettings settings_;
+  int search_window_start_ = -1;
+  int search_window_end_ = -1;
+  LoopCandidates last_candidates_;
+  std::unique_ptr<registrator::IcpPointMatcherHip> scan_matcher_;
+};
 
 struct SubmapPairMatchResult {
   Matrix4d transform_to_next = Matrix4d::Identity();   // what SetMatchedTransformedToNext receives

@@ -31,6 +31,7 @@
 
 #include "smhip/back_end.h"
 #include "smhip/filters.h"
+#include "smhip/m2dp.h"
 
 namespace smhip {
 namespace builder {
@@ -126,6 +127,22 @@ class Submap {
     return cloud_;
   }
 
+  // FrameBase::CalculateDescriptor / GetDescriptor / SetDescriptor (builder/frame_base.cc:99-112) for the submap's cloud: built
+  // on `context`'s device (the process-wide default context when none is given) and described where it lies (descriptor::M2dp
+  // with its defaults, smhip/m2dp.h), without a download.  false (and the descriptor left as it was) when none was got.
+  bool CalculateDescriptor(const std::shared_ptr<DeviceContext>& context = nullptr) {
+    const std::shared_ptr<DeviceContext> c = context ? context : DeviceContext::Default();
+    descriptor::M2dp m2dp;
+    if (BuildResident(c->handle()) > 0 && m2dp.setInputCloudResident(c->handle())) {
+      descriptor_ = m2dp.getFinalDescriptor();
+      return true;
+    }
+    std::fprintf(stderr, "[ERROR] did not get a descriptor for the frame.\n");
+    return false;
+  }
+  descriptor::M2dp::Descriptor GetDescriptor() const { return descriptor_; }
+  void SetDescriptor(const descriptor::M2dp::Descriptor& d) { descriptor_ = d; }
+
   // Device forms: the cloud is built on the matcher's own handle and becomes its source / its CalculateNormals target without
   // a download.  Return the number of points the matcher holds (0 when the device refused; Align then fails loudly).
   int ToSource(registrator::IcpFastHip* matcher) const {
@@ -142,6 +159,7 @@ class Submap {
   std::vector<data::InnerCloudType::Ptr> frames_;
   std::vector<Matrix4d> local_poses_;
   InnerCloudPtr cloud_;
+  descriptor::M2dp::Descriptor descriptor_;
 };
 
 // The pairs ConnectSubmaps matches, in its order: for k = 0, 1, ... source = submap k + 1 on target = submap k

@@ -12,3 +12,4 @@ from .matcher import (IcpFastHip, IcpPointMatcherHip, NdtGicpHip, NdtHip, SmhipE
                       NN_BRUTE, NN_GRID, NN_NABO)
 from .mrvm import MultiResolutionVoxelMapHip  # noqa: F401
 from .submap import SubmapBuilder, build_submap, output_to_target  # noqa: F401
+from . import m2dp  # noqa: F401

@@ -85,6 +85,11 @@ class MrvmSettings(ctypes.Structure):
                 ("use_max_intensity", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class M2dpOptions(ctypes.Structure):
+    _fields_ = [("r", ctypes.c_double), ("max_distance", ctypes.c_double), ("t", ctypes.c_int32), ("p", ctypes.c_int32),
+                ("q", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/smhip.h declares
 SIGNATURES = {
     "smhip_version": (ctypes.c_int, []),
@@ -172,6 +177,12 @@ SIGNATURES = {
     "smhip_submap_build_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(c_float_p), ctypes.c_int, c_int32_p, c_double_p,
                                               ctypes.c_float, ctypes.POINTER(ctypes.c_int)]),
     "smhip_filter_output_to_target": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_m2dp_default_options": (None, [ctypes.POINTER(M2dpOptions)]),
+    "smhip_m2dp_length": (ctypes.c_int, [ctypes.POINTER(M2dpOptions)]),
+    "smhip_m2dp_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(M2dpOptions), c_float_p, ctypes.c_int]),
+    "smhip_m2dp_from_filter_output": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(M2dpOptions), c_float_p, ctypes.c_int]),
+    "smhip_m2dp_last": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_int32_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_m2dp_match": (ctypes.c_double, [c_float_p, c_float_p, ctypes.c_int]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

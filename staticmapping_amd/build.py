@@ -20,8 +20,8 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 FLAGS_STAMP = os.path.join(OBJ_DIR, "flags.txt")          # the compile flags the objects and dependency files were made with
 
 # translation units, slowest first (each #includes its kernel files and fragments: its dependency file lists them)
-UNITS = ["smhip_api.hip", "smhip_mrvm.hip", "cloud_filters.hip", "prep_normals.hip", "smhip_ndt_gicp.hip", "smhip_filter_api.hip", "smhip_submap.hip",
-         "host_cloud.cc"]
+UNITS = ["smhip_api.hip", "smhip_mrvm.hip", "cloud_filters.hip", "prep_normals.hip", "smhip_ndt_gicp.hip", "smhip_filter_api.hip", "smhip_m2dp.hip",
+         "smhip_submap.hip", "host_cloud.cc"]
 
 
 def _hipcc() -> str:

@@ -1,6 +1,6 @@
 // smhip_context.h -- what the host translation units of libsmhip.so share: the handle behind smhip_handle, the error and
 // allocation helpers every entry point uses, and the handful of functions of the ICP unit (smhip_api.hip) that the NDT /
-// NdtWithGicp unit (smhip_ndt_gicp.hip), the filter unit (smhip_filter_api.hip) and the submap unit (smhip_submap.hip) call.
+// NdtWithGicp unit (smhip_ndt_gicp.hip), the filter unit (smhip_filter_api.hip), the submap unit (smhip_submap.hip) and the descriptor unit (smhip_m2dp.hip) call.
 // Internal: not installed, not part of the C ABI (include/smhip.h).  Everything else in those units is file-local.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,10 +19,12 @@ using namespace smhip;          // (every includer is a host unit of the library
 
 struct smhip_ndt_state;         // the NDT / NdtWithGicp unit's own (smhip_ndt_api.hip, smhip_gicp_api.hip): created on first use,
 struct smhip_gicp_state;        // freed through smhip_internal_free_ndt / _gicp
+struct smhip_m2dp_state;        // the descriptor unit's own (smhip_m2dp.hip): created on first use, freed through smhip_internal_free_m2dp
 
 struct smhip_context {
   smhip_ndt_state* ndt = nullptr;
   smhip_gicp_state* gicp = nullptr;
+  smhip_m2dp_state* m2dp = nullptr;
   PrepWorkspace* prep = nullptr;          // device CalculateNormals workspace (allocated on first use)
   PrepWorkspace* prep_batch = nullptr;    // the same sized for every slot at once (batched target preparation)
   FilterWorkspace* filt = nullptr;        // device pre-filters (allocated on first use)
