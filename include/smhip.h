@@ -577,6 +577,75 @@ smhip_status smhip_m2dp_last(smhip_handle h, float* projected3, int32_t* kept, i
 /* matchTwoM2dpDescriptors, m2dp.cc:151-169, on the host in double: -1 for a null pointer or n < 10 */
 double smhip_m2dp_match(const float* P, const float* Q, int n);
 
+/* ---- pose graph (what back_end::IsamOptimizer asks of GTSAM, back_end/isam_optimizer.{h,cc}) ----------
+ * One rigid pose per node (a submap), between-factors on edges (odometry between consecutive submaps, loop edges from the loop
+ * detector), nodes flagged `fixed` held where they are.  Defined in DESIGN.md section 6 ("Pose graph") and restated in
+ * tests/pose_graph_ref.py -- GTSAM is third-party code the reference only calls:
+ *   E = Z^-1 X_i^-1 X_j,  e = [Log_SO3(R_E); t_E] (rotation first),  cost = sum over edges of |e / sigma|^2,
+ *   retraction R <- R Exp(dw), t <- t + R dv,
+ * minimised from the given poses by Gauss-Newton steps with damping on a rejected step; each step's linear system by conjugate
+ * gradients preconditioned with the block-tridiagonal part of the matrix (block cyclic reduction).  All f64, and ONE kernel
+ * launch per call: nothing is read back between iterations.  Two calls on the same input give the same bits.
+ * Not restated: GPS / ENU factors and SolveGpsCorrdAlone, the odometry calibration factor, the Huber odometry model
+ * (isam_optimizer.cc:84-93), IMU, ViewGraph's picture output, the multi-trajectory optimiser. */
+#define SMHIP_POSE_GRAPH_MAX_NODES 8192
+#define SMHIP_POSE_GRAPH_MAX_EDGES 32768
+/* One launch runs at most this many conjugate-gradient iterations in all, whatever max_iterations and the per-solve cap allow, and
+ * then stops with MAX_ITERATIONS at the poses of its last accepted step.  The per-solve cap alone, 12 x (non-chain edges) + 64, is
+ * about 295 000 at the limits, times 50 steps: at the measured 0.2-0.3 ms per iteration that would hold the
+ * device for an hour.  With this bound the worst accepted graph takes about a minute; a 909-node drive with 60 loop edges needs
+ * 3 600 iterations, 0.65 s. */
+#define SMHIP_POSE_GRAPH_MAX_PCG_TOTAL 200000
+enum {
+  SMHIP_POSE_GRAPH_STOP_STEP = 1,            /* max |delta| < 1e-10 */
+  SMHIP_POSE_GRAPH_STOP_COST = 2,            /* a step lowered the cost by no more than 1e-12 of it */
+  SMHIP_POSE_GRAPH_STOP_MAX_ITERATIONS = 3,  /* max_iterations steps, or SMHIP_POSE_GRAPH_MAX_PCG_TOTAL iterations inside them */
+  SMHIP_POSE_GRAPH_STOP_DAMPING = 4,         /* every step up to lambda = 1e8 raised the cost */
+  SMHIP_POSE_GRAPH_STOP_NUMERIC = 5          /* a pivot of the preconditioner's factorisation was not positive, or a sum not finite */
+};
+typedef struct smhip_pose_graph_options {
+  int32_t max_iterations;       /* default 50: accepted and rejected steps together */
+  int32_t reserved[3];
+} smhip_pose_graph_options;
+typedef struct smhip_pose_graph_stats {
+  double initial_cost, final_cost;
+  double damping;               /* lambda after the last step (lowered after an accepted one, also the one that stops) */
+  int32_t stop_reason;          /* SMHIP_POSE_GRAPH_STOP_* */
+  int32_t iterations;           /* steps tried = accepted_steps + rejected_steps, <= max_iterations */
+  int32_t accepted_steps, rejected_steps;
+  int32_t pcg_iterations;       /* summed over the steps */
+  int32_t pcg_max_iterations;   /* the longest single solve, <= pcg_cap */
+  int32_t pcg_cap;              /* 12 x (edges with |i - j| != 1) + 64 */
+  int32_t levels;               /* of the cyclic reduction: the smallest L with 2^L >= n_nodes */
+} smhip_pose_graph_stats;
+void smhip_pose_graph_default_options(smhip_pose_graph_options* o);
+/* The host half of smhip_pose_graph_optimize, which needs no device and no handle: its refusals, and on SMHIP_OK the list node ->
+ * incident edges the kernel gathers in (csr_offsets: n_nodes + 1 words; csr_edges: 2 n_edges edge indices, ascending within a
+ * node; either may be NULL).  why: the reason of a refusal, at most why_len bytes with the terminator (may be NULL). */
+smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij,
+                                   const double* edge_Z, const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why,
+                                   int why_len);
+/* poses_inout: n_nodes column-major 4x4; fixed: n_nodes bytes, non-zero = held; edge_ij: n_edges pairs (i, j); edge_Z: n_edges
+ * column-major 4x4, the measured X_i^-1 X_j; edge_sigmas: 6 per edge, rotation first, or NULL for 0.1 x 3, 0.15 x 3
+ * (isam_optimizer.cc:80-83); opts: NULL = defaults; stats: may be NULL.  The poses of free nodes are replaced, those of fixed
+ * nodes are not written.  Device memory for the limits above is allocated at a handle's first call, nothing afterwards.
+ * Refused before anything is touched, the poses left as given --
+ *   SMHIP_ERR_INVALID_ARGUMENT: a null pointer, n_nodes < 1, an index out of range, i == j, a sigma that is not finite and positive,
+ *     a non-finite pose or Z, a rotation block further than 1e-6 from orthonormal (or a reflection), a free node without an edge,
+ *     a connected component without a fixed node, max_iterations < 1;
+ *   SMHIP_ERR_CAPACITY: more nodes or edges than the limits (decided from the sizes alone: nothing is read or launched).
+ * Found by the kernel, SMHIP_ERR_NO_MATCH afterwards with the poses left as given: stop_reason NUMERIC. */
+smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges,
+                                       const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas,
+                                       const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
+/* parity-test hook: the first linearisation of the last smhip_pose_graph_optimize on the handle (at the poses that call was given),
+ * computed again by one launch.  n_nodes, n_edges: what the caller's arrays are sized for; they must equal that call's sizes
+ * (SMHIP_ERR_INVALID_ARGUMENT otherwise, nothing written).  Any pointer may be NULL.  residuals: 6 per edge, whitened (e / sigma); A, B: 36 per edge,
+ * row-major, whitened; gradient: 6 per node (J^T r; zero for a fixed node); minv_v: M^-1 v for the caller's v (6 per node; entries
+ * of fixed nodes are ignored and come back as zero), M = the block-tridiagonal part of H = J^T J.  SMHIP_ERR_NOT_READY when no
+ * call got as far as the launch. */
+smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, double* residuals, double* A, double* B, double* gradient, const double* v, double* minv_v);
+
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one
  * InsertPointCloud per frame, builder/map_builder.cc:832-900), on the device.  Results equal the reference's insert loop

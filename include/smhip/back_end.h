@@ -12,7 +12,8 @@
 //       the distance gate, the descriptor gate (matchTwoM2dpDescriptors on the frames' M2DP descriptors, smhip/m2dp.h), the
 //       choice of candidate pairs, the five-state loop machine, CloseLoop per pair and CheckResult.  The candidate selection
 //       (SelectLoopCandidates), the state machine (NextLoopStatus) and CheckLoopResult are free functions that touch no device.
-// The scheduling around them (threads, pose graph) is host control plane and stays out.
+// The pose graph that consumes the detector's edges (IsamOptimizer) is smhip/pose_graph.h, over the device optimiser; the threads
+// the reference schedules all this on are host control plane and stay out.
 #ifndef SMHIP_BACK_END_H_
 #define SMHIP_BACK_END_H_
 

@@ -72,6 +72,7 @@ class Submap {
       local_poses_.push_back(back_end::Multiply(back_end::RigidInverse(global_pose_), global_pose));  // :87
     }
     frames_.push_back(cloud);
+    frame_global_poses_.push_back(global_pose);
     if (static_cast<int32_t>(frames_.size()) == options_.frame_count) full_ = true;                   // :94-96
   }
   bool Full() const { return full_; }
@@ -79,6 +80,15 @@ class Submap {
   const Matrix4d& LocalPose(int i) const { return local_poses_.at(static_cast<size_t>(i)); }
   // GetFrames()[0]->GlobalPose(), what SubmapPairMatch builds its guess from (map_builder.cc:426-428)
   const Matrix4d& FirstFramePose() const { return global_pose_; }
+  // Submap::GlobalPose / SetGlobalPose (what the pose graph reads and writes, isam_optimizer.cc:106-125) and
+  // UpdateInnerFramePose, submap.cc:268-274: every frame's global pose = submap pose * local pose.  Until it is called the frames
+  // keep the poses they were inserted with.
+  const Matrix4d& GlobalPose() const { return global_pose_; }
+  void SetGlobalPose(const Matrix4d& pose) { global_pose_ = pose; }
+  void UpdateInnerFramePose() {
+    for (size_t i = 0; i < frame_global_poses_.size(); ++i) frame_global_poses_[i] = back_end::Multiply(global_pose_, local_poses_[i]);
+  }
+  const Matrix4d& FrameGlobalPose(int i) const { return frame_global_poses_.at(static_cast<size_t>(i)); }
   const SubmapOptions& Options() const { return options_; }
   // rows of all frames together: what a handle must have room for
   int TotalPoints() const {
@@ -157,7 +167,7 @@ class Submap {
   bool full_ = false;
   Matrix4d global_pose_ = Matrix4d::Identity();
   std::vector<data::InnerCloudType::Ptr> frames_;
-  std::vector<Matrix4d> local_poses_;
+  std::vector<Matrix4d> local_poses_, frame_global_poses_;
   InnerCloudPtr cloud_;
   descriptor::M2dp::Descriptor descriptor_;
 };

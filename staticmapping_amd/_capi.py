@@ -90,6 +90,17 @@ class M2dpOptions(ctypes.Structure):
                 ("q", ctypes.c_int32)]
 
 
+class PoseGraphOptions(ctypes.Structure):
+    _fields_ = [("max_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class PoseGraphStats(ctypes.Structure):
+    _fields_ = [("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double), ("damping", ctypes.c_double),
+                ("stop_reason", ctypes.c_int32), ("iterations", ctypes.c_int32), ("accepted_steps", ctypes.c_int32),
+                ("rejected_steps", ctypes.c_int32), ("pcg_iterations", ctypes.c_int32), ("pcg_max_iterations", ctypes.c_int32),
+                ("pcg_cap", ctypes.c_int32), ("levels", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/smhip.h declares
 SIGNATURES = {
     "smhip_version": (ctypes.c_int, []),
@@ -183,6 +194,12 @@ SIGNATURES = {
     "smhip_m2dp_from_filter_output": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(M2dpOptions), c_float_p, ctypes.c_int]),
     "smhip_m2dp_last": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_int32_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_m2dp_match": (ctypes.c_double, [c_float_p, c_float_p, ctypes.c_int]),
+    "smhip_pose_graph_default_options": (None, [ctypes.POINTER(PoseGraphOptions)]),
+    "smhip_pose_graph_plan": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, c_int32_p, c_double_p, c_double_p,
+                                             c_int32_p, c_int32_p, ctypes.c_char_p, ctypes.c_int]),
+    "smhip_pose_graph_optimize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, c_int32_p,
+                                                 c_double_p, c_double_p, ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
+    "smhip_pose_graph_last": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -22,6 +22,12 @@
 // so the map is a function of that file: --map-poses FILE builds the same map, byte for byte, with no alignment, no RCCL and
 // one process -- also from poses that came from elsewhere.
 //
+// --close-loops PATH: the pose graph over those submaps (MapBuilder::ConnectAllSubmap, builder/map_builder.cc:448-613): every submap
+// with its device descriptor goes through back_end::IsamOptimizer (smhip/pose_graph.h: the loop detector, consecutive matches as
+// odometry factors, loop edges, one device solve per update), and the frames' corrected poses are written to PATH in the pose
+// writer's format, one line per frame -- so --map --map-poses PATH builds the corrected map.  The detector's settings are the
+// --loop-* flags (back_end/loop_detector_options.h:29-40).  Without the flag nothing of this runs and every output is what it was.
+//
 // --submap-edges PATH: the submaps of the sequence and the match of every pair of consecutive ones (Submap::InsertFrame,
 // builder/submap.cc:76-163; MapBuilder::SubmapPairMatch, builder/map_builder.cc:399-446).  Like --map, rank 0 works from the poses
 // AS WRITTEN to the pose file once the matchers are gone.  Frames [kN, (k + 1)N) form submap k (--submap-frames N); a trailing
@@ -59,6 +65,7 @@
 #include "../../include/smhip/kitti_scans.h"
 #include "../../include/smhip/pcd.h"
 #include "../../include/smhip/back_end.h"
+#include "../../include/smhip/pose_graph.h"
 
 namespace {
 
@@ -82,6 +89,10 @@ struct Args {
   std::string submap_edges;
   int submap_frames = 5;
   float submap_voxel = 0.1f, submap_min_score = 0.7f;
+  // --close-loops: the pose graph over those submaps; the detector's settings (back_end/loop_detector_options.h:29-40), with the
+  // descriptor gate on as in the shipped KITTI config
+  std::string close_loops;
+  smhip::back_end::LoopDetectorSettings loop = [] { smhip::back_end::LoopDetectorSettings s; s.use_descriptor = true; return s; }();
 };
 
 [[noreturn]] void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -149,12 +160,23 @@ Args Parse(int argc, char** argv) {
     else if (k == "--submap-frames") a.submap_frames = std::atoi(val().c_str());
     else if (k == "--submap-voxel") a.submap_voxel = static_cast<float>(std::atof(val().c_str()));
     else if (k == "--submap-min-score") a.submap_min_score = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--close-loops") a.close_loops = val();
+    else if (k == "--loop-ignore-threshold") a.loop.loop_ignore_threshold = std::atoi(val().c_str());
+    else if (k == "--loop-detect-count") a.loop.trying_detect_loop_count = std::atoi(val().c_str());
+    else if (k == "--loop-history") a.loop.nearest_history_pos_num = std::atoi(val().c_str());
+    else if (k == "--loop-max-distance") a.loop.max_close_loop_distance = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--loop-max-z") a.loop.max_close_loop_z_distance = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--loop-use-descriptor") a.loop.use_descriptor = std::atoi(val().c_str()) != 0;
+    else if (k == "--loop-m2dp-score") a.loop.m2dp_match_score = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--loop-accept-score") a.loop.accept_scan_match_score = static_cast<float>(std::atof(val().c_str()));
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
              "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
              "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
              "[--map-max-table-log2 28]\n"
-             "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]");
+             "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]\n"
+             "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
+             "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
   if (!a.map_poses.empty() && a.map_path.empty()) Die("--map-poses needs --map PATH");
@@ -164,6 +186,9 @@ Args Parse(int argc, char** argv) {
   if (a.submap_frames < 1 || !(a.submap_voxel >= 0.f) || !std::isfinite(a.submap_voxel))
     Die("bad submap setting (--submap-frames >= 1, --submap-voxel >= 0)");
   if (!a.submap_edges.empty() && !a.map_poses.empty()) Die("--submap-edges needs the alignment run (not --map-poses)");
+  if (!a.close_loops.empty() && !a.map_poses.empty()) Die("--close-loops needs the alignment run (not --map-poses)");
+  if (a.loop.nearest_history_pos_num < 1 || a.loop.loop_ignore_threshold < 0 || a.loop.trying_detect_loop_count < 1)
+    Die("bad loop setting (--loop-history >= 1, --loop-ignore-threshold >= 0, --loop-detect-count >= 1)");
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
   if (a.world < 0 && std::getenv("WORLD_SIZE")) a.world = std::atoi(std::getenv("WORLD_SIZE"));
   if (a.local_rank < 0 && std::getenv("LOCAL_RANK")) a.local_rank = std::atoi(std::getenv("LOCAL_RANK"));
@@ -459,6 +484,159 @@ int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files, int n
   return rc;
 }
 
+// ---- --close-loops ------------------------------------------------------------------------------------------------------------
+struct LoopResult { int submaps = 0, loop_edges = 0, solves = 0, stop_reason = 0; double seconds = 0.0, final_cost = 0.0, moved_m = 0.0; };
+
+std::string LoopJsonFields(const Args& a, const LoopResult& m) {
+  return Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
+             "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), m.submaps,
+             m.loop_edges, m.solves, m.stop_reason, m.final_cost, m.moved_m, m.seconds);
+}
+
+// MapBuilder::ConnectAllSubmap (builder/map_builder.cc:448-613) over the submaps --submap-edges builds, from the poses as written:
+// every submap is built on the device, described where it lies (M2DP), matched against the previous one (the odometry factor:
+// the match when its score reaches --submap-min-score, else the guess) and handed to back_end::IsamOptimizer -- the loop detector,
+// the factors, one device solve of the pose graph per update, every submap's pose written back.  A submap enters at the previous
+// submap's corrected pose times its odometry factor.  After RunFinalOptimazation the frames get submap pose x local pose
+// (Submap::UpdateInnerFramePose) and go to --close-loops in the pose writer's format, one line per frame of the sequence (the
+// frames of a trailing group that is not full ride on the last submap), so --map-poses on that file builds the corrected map.
+// Returns 0, or 3 when the device refused something (the file is then removed).
+int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, LoopResult* res) {
+  namespace be = smhip::back_end;
+  namespace bld = smhip::builder;
+  using smhip::registrator::Matrix4d;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;
+  res->submaps = S;
+  std::ofstream out(a.close_loops);
+  if (!out) Die("cannot write " + a.close_loops);
+  out.precision(8);
+  auto write_pose = [&out](const double* m) {                             // column-major in, the top 3 x 4 row by row out
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out << m[4 * c + r] << ((r == 2 && c == 3) ? "\n" : " ");
+  };
+  if (S < 1) {
+    for (int f = 0; f < n_frames; ++f) write_pose(poses[f].data());
+    res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+  }
+  long long cap = 16;
+  size_t max_bytes = 16;
+  for (int k = 0; k < S; ++k) {
+    long long rows = 0;
+    for (int f = k * N; f < (k + 1) * N; ++f) {
+      struct stat sb;
+      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+    }
+    cap = std::max(cap, rows);
+  }
+  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
+  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
+  smhip_handle h = nullptr;
+  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
+  if (st != SMHIP_OK) Die(std::string("smhip_create (loop closing): ") + smhip_status_string(st));
+  smhip_icp_options o;
+  smhip_icp_default_options(&o);
+  o.max_iteration = a.iterations;
+  o.early_exit = a.early_exit;
+  if (smhip_icp_set_options(h, &o) != SMHIP_OK) Die(smhip_last_error(h));
+  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
+  smhip_m2dp_options mo;
+  smhip_m2dp_default_options(&mo);
+  const int dlen = smhip_m2dp_length(&mo);
+
+  be::LoopDetectorSettings settings = a.loop;
+  settings.device = device;
+  int rc = 0;
+  {
+    be::IsamOptimizer optimizer(be::IsamOptimizerOptions(), settings, h);
+    std::vector<std::shared_ptr<bld::Submap>> maps;
+    std::vector<std::shared_ptr<be::LoopFrame>> frames;
+    bld::SubmapOptions so;
+    so.frame_count = N;
+    const smhip::data::InnerCloudType::Ptr no_points(new smhip::data::InnerCloudType);   // the Submap objects keep the poses' books only
+    std::vector<int> order(static_cast<size_t>(S) * N);
+    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
+    smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
+    for (int k = 0; k < S && rc == 0; ++k) {
+      std::vector<const float*> rows(N);
+      std::vector<int> n(N);
+      std::vector<double> local(16 * static_cast<size_t>(N));
+      maps.emplace_back(new bld::Submap(so));
+      for (int f = 0; f < N; ++f) {
+        int fi = -1;
+        rows[f] = scans.Next(&n[f], &fi);
+        if (!rows[f] || fi != k * N + f) Die("loop closing: prefetcher out of step");
+        if (n[f] < 0) Die("cannot read " + files[fi]);
+        Matrix4d P;
+        std::memcpy(P.data(), poses[k * N + f].data(), sizeof(double) * 16);
+        maps.back()->InsertFrame(no_points, P);
+        std::memcpy(&local[16 * static_cast<size_t>(f)], maps.back()->LocalPose(f).data(), sizeof(double) * 16);   // submap.cc:83-87
+      }
+      int m = 0;
+      st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
+      scans.ReleaseHeld();
+      if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+      std::shared_ptr<be::LoopFrame> frame(new be::LoopFrame);
+      frame->descriptor.resize(static_cast<size_t>(dlen));
+      if (smhip_m2dp_from_filter_output(h, &mo, frame->descriptor.data(), dlen) != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: descriptor of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break;
+      }
+      {   // the cloud CloseLoop matches (Submap::Cloud(): normals calculated, submap.cc:160-161)
+        std::vector<smhip::data::InnerPointType> pts(static_cast<size_t>(m));
+        if (smhip_filter_get_output(h, &pts[0].x, nullptr, m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+        frame->cloud.reset(new smhip::data::InnerPointCloudData(pts));
+        frame->cloud->CalculateNormals();
+      }
+      Matrix4d from_last = Matrix4d::Identity();
+      if (k > 0) {
+        // SubmapPairMatch(source = submap k, target = submap k - 1), map_builder.cc:399-446, as --submap-edges does it
+        if (smhip_filter_output_to_source(h, 0) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as source: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+        const Pose guess = MulPose(AffineInverse(poses[(k - 1) * N]), poses[k * N]);
+        double result[16], score = 0.0;
+        smhip_icp_stats stats;
+        st = smhip_icp_align(h, guess.data(), result, &score, &stats);
+        if (st != SMHIP_OK) score = 0.0;
+        Matrix4d T;
+        std::memcpy(T.data(), result, sizeof(result));
+        be::NormalizeRotation(T);
+        if (st == SMHIP_OK && score >= a.submap_min_score) from_last = T;
+        else std::memcpy(from_last.data(), guess.data(), sizeof(double) * 16);
+        frame->global_pose = be::Multiply(frames.back()->global_pose, from_last);
+      } else {
+        frame->global_pose = maps[0]->GlobalPose();
+      }
+      if (k + 1 < S && smhip_filter_output_to_target(h, 0, &m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+      frames.push_back(frame);
+      if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
+    }
+    if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
+    if (rc == 0) {
+      res->loop_edges = optimizer.LoopEdgeCount(); res->solves = optimizer.SolveCount();
+      res->stop_reason = optimizer.LastStats().stop_reason; res->final_cost = optimizer.LastStats().final_cost;
+      for (int k = 0; k < S; ++k) {
+        maps[k]->SetGlobalPose(frames[k]->global_pose);
+        maps[k]->UpdateInnerFramePose();                                   // map_builder.cc:598-601
+        for (int f = 0; f < N; ++f) {
+          const Matrix4d& G = maps[k]->FrameGlobalPose(f);
+          const Pose& was = poses[k * N + f];
+          res->moved_m = std::max(res->moved_m, std::sqrt((G(0, 3) - was[12]) * (G(0, 3) - was[12]) + (G(1, 3) - was[13]) * (G(1, 3) - was[13]) +
+                                                          (G(2, 3) - was[14]) * (G(2, 3) - was[14])));
+          write_pose(G.data());
+        }
+      }
+      Pose last;
+      std::memcpy(last.data(), frames.back()->global_pose.data(), sizeof(double) * 16);
+      const Pose carry = MulPose(last, AffineInverse(poses[(S - 1) * N]));
+      for (int f = S * N; f < n_frames; ++f) write_pose(MulPose(carry, poses[f]).data());
+    }
+  }
+  out.close();
+  smhip_destroy(h);
+  if (rc != 0) std::remove(a.close_loops.c_str());
+  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
 // --map-poses FILE: the map alone, one process, no alignment and no RCCL.  The pose file is checked before any GPU work: it needs
 // a pose for every frame the map inserts.
 int RunMapOnly(const Args& a) {
@@ -728,7 +906,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
                   "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
-      if (a.map_path.empty() && a.submap_edges.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
+      if (a.map_path.empty() && a.submap_edges.empty() && a.close_loops.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;
   }
@@ -737,7 +915,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
   if (pinned) for (float* b : ring_buffers) (void)hipHostFree(b);
   NCCLOK(ncclCommDestroy(comm));
   for (int k = 0; k < NH; ++k) (void)hipStreamDestroy(streams[k]);
-  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty())) {
+  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty() || !a.close_loops.empty())) {
     // the static map and the submap edges from the poses as written: the pose file read back (--map-poses on that file builds
     // the same map)
     std::string fields;
@@ -752,6 +930,11 @@ int RunRank(const Args& a, int rank, int world, int device) {
       SubmapResult m;
       rc = BuildSubmapEdges(a, files, n_pairs + 1, poses, device, &m);
       if (rc == 0) fields += SubmapJsonFields(a, m);
+    }
+    if (rc == 0 && !a.close_loops.empty()) {
+      LoopResult m;
+      rc = CloseLoops(a, files, n_pairs + 1, poses, device, &m);
+      if (rc == 0) fields += LoopJsonFields(a, m);
     }
     if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? fields.c_str() : "");
   }

@@ -632,6 +632,7 @@ smhip_status smhip_create(int device, void* stream, int pair_slots, int max_sour
 extern "C" void smhip_internal_free_ndt(smhip_context* h);
 extern "C" void smhip_internal_free_gicp(smhip_context* h);
 extern "C" void smhip_internal_free_m2dp(smhip_context* h);
+extern "C" void smhip_internal_free_pose_graph(smhip_context* h);
 
 smhip_status smhip_destroy(smhip_handle h) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
@@ -640,6 +641,7 @@ smhip_status smhip_destroy(smhip_handle h) {
   smhip_internal_free_ndt(h);
   smhip_internal_free_gicp(h);
   smhip_internal_free_m2dp(h);
+  smhip_internal_free_pose_graph(h);
   if (h->prep) prep_destroy(h->prep);
   if (h->prep_batch) prep_destroy(h->prep_batch);
   if (h->filt) filt_destroy(h->filt);

@@ -1,0 +1,245 @@
+// smhip_pose_graph.hip -- the pose-graph optimiser (what back_end::IsamOptimizer asks of GTSAM, back_end/isam_optimizer.{h,cc}) on
+// the device: the kernel and the C ABI.  The definition is DESIGN.md section 6 ("Pose graph"), restated in tests/pose_graph_ref.py.
+//
+// One optimisation is ONE launch of pose_graph_solve: one workgroup of 1024 threads runs every Gauss-Newton step, every
+// conjugate-gradient iteration and every level of the preconditioner's cyclic reduction, with __syncthreads as the only barrier
+// and nothing read back in between (pose_graph_kernel.h holds the loop; it also compiles for a CPU).  The work between two
+// barriers is a few thousand 6x6 block operations at most, so a grid-wide seam would cost more than what it separates.
+//   linearise     one thread per edge: e, the whitened A and B
+//   assemble      one thread per node, its edges in index order (the host's CSR list): Hkk, g, the chain block -- no atomics
+//   factor        block cyclic reduction of M = the block-tridiagonal part of H + lambda blockdiag(H): two barriers per level
+//   pcg           H p matrix-free (per edge, then per node), M^-1 by one sweep up and one down the levels, dot products as
+//                 per-thread partials folded by wave shuffles and then in wave order: two calls give the same bits
+// The refusals and the CSR list are made on the host (pose_graph_plan.h) before anything is touched.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "pose_graph_kernel.h"
+#include "pose_graph_plan.h"
+#include "smhip_context.h"
+
+using namespace smhip_host;
+namespace pg = smhip::pose_graph;
+
+namespace {
+
+constexpr int kPgThreads = 1024;
+
+struct BlockCtx {
+  double* part;                    // one slot per wave, in LDS
+  __device__ int tid() const { return (int)threadIdx.x; }
+  __device__ int nthreads() const { return kPgThreads; }
+  __device__ void sync() const { __syncthreads(); }
+  __device__ double sum(double v) const {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < kPgThreads / 64; ++w) t += part[w];
+    __syncthreads();
+    return t;
+  }
+  __device__ double max(double v) const {
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = part[0];
+    for (int w = 1; w < kPgThreads / 64; ++w) t = fmax(t, part[w]);
+    __syncthreads();
+    return t;
+  }
+};
+
+__global__ __launch_bounds__(kPgThreads) void pose_graph_solve(const pg::Dev d) {
+  __shared__ double s_part[kPgThreads / 64];
+  BlockCtx c{s_part};
+  pg::run(d, c);
+}
+
+// doubles and words of the device state per node / per edge, and of the staging the host fills
+constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6;
+constexpr int kNodeI = 2, kEdgeI = 4;           // fixed, csr_off (+1); ij, csr_edge
+
+}  // namespace
+
+struct smhip_pose_graph_state {
+  double* dbl = nullptr;           // device
+  int32_t* ints = nullptr;
+  pg::Dev dev{};
+  std::vector<double> host_d;      // staging, sized once
+  std::vector<int32_t> host_i;
+  pg::Plan plan;
+  int last_n = -1, last_m = 0;     // what smhip_pose_graph_last can run again (-1: nothing)
+};
+
+namespace {
+
+smhip_status pg_ensure(smhip_context* h) {
+  if (h->pose_graph) return SMHIP_OK;
+  auto* st = new smhip_pose_graph_state;
+  const size_t N = pg::kMaxNodes, M = pg::kMaxEdges;
+  const size_t nd = N * kNodeD + M * kEdgeD + pg::kOutDoubles, ni = N * kNodeI + 1 + M * kEdgeI + pg::kOutInts;
+  smhip_status s = dev_alloc(h, &st->dbl, nd);
+  if (!s) s = dev_alloc(h, &st->ints, ni);
+  if (s) { delete st; return s; }
+  double* p = st->dbl;
+  auto take = [&p](size_t count) { double* r = p; p += count; return r; };
+  pg::Dev& d = st->dev;
+  // (what the host uploads: pose0, Z, sinv; v for the probe)
+  d.pose0 = take(12 * N); d.Z = take(12 * M); d.sinv = take(6 * M);
+  d.v = take(6 * N); d.minv = take(6 * N);
+  d.cur = take(12 * N); d.cand = take(12 * N);
+  d.Hkk = take(36 * N); d.C = take(36 * N); d.D = take(36 * N); d.U = take(36 * N); d.Dinv = take(36 * N); d.Wm = take(36 * N); d.Wp = take(36 * N);
+  d.g = take(6 * N); d.x = take(6 * N); d.r = take(6 * N); d.z = take(6 * N); d.p = take(6 * N); d.q = take(6 * N); d.b = take(6 * N);
+  d.A = take(36 * M); d.B = take(36 * M); d.rw = take(6 * M); d.u = take(6 * M);
+  d.out_d = take(pg::kOutDoubles);
+  int32_t* q = st->ints;
+  auto takei = [&q](size_t count) { int32_t* r = q; q += count; return r; };
+  // (uploaded: fixed, csr_off, ij, csr_edge)
+  d.fixed = takei(N); d.csr_off = takei(N + 1); d.ij = takei(2 * M); d.csr_edge = takei(2 * M);
+  d.out_i = takei(pg::kOutInts);
+  st->host_d.resize(12 * N + 12 * M + 6 * M);
+  st->host_i.resize(N + (N + 1) + 2 * M + 2 * M);
+  h->pose_graph = st;
+  return SMHIP_OK;
+}
+
+// column-major 4x4 -> 12 doubles, the rotation row-major then the translation
+void pack12(const double* m, double* o) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) o[3 * r + c] = m[4 * c + r];
+    o[9 + r] = m[12 + r];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void smhip_internal_free_pose_graph(smhip_context* h) {
+  delete h->pose_graph;            // (the device arrays are among the handle's allocations)
+  h->pose_graph = nullptr;
+}
+
+void smhip_pose_graph_default_options(smhip_pose_graph_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->max_iterations = 50;
+}
+
+smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
+                                   const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  pg::Plan plan;
+  std::string text;
+  const smhip_status s = pg::check_and_plan(n_nodes, poses, fixed, n_edges, edge_ij, edge_Z, edge_sigmas, &plan, &text);
+  if (why && why_len > 0) { std::strncpy(why, text.c_str(), (size_t)why_len - 1); why[why_len - 1] = '\0'; }
+  if (s) return s;
+  if (csr_offsets) std::memcpy(csr_offsets, plan.csr_offsets.data(), sizeof(int32_t) * plan.csr_offsets.size());
+  if (csr_edges && n_edges > 0) std::memcpy(csr_edges, plan.csr_edges.data(), sizeof(int32_t) * plan.csr_edges.size());
+  return SMHIP_OK;
+}
+
+smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const int32_t* edge_ij,
+                                       const double* edge_Z, const double* edge_sigmas, const smhip_pose_graph_options* opts,
+                                       smhip_pose_graph_stats* stats) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  smhip_pose_graph_options o;
+  smhip_pose_graph_default_options(&o);
+  if (opts) o = *opts;
+  if (o.max_iterations < 1) { h->err = "pose graph: max_iterations must be at least 1"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  pg::Plan plan;
+  if (const smhip_status s = pg::check_and_plan(n_nodes, poses_inout, fixed, n_edges, edge_ij, edge_Z, edge_sigmas, &plan, &h->err)) return s;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const smhip_status s = pg_ensure(h)) return s;
+  smhip_pose_graph_state* st = h->pose_graph;
+  st->last_n = -1;
+  st->plan = plan;
+  const size_t N = pg::kMaxNodes, M = pg::kMaxEdges;
+  double* hd = st->host_d.data();
+  for (int k = 0; k < n_nodes; ++k) pack12(poses_inout + 16 * (size_t)k, hd + 12 * (size_t)k);
+  for (int e = 0; e < n_edges; ++e) {
+    pack12(edge_Z + 16 * (size_t)e, hd + 12 * N + 12 * (size_t)e);
+    for (int c = 0; c < 6; ++c) hd[12 * N + 12 * M + 6 * (size_t)e + c] = 1.0 / (edge_sigmas ? edge_sigmas[6 * (size_t)e + c] : pg::kDefaultSigmas[c]);
+  }
+  int32_t* hi = st->host_i.data();
+  for (int k = 0; k < n_nodes; ++k) hi[k] = fixed[k] ? 1 : 0;
+  std::memcpy(hi + N, plan.csr_offsets.data(), sizeof(int32_t) * ((size_t)n_nodes + 1));
+  if (n_edges > 0) {
+    std::memcpy(hi + N + N + 1, edge_ij, sizeof(int32_t) * 2 * (size_t)n_edges);
+    std::memcpy(hi + N + N + 1 + 2 * M, plan.csr_edges.data(), sizeof(int32_t) * 2 * (size_t)n_edges);
+  }
+  hipStream_t s = h->stream;
+  pg::Dev d = st->dev;
+  d.n = n_nodes; d.m = n_edges; d.max_it = o.max_iterations; d.pcg_cap = plan.pcg_cap; d.pcg_budget = SMHIP_POSE_GRAPH_MAX_PCG_TOTAL; d.probe = 0;
+  HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.pose0), hd, sizeof(double) * 12 * (size_t)n_nodes, hipMemcpyHostToDevice, s));
+  if (n_edges > 0) {
+    HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.Z), hd + 12 * N, sizeof(double) * 12 * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.sinv), hd + 12 * N + 12 * M, sizeof(double) * 6 * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.ij), hi + N + N + 1, sizeof(int32_t) * 2 * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.csr_edge), hi + N + N + 1 + 2 * M, sizeof(int32_t) * 2 * (size_t)n_edges, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.fixed), hi, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.csr_off), hi + N, sizeof(int32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
+  HIPCHK(h, hipGetLastError());
+  double out_d[pg::kOutDoubles];
+  int32_t out_i[pg::kOutInts];
+  HIPCHK(h, hipMemcpyAsync(hd, d.cur, sizeof(double) * 12 * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(out_d, d.out_d, sizeof(out_d), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(out_i, d.out_i, sizeof(out_i), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  st->last_n = n_nodes; st->last_m = n_edges;
+  if (stats) {
+    stats->initial_cost = out_d[pg::kOutInitial]; stats->final_cost = out_d[pg::kOutFinal]; stats->damping = out_d[pg::kOutLambda];
+    stats->stop_reason = out_i[pg::kOutStop]; stats->iterations = out_i[pg::kOutIterations];
+    stats->accepted_steps = out_i[pg::kOutAccepted]; stats->rejected_steps = out_i[pg::kOutRejected];
+    stats->pcg_iterations = out_i[pg::kOutPcg]; stats->pcg_max_iterations = out_i[pg::kOutPcgMax];
+    stats->pcg_cap = plan.pcg_cap; stats->levels = plan.levels;
+  }
+  if (out_i[pg::kOutStop] == SMHIP_POSE_GRAPH_STOP_NUMERIC) {
+    h->err = "pose graph: a pivot of the preconditioner's factorisation was not positive, or a sum was not finite; the poses are left as given";
+    return SMHIP_ERR_NO_MATCH;
+  }
+  for (int k = 0; k < n_nodes; ++k) {
+    if (fixed[k]) continue;
+    const double* p = hd + 12 * (size_t)k;
+    double* m = poses_inout + 16 * (size_t)k;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) m[4 * c + r] = p[3 * r + c];
+      m[12 + r] = p[9 + r];
+      m[4 * r + 3] = 0.0;
+    }
+    m[15] = 1.0;
+  }
+  return SMHIP_OK;
+}
+
+smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, double* residuals, double* A, double* B, double* gradient, const double* v, double* minv_v) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  smhip_pose_graph_state* st = h->pose_graph;
+  if (!st || st->last_n < 0) { h->err = "pose graph: no optimisation has been launched on this handle"; return SMHIP_ERR_NOT_READY; }
+  if (n_nodes != st->last_n || n_edges != st->last_m) {
+    h->err = "pose graph: the last optimisation had " + std::to_string(st->last_n) + " nodes and " + std::to_string(st->last_m) + " edges, not the sizes given";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  if (minv_v && !v) { h->err = "pose graph: minv_v needs v"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const int n = st->last_n, m = st->last_m;
+  hipStream_t s = h->stream;
+  pg::Dev d = st->dev;
+  d.n = n; d.m = m; d.max_it = 0; d.pcg_cap = 0; d.probe = 1;
+  if (v) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.v), v, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, s));
+  else HIPCHK(h, hipMemsetAsync(const_cast<double*>(d.v), 0, sizeof(double) * 6 * (size_t)n, s));
+  hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
+  HIPCHK(h, hipGetLastError());
+  if (residuals && m > 0) HIPCHK(h, hipMemcpyAsync(residuals, d.rw, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (A && m > 0) HIPCHK(h, hipMemcpyAsync(A, d.A, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (B && m > 0) HIPCHK(h, hipMemcpyAsync(B, d.B, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (gradient) HIPCHK(h, hipMemcpyAsync(gradient, d.g, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (minv_v) HIPCHK(h, hipMemcpyAsync(minv_v, d.minv, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return SMHIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,94 @@
+"""ctypes view of the device pose-graph optimiser (include/smhip.h, `smhip_pose_graph_*`): what back_end::IsamOptimizer asks of GTSAM
+in the reference (back_end/isam_optimizer.{h,cc}) -- rigid poses, between-factors, fixed nodes -- as one kernel launch per
+optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _capi
+
+MAX_NODES, MAX_EDGES = 8192, 32768
+STOP_REASONS = {1: "step", 2: "cost", 3: "max_iterations", 4: "damping", 5: "numeric"}
+c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
+
+
+class PoseGraphRefused(ValueError):
+    """smhip_pose_graph_plan refused the graph; .status is the smhip_status"""
+
+    def __init__(self, status, text):
+        super().__init__(text)
+        self.status = status
+
+
+def _arrays(poses, fixed, edges, Z, sigmas):
+    poses = np.asarray(poses, np.float64)
+    n = len(poses)
+    edges = np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1, 2))
+    Z = np.asarray(Z, np.float64).reshape(-1, 4, 4)
+    if poses.shape[1:] != (4, 4) or len(Z) != len(edges):
+        raise ValueError("poses [N, 4, 4], edges [E, 2], Z [E, 4, 4]")
+    if fixed is None:
+        fixed = np.zeros(n, np.uint8)
+        fixed[:1] = 1
+    fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8))
+    if len(fixed) != n:
+        raise ValueError("one fixed flag per pose")
+    if sigmas is not None:
+        sigmas = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas, np.float64), (len(edges), 6)))
+    # the ABI's 4x4 are column-major: the transpose of numpy's rows
+    return (np.ascontiguousarray(poses.transpose(0, 2, 1)), fixed, edges, np.ascontiguousarray(Z.transpose(0, 2, 1)), sigmas)
+
+
+def _ptr(a, kind):
+    return None if a is None or a.size == 0 else a.ctypes.data_as(kind)
+
+
+def plan(poses, edges, Z, fixed=None, sigmas=None):
+    """The host half of optimize(), which needs no device: (csr_offsets [N + 1], csr_edges [2 E]) -- node k's edges, ascending, at
+    csr_edges[csr_offsets[k]:csr_offsets[k + 1]] -- or PoseGraphRefused with the reason."""
+    P, F, E, Zc, S = _arrays(poses, fixed, edges, Z, sigmas)
+    off = np.zeros(len(P) + 1, np.int32)
+    inc = np.zeros(max(2 * len(E), 1), np.int32)
+    why = ctypes.create_string_buffer(256)
+    s = _capi.load_library().smhip_pose_graph_plan(len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(E, _capi.c_int32_p),
+                                                   _ptr(Zc, _capi.c_double_p), _ptr(S, _capi.c_double_p), off.ctypes.data_as(_capi.c_int32_p),
+                                                   inc.ctypes.data_as(_capi.c_int32_p), why, len(why))
+    if s != 0:
+        raise PoseGraphRefused(s, why.value.decode())
+    return off, inc[:2 * len(E)]
+
+
+def optimize(matcher, poses, edges, Z, fixed=None, sigmas=None, max_iterations: int | None = None):
+    """Minimise sum |e / sigma|^2 over the free poses from `poses` ([N, 4, 4]); edges [E, 2] of (i, j) with Z [E, 4, 4] the measured
+    X_i^-1 X_j; fixed: N flags (default: node 0 alone); sigmas: [6] or [E, 6], rotation first (default 0.1 x 3, 0.15 x 3).
+    Returns (poses [N, 4, 4], stats dict).  `matcher`: any handle owner of this package (e.g. IcpFastHip)."""
+    P, F, E, Zc, S = _arrays(poses, fixed, edges, Z, sigmas)
+    lib = matcher._lib
+    o = _capi.PoseGraphOptions()
+    lib.smhip_pose_graph_default_options(ctypes.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = max_iterations
+    st = _capi.PoseGraphStats()
+    matcher._check(lib.smhip_pose_graph_optimize(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(E, _capi.c_int32_p),
+                                                 _ptr(Zc, _capi.c_double_p), _ptr(S, _capi.c_double_p), ctypes.byref(o), ctypes.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
+    stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
+
+
+def last(matcher, n_nodes: int, n_edges: int, v=None):
+    """Parity hook: the first linearisation of the last optimize() on the handle, which had n_nodes and n_edges (other sizes are refused).  Returns dict(r [E, 6]
+    whitened residuals, A, B [E, 6, 6] whitened, g [N, 6], minv_v [N, 6] = M^-1 v or None without v)."""
+    r = np.zeros((n_edges, 6))
+    A = np.zeros((n_edges, 6, 6))
+    B = np.zeros((n_edges, 6, 6))
+    g = np.zeros((n_nodes, 6))
+    out = None
+    if v is not None:
+        v = np.ascontiguousarray(np.asarray(v, np.float64).reshape(n_nodes, 6))
+        out = np.zeros((n_nodes, 6))
+    matcher._check(matcher._lib.smhip_pose_graph_last(matcher._h, n_nodes, n_edges, _ptr(r, _capi.c_double_p), _ptr(A, _capi.c_double_p), _ptr(B, _capi.c_double_p),
+                                                      _ptr(g, _capi.c_double_p), _ptr(v, _capi.c_double_p), _ptr(out, _capi.c_double_p)))
+    return dict(r=r, A=A, B=B, g=g, minv_v=out)

@@ -1,0 +1,76 @@
+"""Time of one device pose-graph optimisation (smhip_pose_graph_optimize: one kernel launch) at the size of a KITTI-00 run: a
+circle drive of 909 submaps (tests/pose_graph_ref.py circle_drive), once overlapping its start by 4 submaps with 3 loop edges and once by 64 with 60, from the
+chained odometry.  Median of --repeats calls after --warmup calls, a host clock around calls that end in a synchronise (the call uploads
+the graph, launches, and copies the poses back).  Beside it, as the yardstick on the same box, the restatement with scipy's sparse
+direct solve: its whole time (the linearisation there is a Python loop) and the time inside the sparse solves alone.
+One JSON line on stdout (and in --out when given)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+N_NODES = 909
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-restatement", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    try:
+        import torch  # noqa: F401   (one HIP runtime per process: torch's first, as in tests/conftest.py)
+    except ImportError:
+        pass
+    import pose_graph_ref as ref
+    import staticmapping_amd as sm
+    from staticmapping_amd import pose_graph
+    m = sm.IcpFastHip(pair_slots=1, max_source_points=1024, max_target_points=1024)
+    res = {"nodes": N_NODES, "repeats": a.repeats, "warmup": a.warmup, "cases": []}
+    for n_loops in (3, 60):
+        # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
+        g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
+
+        def call():
+            return pose_graph.optimize(m, g["poses"], g["edges"], g["Z"], fixed=g["fixed"])
+        for _ in range(a.warmup):
+            call()
+        t = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            poses, stats = call()
+            t.append(time.perf_counter() - t0)
+        case = {"loop_edges": n_loops, "edges": int(len(g["edges"])), "device_median_ms": round(float(np.median(t)) * 1e3, 4),
+                "device_min_ms": round(float(np.min(t)) * 1e3, 4), "outer_steps": stats["iterations"], "rejected_steps": stats["rejected_steps"],
+                "pcg_iterations": stats["pcg_iterations"], "pcg_longest_solve": stats["pcg_max_iterations"], "pcg_cap": stats["pcg_cap"],
+                "levels": stats["levels"], "stop": stats["stop"], "initial_cost": stats["initial_cost"], "final_cost": stats["final_cost"]}
+        # barriers of one launch: per M^-1 application 2 levels + 2, per factorisation 2 levels + 2, per PCG iteration that plus H p (2),
+        # two dot products (2 each) and two vector updates
+        case["barriers_per_minv"] = 2 * stats["levels"] + 2
+        if not a.no_restatement:
+            t0 = time.perf_counter()
+            want, st = ref.optimize(g["poses"], g["fixed"], g["edges"], g["Z"], solver="sparse")
+            case["restatement_sparse_total_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            case["restatement_sparse_solves_ms"] = round(st.get("solve_seconds", 0.0) * 1e3, 1)
+            case["restatement_steps"] = st["accepted"] + st["rejected"]
+            case["difference_m"] = float(np.abs(poses[:, :3, 3] - want[:, :3, 3]).max())
+        res["cases"].append(case)
+    m.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
