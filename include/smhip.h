@@ -715,6 +715,44 @@ smhip_status smhip_mrvm_output_ex(smhip_mrvm_handle h, float threshold, int flag
 smhip_status smhip_mrvm_dump(smhip_mrvm_handle h, int32_t* keys3, uint8_t* prob, int32_t* max_intensity, int32_t* npoints, float* points5,
                              int capacity, int* n_out);
 
+/* ---- the map package (SaveTrajectoriesAsMapPackage, builder/map_package.{h,cc}) ----------
+ * The static map cut into overlapping square pieces: three calls on a voxel map that a piece's map is built and cut with, and
+ * the host-only plan of the pieces.  include/smhip/map_package.h drives them and writes the files. */
+/* smhip_mrvm_insert_transformed_f32 of the rows whose TRANSFORMED x, y lie in the closed box [bb_min, bb_max] (map_package.cc:
+ * 169-179): the float coordinates widened to double against the double bounds, so a NaN coordinate fails; the rows kept stay in
+ * their order (a scan of the keep flags places them, no atomic) and the insert runs over exactly those.  The transform's
+ * arithmetic is smhip_mrvm_insert_transformed_f32's; the origin is the pose's translation cast to float.  n_kept (may be NULL):
+ * the rows kept.  None kept: SMHIP_OK, the map bit for bit as it was (the reference makes no insert then, :177-180).  Refused before
+ * the map is touched: everything smhip_mrvm_insert_transformed_f32 refuses, and a bound that is not finite. */
+smhip_status smhip_mrvm_insert_transformed_clipped_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                                       float intensity_scale, const double bb_min[2], const double bb_max[2], int* n_kept);
+/* smhip_mrvm_output_ex's SORTED rows (flags: SMHIP_MRVM_AVERAGE and SMHIP_MRVM_RGB; SORTED is implied) of which only those inside
+ * the closed box are written, recentred: x <- float(double(x) - centre[0]), the same for y (map_package.cc:191-197).  The test is on
+ * the output row -- with AVERAGE on the averaged row, not on the stored points.  capacity = 0 only counts.  Refused: a bound or a
+ * centre that is not finite. */
+smhip_status smhip_mrvm_output_clipped(smhip_mrvm_handle h, float threshold, int flags, const double bb_min[2], const double bb_max[2],
+                                       const double centre[2], float* rows, int capacity, int* n_out);
+/* Empties the map by a kernel; the table keeps its current size (a handle reused for the next piece allocates nothing). */
+smhip_status smhip_mrvm_clear(smhip_mrvm_handle h);
+typedef struct smhip_map_package_options {
+  double border_offset;          /* 100: widens the extent, and a piece's box when its submaps are chosen */
+  double piece_width;            /* 500: pieces are piece_width wide and piece_width / 2 apart */
+  int32_t reserved[4];
+} smhip_map_package_options;
+void smhip_map_package_default_options(smhip_map_package_options* o);
+#define SMHIP_MAP_PACKAGE_MAX_PIECES 65536
+/* The plan (map_package.cc:59-141), on the host: needs no device and no handle.  translations: n_submaps x 3 doubles (x y z of
+ * every submap's global pose, in trajectory order).  steps: x_steps, y_steps; piece (x, y) is entry x * y_steps + y of centres
+ * (2 doubles), boxes (min x, min y, max x, max y) and member_offsets (pieces + 1 words into members, the submaps a piece is
+ * built from, ascending).  n_members: the length of members.  The arrays are filled when piece_capacity >= pieces (members when
+ * member_capacity >= n_members as well); with smaller capacities the call only counts.  Any output pointer but steps may be NULL.
+ * SMHIP_ERR_INVALID_ARGUMENT, the reason in why (at most why_len bytes with the terminator; may be NULL): a negative step count
+ * (the reference's refusal), and, not the reference's: no submap, a translation or border_offset that is not finite, a piece_width
+ * that is not finite and positive, more than SMHIP_MAP_PACKAGE_MAX_PIECES pieces. */
+smhip_status smhip_map_package_plan(int n_submaps, const double* translations, const smhip_map_package_options* opts, int32_t steps[2],
+                                    int piece_capacity, double* centres, double* boxes, int32_t* member_offsets, int member_capacity,
+                                    int32_t* members, int32_t* n_members, char* why, int why_len);
+
 /* ---- profiling ----------------------------------------------------------- */
 /* enable: 0 off, 1 events around every launch; events around ONE kernel class only, cheap enough to leave on inside a timed
  * region: 2 the NN kernels proper (fused search / full walk, certificate pass), 3 accumulate, 4 the listed search */

@@ -14,3 +14,4 @@ from .mrvm import MultiResolutionVoxelMapHip  # noqa: F401
 from .submap import SubmapBuilder, build_submap, output_to_target  # noqa: F401
 from . import m2dp  # noqa: F401
 from . import pose_graph  # noqa: F401
+from . import map_package  # noqa: F401

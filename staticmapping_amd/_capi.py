@@ -90,6 +90,10 @@ class M2dpOptions(ctypes.Structure):
                 ("q", ctypes.c_int32)]
 
 
+class MapPackageOptions(ctypes.Structure):
+    _fields_ = [("border_offset", ctypes.c_double), ("piece_width", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
+
+
 class PoseGraphOptions(ctypes.Structure):
     _fields_ = [("max_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
@@ -214,6 +218,14 @@ SIGNATURES = {
     "smhip_mrvm_output_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, c_float_p, ctypes.c_int, c_int32_p]),
     "smhip_mrvm_last_skipped": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "smhip_mrvm_dump": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_int32_p, c_float_p, ctypes.c_int, c_int32_p]),
+    "smhip_mrvm_insert_transformed_clipped_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_float,
+                                                                 c_double_p, c_double_p, c_int32_p]),
+    "smhip_mrvm_output_clipped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_float_p,
+                                                 ctypes.c_int, c_int32_p]),
+    "smhip_mrvm_clear": (ctypes.c_int, [ctypes.c_void_p]),
+    "smhip_map_package_default_options": (None, [ctypes.POINTER(MapPackageOptions)]),
+    "smhip_map_package_plan": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.POINTER(MapPackageOptions), c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                              c_int32_p, ctypes.c_int, c_int32_p, c_int32_p, ctypes.c_char_p, ctypes.c_int]),
     "smhip_icp_enable_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "smhip_icp_get_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IcpProfile)]),
     "smhip_icp_get_search_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),

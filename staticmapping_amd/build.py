@@ -21,7 +21,7 @@ FLAGS_STAMP = os.path.join(OBJ_DIR, "flags.txt")          # the compile flags th
 
 # translation units, slowest first (each #includes its kernel files and fragments: its dependency file lists them)
 UNITS = ["smhip_api.hip", "smhip_mrvm.hip", "cloud_filters.hip", "prep_normals.hip", "smhip_ndt_gicp.hip", "smhip_filter_api.hip", "smhip_m2dp.hip",
-         "smhip_submap.hip", "smhip_pose_graph.hip", "host_cloud.cc"]
+         "smhip_submap.hip", "smhip_pose_graph.hip", "host_cloud.cc", "map_package.cc"]
 
 
 def _hipcc() -> str:
@@ -66,7 +66,7 @@ def build_shard_driver(force: bool = False, verbose: bool = False) -> str:
     src = os.path.join(CSRC, "shard_driver.cc")
     deps = [src, os.path.join(ROOT, "include", "smhip.h"), os.path.join(ROOT, "include", "smhip", "kitti_scans.h"),
             os.path.join(ROOT, "include", "smhip", "pcd.h"), os.path.join(ROOT, "include", "smhip", "back_end.h"), os.path.join(ROOT, "include", "smhip", "pose_graph.h"),
-            os.path.join(ROOT, "include", "smhip", "submap.h"),
+            os.path.join(ROOT, "include", "smhip", "submap.h"), os.path.join(ROOT, "include", "smhip", "map_package.h"),
             os.path.join(ROOT, "include", "smhip", "registrator.h"), LIB_PATH]
     if not force and os.path.exists(SHARD_EXE) and all(os.path.getmtime(d) <= os.path.getmtime(SHARD_EXE) for d in deps):
         return SHARD_EXE

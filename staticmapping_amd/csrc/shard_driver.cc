@@ -28,6 +28,13 @@
 // writer's format, one line per frame -- so --map --map-poses PATH builds the corrected map.  The detector's settings are the
 // --loop-* flags (back_end/loop_detector_options.h:29-40).  Without the flag nothing of this runs and every output is what it was.
 //
+// --map-package DIR: the map package of MapBuilder::SaveMapPackage (builder/map_builder.cc:816-823, builder/map_package.cc): the
+// static map cut into overlapping square pieces, DIR/<prefix><x>_<y>.pcd centred on the piece and DIR/map_package.xml listing them
+// (smhip/map_package.h).  Like --map it is a function of the pose file as written, so --map-poses FILE builds it too -- also from the
+// file --close-loops wrote.  Frames [kN, (k + 1)N) form submap k (--submap-frames N; a trailing group that is not full is dropped),
+// built once on the device at --submap-voxel with local poses first^-1 * frame; its global pose is its first frame's.  The pieces'
+// voxel maps take the --map-* settings.
+//
 // --submap-edges PATH: the submaps of the sequence and the match of every pair of consecutive ones (Submap::InsertFrame,
 // builder/submap.cc:76-163; MapBuilder::SubmapPairMatch, builder/map_builder.cc:399-446).  Like --map, rank 0 works from the poses
 // AS WRITTEN to the pose file once the matchers are gone.  Frames [kN, (k + 1)N) form submap k (--submap-frames N); a trailing
@@ -66,6 +73,7 @@
 #include "../../include/smhip/pcd.h"
 #include "../../include/smhip/back_end.h"
 #include "../../include/smhip/pose_graph.h"
+#include "../../include/smhip/map_package.h"
 
 namespace {
 
@@ -85,6 +93,9 @@ struct Args {
   int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
   float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
   bool map_average = false, map_rgb = false;
+  // the map package (--map-package); defaults: MapPackageOptions, builder/map_package.h:36-41
+  std::string map_package;
+  smhip::MapPackageOptions package;
   // consecutive submaps (--submap-edges); defaults: builder/submap_options.h:30-38 and accepted_min_score of the configs
   std::string submap_edges;
   int submap_frames = 5;
@@ -156,6 +167,11 @@ Args Parse(int argc, char** argv) {
     else if (k == "--map-average") a.map_average = true;
     else if (k == "--map-rgb") a.map_rgb = true;
     else if (k == "--map-max-table-log2") a.map_max_table_log2 = std::atoi(val().c_str());
+    else if (k == "--map-package") a.map_package = val();
+    else if (k == "--package-piece-width") a.package.piece_width = std::atof(val().c_str());
+    else if (k == "--package-border-offset") a.package.border_offset = std::atof(val().c_str());
+    else if (k == "--package-prefix") a.package.cloud_file_prefix = val();
+    else if (k == "--package-descript") a.package.descript_filename = val();
     else if (k == "--submap-edges") a.submap_edges = val();
     else if (k == "--submap-frames") a.submap_frames = std::atoi(val().c_str());
     else if (k == "--submap-voxel") a.submap_voxel = static_cast<float>(std::atof(val().c_str()));
@@ -174,12 +190,18 @@ Args Parse(int argc, char** argv) {
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
              "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
              "[--map-max-table-log2 28]\n"
+             "  map package: [--map-package DIR (from the poses as written, or --map-poses; submaps of --submap-frames frames at --submap-voxel, a "
+             "trailing group that is not full is dropped; the pieces' maps take the --map-* settings)] [--package-piece-width 500] "
+             "[--package-border-offset 100] [--package-prefix part_] [--package-descript map_package.xml]\n"
              "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]\n"
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
              "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
-  if (!a.map_poses.empty() && a.map_path.empty()) Die("--map-poses needs --map PATH");
+  if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
+  if (!a.map_package.empty() && (!std::isfinite(a.package.piece_width) || !(a.package.piece_width > 0.0) || !std::isfinite(a.package.border_offset) ||
+                                 a.package.descript_filename.empty()))
+    Die("bad package setting (--package-piece-width finite and > 0, --package-border-offset finite, --package-descript not empty)");
   if (a.map_every < 1 || a.map_part_every < 0 || a.map_points_per_cell < 1 || a.map_max_table_log2 < 10 || a.map_max_table_log2 > 28 ||
       !(a.map_resolution > 0.f))
     Die("bad map setting (--map-every >= 1, --map-part-every >= 0, --map-points-per-cell >= 1, --map-max-table-log2 10..28, --map-resolution > 0)");
@@ -484,6 +506,96 @@ int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files, int n
   return rc;
 }
 
+// ---- --map-package ----------------------------------------------------------------------------------------------------------
+struct PackageResult { int pieces = 0, submaps = 0; long long points = 0; double seconds = 0.0; };
+
+std::string PackageJsonFields(const Args& a, const PackageResult& m) {
+  return Fmt(", \"package_dir\": \"%s\", \"package_pieces\": %d, \"package_submaps\": %d, \"package_points\": %lld, \"package_seconds\": %.4f",
+             a.map_package.c_str(), m.pieces, m.submaps, m.points, m.seconds);
+}
+
+// The submaps of frames [0, n_frames) under `poses`, each built once on the device and downloaded, then
+// smhip::SaveTrajectoriesAsMapPackage over them.  The plan is made from the poses alone before any device work: a refused plan ends
+// the run with 2, and so does a directory the description cannot be written into.  Returns 0, or 3 when the device refused a submap or
+// an insert or a piece could not be written (this run's files are then removed).
+int BuildMapPackage(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, PackageResult* res) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
+  if (S < 1) Die("--map-package: " + std::to_string(n_frames) + " frames hold no full submap of " + std::to_string(N));
+  {
+    std::vector<std::array<double, 3>> translations(static_cast<size_t>(S));
+    for (int k = 0; k < S; ++k) translations[k] = {poses[k * N][12], poses[k * N][13], poses[k * N][14]};
+    smhip::MapPackagePlan plan;
+    std::string why;
+    if (!smhip::PlanMapPackage(translations, a.package, &plan, &why)) Die("--map-package refused: " + why);
+  }
+  std::string dir = a.map_package;
+  if (dir.back() != '/') dir += '/';
+  // the description's place is taken before any device work: a directory that is missing or cannot be written ends the run here
+  if (!std::ofstream(dir + a.package.descript_filename)) Die("cannot write " + dir + a.package.descript_filename);
+  long long cap = 16;
+  size_t max_bytes = 16;
+  for (int k = 0; k < S; ++k) {
+    long long rows = 0;
+    for (int f = k * N; f < (k + 1) * N; ++f) {
+      struct stat sb;
+      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+    }
+    cap = std::max(cap, rows);
+  }
+  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
+  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
+  smhip_handle h = nullptr;
+  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
+  if (st != SMHIP_OK) Die(std::string("smhip_create (map package): ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
+  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
+  std::vector<smhip::MapPackageSubmap> submaps(static_cast<size_t>(S));
+  int rc = 0;
+  {
+    std::vector<int> order(static_cast<size_t>(S) * N);
+    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
+    smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
+    for (int k = 0; k < S && rc == 0; ++k) {
+      std::vector<const float*> rows(N);
+      std::vector<int> n(N);
+      std::vector<double> local(16 * static_cast<size_t>(N));
+      const Pose first_inv = AffineInverse(poses[k * N]);
+      for (int f = 0; f < N; ++f) {
+        int fi = -1;
+        rows[f] = scans.Next(&n[f], &fi);
+        if (!rows[f] || fi != k * N + f) Die("map package: prefetcher out of step");
+        if (n[f] < 0) Die("cannot read " + files[fi]);
+        const Pose lp = f == 0 ? Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} : MulPose(first_inv, poses[k * N + f]);   // submap.cc:83-87
+        std::memcpy(&local[16 * static_cast<size_t>(f)], lp.data(), sizeof(double) * 16);
+      }
+      int m = 0;
+      st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
+      scans.ReleaseHeld();
+      if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+      smhip::MapPackageSubmap& sub = submaps[static_cast<size_t>(k)];
+      std::memcpy(sub.global_pose.data(), poses[k * N].data(), sizeof(double) * 16);
+      sub.cloud.resize(static_cast<size_t>(m));
+      if (m > 0 && smhip_filter_get_output(h, &sub.cloud[0].x, nullptr, m) != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break;
+      }
+    }
+  }
+  smhip_destroy(h);
+  if (rc == 0) {
+    smhip::MrvmSettings set;
+    set.output_average = a.map_average; set.output_rgb = a.map_rgb; set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution;
+    set.hit_prob = a.map_hit; set.miss_prob = a.map_miss; set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
+    smhip::MapPackageResult pr;
+    // raw KITTI rows: intensity x 255 on the way into the map, as --map inserts them (kitti_reader.cc:113)
+    if (!smhip::SaveTrajectoriesAsMapPackage(submaps, a.package, set, dir, &pr, device, 255.f, a.map_max_table_log2)) rc = 3;
+    res->pieces = pr.pieces; res->submaps = pr.submaps; res->points = pr.points;
+  } else {
+    std::remove((dir + a.package.descript_filename).c_str());
+  }
+  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
 // ---- --close-loops ------------------------------------------------------------------------------------------------------------
 struct LoopResult { int submaps = 0, loop_edges = 0, solves = 0, stop_reason = 0; double seconds = 0.0, final_cost = 0.0, moved_m = 0.0; };
 
@@ -647,14 +759,27 @@ int RunMapOnly(const Args& a) {
   if (!ReadPoses(a.map_poses, &poses)) Die("cannot open " + a.map_poses);
   const std::vector<int> frames = MapFrames(a, n_frames);
   if (frames.empty()) Die("no scans in " + a.scans_dir);
-  if (static_cast<int>(poses.size()) <= frames.back())
+  if (!a.map_path.empty() && static_cast<int>(poses.size()) <= frames.back())
     Die(a.map_poses + " holds " + std::to_string(poses.size()) + " poses; the map needs one for every frame up to " + std::to_string(frames.back()) +
         " (" + std::to_string(frames.back() + 1) + " lines)");
-  MapResult m;
-  const int rc = BuildMap(a, files, frames, poses, 0, &m);
+  const int package_frames = n_frames / a.submap_frames * a.submap_frames;          // the frames of the full submaps
+  if (!a.map_package.empty() && static_cast<int>(poses.size()) < package_frames)
+    Die(a.map_poses + " holds " + std::to_string(poses.size()) + " poses; the map package needs one for each of the first " + std::to_string(package_frames) + " frames");
+  std::string fields;
+  int rc = 0;
+  if (!a.map_path.empty()) {
+    MapResult m;
+    rc = BuildMap(a, files, frames, poses, 0, &m);
+    if (rc == 0) fields += MapJsonFields(a, m);
+  }
+  if (rc == 0 && !a.map_package.empty()) {
+    PackageResult m;
+    rc = BuildMapPackage(a, files, n_frames, poses, 0, &m);
+    if (rc == 0) fields += PackageJsonFields(a, m);
+  }
   if (rc == 0 && !a.quiet)
     std::printf("%s}\n", (Fmt("{\"driver\": \"smhip_shard (map only)\", \"poses_file\": \"%s\", \"poses_in_file\": %d", a.map_poses.c_str(),
-                              static_cast<int>(poses.size())) + MapJsonFields(a, m)).c_str());
+                              static_cast<int>(poses.size())) + fields).c_str());
   return rc;
 }
 
@@ -906,7 +1031,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
                   "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
-      if (a.map_path.empty() && a.submap_edges.empty() && a.close_loops.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
+      if (a.map_path.empty() && a.submap_edges.empty() && a.close_loops.empty() && a.map_package.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;
   }
@@ -915,7 +1040,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
   if (pinned) for (float* b : ring_buffers) (void)hipHostFree(b);
   NCCLOK(ncclCommDestroy(comm));
   for (int k = 0; k < NH; ++k) (void)hipStreamDestroy(streams[k]);
-  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty() || !a.close_loops.empty())) {
+  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty() || !a.close_loops.empty() || !a.map_package.empty())) {
     // the static map and the submap edges from the poses as written: the pose file read back (--map-poses on that file builds
     // the same map)
     std::string fields;
@@ -935,6 +1060,11 @@ int RunRank(const Args& a, int rank, int world, int device) {
       LoopResult m;
       rc = CloseLoops(a, files, n_pairs + 1, poses, device, &m);
       if (rc == 0) fields += LoopJsonFields(a, m);
+    }
+    if (rc == 0 && !a.map_package.empty()) {
+      PackageResult m;
+      rc = BuildMapPackage(a, files, n_pairs + 1, poses, device, &m);
+      if (rc == 0) fields += PackageJsonFields(a, m);
     }
     if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? fields.c_str() : "");
   }

@@ -20,6 +20,10 @@
 // rows and pose (the reference's TransformPoint, every product and sum rounded to float), and the SORTED output orders the rows by
 // voxel key on the device (select the voxels kept, radix sort them by key, exclusive scan of their row counts), so that the same
 // map gives the same file on every run.
+//
+// Three more for the map package (builder/map_package.cc:143-198): the clipped insert (mrvm_clip_flags, a scan, mrvm_transform_kept),
+// the SORTED output cut to a box and moved to its centre (mrvm_row_counts_clipped, mrvm_sorted_rows_clipped), and mrvm_clear_table,
+// which empties the map for the next piece without giving the table back.
 #include <cstring>
 #include <string.h>
 
@@ -134,6 +138,50 @@ __global__ __launch_bounds__(256) void mrvm_transform(const float* raw, int stri
     o[i] = ((t.m[4 * i] * x + t.m[4 * i + 1] * y) + t.m[4 * i + 2] * z) + t.m[4 * i + 3];
   o[3] = r[3] * scale;                           // intensity (kitti_reader.cc:113 scales by 255)
   o[4] = stride > 4 ? r[4] : 0.f;                // factor
+}
+
+// The clipped insert of the map package (builder/map_package.cc:169-179): only the rows whose TRANSFORMED x, y lie in the closed
+// box go into the map, in their order.  mrvm_clip_flags computes x', y' with mrvm_transform's arithmetic, widens them to double
+// against the double bounds (a NaN fails every comparison) and leaves a flag per row; an inclusive scan of the flags gives every
+// kept row its place (no atomic decides one), and mrvm_transform_kept writes the kept rows there -- the unclipped world-frame
+// cloud is never stored.
+struct MrvmBox { double lo[2], hi[2], c[2]; };   // closed box; c: the centre the output is moved to (unused by the insert)
+__device__ __forceinline__ bool in_box(float x, float y, const MrvmBox& b) {
+  return (double)x >= b.lo[0] && (double)x <= b.hi[0] && (double)y >= b.lo[1] && (double)y <= b.hi[1];
+}
+__global__ __launch_bounds__(256) void mrvm_clip_flags(const float* raw, int stride, int n, MrvmPose t, MrvmBox box, int32_t* flags) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float* r = raw + (size_t)stride * j;
+  const float x = r[0], y = r[1], z = r[2];
+  const float wx = ((t.m[0] * x + t.m[1] * y) + t.m[2] * z) + t.m[3];
+  const float wy = ((t.m[4] * x + t.m[5] * y) + t.m[6] * z) + t.m[7];
+  flags[j] = in_box(wx, wy, box) ? 1 : 0;
+}
+// at: the inclusive scan of the flags -- a kept row j goes to row at[j] - 1
+__global__ __launch_bounds__(256) void mrvm_transform_kept(const float* raw, int stride, int n, MrvmPose t, float scale, const int32_t* flags,
+                                                           const int32_t* at, float* cloud) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n || flags[j] == 0) return;
+  const float* r = raw + (size_t)stride * j;
+  const float x = r[0], y = r[1], z = r[2];
+  float* o = cloud + 5 * (size_t)(at[j] - 1);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    o[i] = ((t.m[4 * i] * x + t.m[4 * i + 1] * y) + t.m[4 * i + 2] * z) + t.m[4 * i + 3];
+  o[3] = r[3] * scale;
+  o[4] = stride > 4 ? r[4] : 0.f;
+}
+
+// smhip_mrvm_clear: every slot empty as mrvm_alloc_table leaves it, every counter zero (the stored points need no reset: npts = 0)
+__global__ __launch_bounds__(256) void mrvm_clear_table(MrvmDev d) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < 6) d.counters[s] = 0;
+  if (s > (size_t)d.tmask) return;
+  d.keys[s] = 0ull; d.prob[s] = kUnknown; d.max_int[s] = 0; d.npts[s] = 0; d.created[s] = 0;
+  d.jmin[s] = 0xffffffffu; d.hits[s] = 0; d.misses[s] = 0;
 }
 
 // end voxels of the cloud: :86-104
@@ -316,6 +364,62 @@ __global__ __launch_bounds__(256) void mrvm_sorted_rows(MrvmDev d, const uint32_
   mrvm_voxel_rows(d, slots[i], use_max, flags, xyzi, offsets[i], capacity);
 }
 
+// The map package's cut (builder/map_package.cc:191-197) inside the SORTED output: of voxel s's output rows (mrvm_voxel_rows) only
+// those whose x, y lie in the closed box, each moved by the centre in double and rounded to float once.  kWrite = false counts them
+// (the voxel's entry for the scan), kWrite = true writes them from row `base` on: the same test in both, so the counts are the places.
+template <bool kWrite>
+__device__ __forceinline__ uint32_t mrvm_voxel_rows_clipped(const MrvmDev& d, uint32_t s, int use_max, int flags, const MrvmBox& box, float* xyzi,
+                                                            uint32_t base, int capacity) {
+  const int c = d.npts[s];
+  const bool average = flags & 1, rgb = flags & 2;
+  float grey = 0.f;
+  if (kWrite && rgb) {
+    uint32_t g = (uint32_t)d.max_int[s];
+    g = (uint32_t)((double)g * 1.4);
+    if (g > 255u) g = 255u;
+    grey = __uint_as_float(0xff000000u | (g << 16) | (g << 8) | g);
+  }
+  uint32_t kept = 0;
+  if (average) {
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int k = 0; k < c; ++k) {
+      const float* p = d.pts + ((size_t)s * d.maxp + k) * 5;
+      ax = __fadd_rn(ax, p[0]); ay = __fadd_rn(ay, p[1]); az = __fadd_rn(az, p[2]);
+    }
+    const float size = (float)c;
+    const float x = __fdiv_rn(ax, size), y = __fdiv_rn(ay, size);
+    if (!in_box(x, y, box)) return 0u;
+    if (kWrite && (long long)base < capacity) {
+      float* o = xyzi + 4 * (size_t)base;
+      o[0] = (float)((double)x - box.c[0]); o[1] = (float)((double)y - box.c[1]); o[2] = __fdiv_rn(az, size);
+      o[3] = rgb ? grey : (use_max ? (float)d.max_int[s] : 0.f);
+    }
+    return 1u;
+  }
+  for (int k = 0; k < c; ++k) {
+    const float* p = d.pts + ((size_t)s * d.maxp + k) * 5;
+    if (!in_box(p[0], p[1], box)) continue;
+    if (kWrite && (long long)base + kept < capacity) {
+      float* o = xyzi + 4 * ((size_t)base + kept);
+      o[0] = (float)((double)p[0] - box.c[0]); o[1] = (float)((double)p[1] - box.c[1]); o[2] = p[2];
+      o[3] = rgb ? grey : (use_max ? (float)d.max_int[s] : p[3]);
+    }
+    ++kept;
+  }
+  return kept;
+}
+__global__ __launch_bounds__(256) void mrvm_row_counts_clipped(MrvmDev d, const uint32_t* slots, int v, int flags, MrvmBox box, uint32_t* counts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > v) return;
+  counts[i] = i == v ? 0u : mrvm_voxel_rows_clipped<false>(d, slots[i], 0, flags, box, nullptr, 0u, 0);
+}
+__global__ __launch_bounds__(256) void mrvm_sorted_rows_clipped(MrvmDev d, const uint32_t* slots, const uint32_t* offsets, int v, int use_max, int flags,
+                                                                MrvmBox box, float* xyzi, int capacity) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v) return;
+  (void)mrvm_voxel_rows_clipped<true>(d, slots[i], use_max, flags, box, xyzi, offsets[i], capacity);
+}
+
 // every voxel, for the parity tests
 __global__ __launch_bounds__(256) void mrvm_dump(MrvmDev d, int32_t* keys3, uint8_t* prob, int32_t* max_int, int32_t* npts, float* pts, int capacity) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -408,7 +512,8 @@ static void mrvm_grow_for(smhip_mrvm_context* h, int n) {
 // smhip_mrvm_output_ex with SMHIP_MRVM_SORTED: the kept voxels' slots (rocprim::select over the table), sorted by key (radix sort
 // of (key, slot)), their row counts scanned (exclusive) into write positions, then one thread per voxel writes its rows there --
 // no row's place depends on which thread got there first.  Scratch memory lives for the call.
-static smhip_status mrvm_output_sorted(smhip_mrvm_handle h, float threshold, int flags, float* rows, int capacity, int* n_out) {
+// box != nullptr: the map package's cut -- a voxel's row count is the number of its rows inside the box, the rows are written recentred.
+static smhip_status mrvm_output_sorted(smhip_mrvm_handle h, float threshold, int flags, float* rows, int capacity, int* n_out, const MrvmBox* box = nullptr) {
   struct Scratch {                                         // freed on every way out
     std::vector<void*> p;
     ~Scratch() { for (void* q : p) (void)hipFree(q); }
@@ -445,18 +550,20 @@ static smhip_status mrvm_output_sorted(smhip_mrvm_handle h, float threshold, int
   hipLaunchKernelGGL(mrvm_gather_keys, gv, b256, 0, h->stream, d, slots, v, keys);
   b = bytes;                                               // the key's top bit is always set: bits 0..62
   MCHK(h, rocprim::radix_sort_pairs(tmp, b, keys, keys2, slots, slots2, (unsigned)v, 0, 63, h->stream));
-  hipLaunchKernelGGL(mrvm_row_counts, gv, b256, 0, h->stream, d, slots2, v, flags, cnt);
+  if (box) hipLaunchKernelGGL(mrvm_row_counts_clipped, gv, b256, 0, h->stream, d, slots2, v, flags, *box, cnt);
+  else hipLaunchKernelGGL(mrvm_row_counts, gv, b256, 0, h->stream, d, slots2, v, flags, cnt);
   b = bytes;
   MCHK(h, rocprim::exclusive_scan(tmp, b, cnt, off, 0u, (size_t)v + 1, rocprim::plus<uint32_t>(), h->stream));
   MCHK(h, hipMemcpyAsync(h->counters_host + 8, off + v, 4, hipMemcpyDeviceToHost, h->stream));
   MCHK(h, hipStreamSynchronize(h->stream));
   const uint32_t total = h->counters_host[8];
   *n_out = (int)total;
-  if (capacity <= 0) return SMHIP_OK;
+  if (capacity <= 0 || total == 0) return SMHIP_OK;
   const size_t m = std::min<size_t>((size_t)capacity, total);
   float* dev = nullptr;
   MCHK(h, sc.get((void**)&dev, sizeof(float) * 4 * m));
-  hipLaunchKernelGGL(mrvm_sorted_rows, gv, b256, 0, h->stream, d, slots2, off, v, h->set.use_max_intensity, flags, dev, (int)m);
+  if (box) hipLaunchKernelGGL(mrvm_sorted_rows_clipped, gv, b256, 0, h->stream, d, slots2, off, v, h->set.use_max_intensity, flags, *box, dev, (int)m);
+  else hipLaunchKernelGGL(mrvm_sorted_rows, gv, b256, 0, h->stream, d, slots2, off, v, h->set.use_max_intensity, flags, dev, (int)m);
   MCHK(h, hipGetLastError());
   MCHK(h, hipMemcpyAsync(rows, dev, sizeof(float) * 4 * m, hipMemcpyDeviceToHost, h->stream));
   MCHK(h, hipStreamSynchronize(h->stream));
@@ -496,7 +603,9 @@ smhip_status smhip_mrvm_create(int device, int table_log2, int max_cloud_points,
     size_t b1 = 0, b2 = 0;
     (void)rocprim::radix_sort_keys(nullptr, b1, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned)N, 0, 64, (hipStream_t)0);
     (void)rocprim::inclusive_scan(nullptr, b2, (const int32_t*)nullptr, (int32_t*)nullptr, N, rocprim::maximum<int32_t>(), (hipStream_t)0);
-    h->sort_bytes = std::max(b1, b2) + 256;
+    size_t b3 = 0;                                          // (the clipped insert's scan of its keep flags)
+    (void)rocprim::inclusive_scan(nullptr, b3, (const int32_t*)nullptr, (int32_t*)nullptr, N, rocprim::plus<int32_t>(), (hipStream_t)0);
+    h->sort_bytes = std::max(std::max(b1, b2), b3) + 256;
     A(&h->sort_tmp, h->sort_bytes);
   }
   ok = ok && hipHostMalloc((void**)&h->stage, N * 5 * 4) == hipSuccess && hipHostMalloc((void**)&h->counters_host, 64) == hipSuccess;
@@ -540,8 +649,10 @@ void smhip_mrvm_set_offset_z(smhip_mrvm_handle h, float offset) { if (h) h->set.
 // InsertPointCloud behind both entries.  pose == nullptr: `points` are map-frame rows of `stride_floats` >= 4 floats, packed to
 // InnerPointType rows on the host.  Otherwise the raw rows (stride 4 or 5) go up as they are and mrvm_transform writes the
 // world-frame rows on the device.
+// clip != nullptr (with a pose): the map package's clipped insert -- the rows are flagged and counted before anything of the map
+// is touched, and with none kept the call returns there; otherwise the insert runs over the *n_kept rows mrvm_transform_kept wrote.
 static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3], const MrvmPose* pose,
-                                float intensity_scale) {
+                                float intensity_scale, const MrvmBox* clip = nullptr, int* n_kept = nullptr) {
   if (n > h->max_cloud) { h->err = "cloud larger than max_cloud_points"; return SMHIP_ERR_CAPACITY; }
   {   // every ray starts at the origin: a non-finite or far-away one would walk ~2^21 voxels per ray for nothing.  Checked before
       // anything is touched, so a refused cloud leaves the map as it was.
@@ -565,10 +676,24 @@ static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int st
     MCHK(h, hipMemcpy(h->counters_host, h->d.counters, 16, hipMemcpyDeviceToHost));
     h->voxels = h->counters_host[1];
   }
+  const int n_raw = n;
+  if (clip) {
+    std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);
+    MCHK(h, hipMemcpyAsync(h->raw_dev, h->stage, sizeof(float) * (size_t)stride_floats * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mrvm_clip_flags, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->raw_dev, stride_floats, n, *pose, *clip, h->d.run_start);
+    size_t scan_bytes = h->sort_bytes;
+    MCHK(h, rocprim::inclusive_scan(h->sort_tmp, scan_bytes, h->d.run_start, h->scan_out, (size_t)n, rocprim::plus<int32_t>(), h->stream));
+    MCHK(h, hipMemcpyAsync(h->counters_host + 8, h->scan_out + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    MCHK(h, hipStreamSynchronize(h->stream));
+    const int kept = (int)h->counters_host[8];
+    if (n_kept) *n_kept = kept;
+    if (kept <= 0) return SMHIP_OK;                         // no insert at all (map_package.cc:177-180): the map is as it was
+    n = kept;
+  }
   h->voxels_stale = true;
   mrvm_grow_for(h, n);                                      // room for the voxels this cloud can add, like the reference's std::map
   if (pose) {
-    std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);
+    if (!clip) std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);   // (clipped: the raw rows are on the device already)
   } else {
     for (int i = 0; i < n; ++i) {
       const float* r = points + (size_t)stride_floats * i;
@@ -580,7 +705,10 @@ static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int st
   ++d.epoch;
   d.o[0] = origin[0]; d.o[1] = origin[1]; d.o[2] = origin[2] + h->set.z_offset;                         // .cc:66-67
   const dim3 g((n + 255) / 256), b(256);
-  if (pose) {
+  if (clip) {                                               // the flags and their scan are still in run_start / scan_out: both are rewritten below
+    hipLaunchKernelGGL(mrvm_transform_kept, dim3((n_raw + 255) / 256), b, 0, h->stream, h->raw_dev, stride_floats, n_raw, *pose, intensity_scale,
+                       h->d.run_start, h->scan_out, h->cloud_dev);
+  } else if (pose) {
     MCHK(h, hipMemcpyAsync(h->raw_dev, h->stage, sizeof(float) * (size_t)stride_floats * n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(mrvm_transform, g, b, 0, h->stream, h->raw_dev, stride_floats, n, *pose, intensity_scale, h->cloud_dev);
   } else {
@@ -639,6 +767,53 @@ smhip_status smhip_mrvm_insert_transformed_f32(smhip_mrvm_handle h, const float*
     for (int c = 0; c < 4; ++c) t.m[4 * r + c] = static_cast<float>(pose[4 * c + r]);                  // transform.cast<float>()
   const float origin[3] = {t.m[3], t.m[7], t.m[11]};                                                 // GlobalTranslation().cast<float>()
   return mrvm_insert(h, rows, stride_floats, n, origin, &t, intensity_scale);
+}
+
+smhip_status smhip_mrvm_insert_transformed_clipped_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                                       float intensity_scale, const double bb_min[2], const double bb_max[2], int* n_kept) {
+  if (!h || !pose) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (n_kept) *n_kept = 0;
+  if (!rows || n <= 0) { h->err = "cloud is empty."; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (stride_floats != 4 && stride_floats != 5) { h->err = "raw rows are x y z intensity [factor]: stride 4 or 5"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(pose[k])) { h->err = "pose is not finite: cloud refused"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (!bb_min || !bb_max || !std::isfinite(bb_min[0]) || !std::isfinite(bb_min[1]) || !std::isfinite(bb_max[0]) || !std::isfinite(bb_max[1])) {
+    h->err = "the box is missing or not finite: cloud refused";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  MrvmPose t;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) t.m[4 * r + c] = static_cast<float>(pose[4 * c + r]);                  // transform.cast<float>()
+  const float origin[3] = {t.m[3], t.m[7], t.m[11]};                                                 // translation.cast<float>(), map_package.cc:178-179
+  const MrvmBox box = {{bb_min[0], bb_min[1]}, {bb_max[0], bb_max[1]}, {0.0, 0.0}};
+  return mrvm_insert(h, rows, stride_floats, n, origin, &t, intensity_scale, &box, n_kept);
+}
+
+smhip_status smhip_mrvm_output_clipped(smhip_mrvm_handle h, float threshold, int flags, const double bb_min[2], const double bb_max[2],
+                                       const double centre[2], float* rows, int capacity, int* n_out) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (!n_out || (capacity > 0 && !rows) || (flags & ~7)) { h->err = "output: null pointer or unknown flag"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (!bb_min || !bb_max || !centre || !std::isfinite(bb_min[0]) || !std::isfinite(bb_min[1]) || !std::isfinite(bb_max[0]) || !std::isfinite(bb_max[1]) ||
+      !std::isfinite(centre[0]) || !std::isfinite(centre[1])) {
+    h->err = "output: the box or the centre is missing or not finite";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  h->err.clear();
+  MCHK(h, hipSetDevice(h->device));
+  const MrvmBox box = {{bb_min[0], bb_min[1]}, {bb_max[0], bb_max[1]}, {centre[0], centre[1]}};
+  return mrvm_output_sorted(h, threshold, flags & 3, rows, capacity, n_out, &box);
+}
+
+smhip_status smhip_mrvm_clear(smhip_mrvm_handle h) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  MCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(mrvm_clear_table, dim3((unsigned)((h->T + 255) / 256)), dim3(256), 0, h->stream, h->d);
+  MCHK(h, hipGetLastError());
+  MCHK(h, hipStreamSynchronize(h->stream));
+  h->d.epoch = 0;
+  h->voxels = 0; h->voxels_stale = false; h->last_skipped = 0;
+  return SMHIP_OK;
 }
 
 smhip_status smhip_mrvm_set_max_table_log2(smhip_mrvm_handle h, int max_table_log2) {

@@ -77,6 +77,53 @@ class MultiResolutionVoxelMapHip:
         self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
         self.last_skipped = n.value
 
+    def insert_transformed_clipped(self, rows, pose, bb_min, bb_max, intensity_scale: float = 1.0) -> int:
+        """insert_transformed of the rows whose transformed x, y lie in the closed box [bb_min, bb_max] (builder/map_package.cc:169-179;
+        float coordinates against double bounds, a NaN fails), in their order.  Returns the number of rows kept; with none the map is
+        left exactly as it was."""
+        p = np.ascontiguousarray(rows, dtype=np.float32)
+        T = np.asarray(pose, dtype=np.float64)
+        if p.ndim != 2 or T.shape != (4, 4):
+            raise ValueError("rows must be [N, 4|5], pose [4, 4]")
+        cm = np.ascontiguousarray(T.T).ravel()
+        lo = np.ascontiguousarray(bb_min, dtype=np.float64).reshape(2)
+        hi = np.ascontiguousarray(bb_max, dtype=np.float64).reshape(2)
+        kept = ctypes.c_int32()
+        self._check(self._lib.smhip_mrvm_insert_transformed_clipped_f32(self._h, p.ctypes.data_as(_capi.c_float_p), p.shape[1], p.shape[0],
+                                                                        cm.ctypes.data_as(_capi.c_double_p), float(intensity_scale),
+                                                                        lo.ctypes.data_as(_capi.c_double_p), hi.ctypes.data_as(_capi.c_double_p),
+                                                                        ctypes.byref(kept)))
+        self.last_warning = self._lib.smhip_mrvm_last_error(self._h).decode()
+        n = ctypes.c_int32()
+        self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
+        self.last_skipped = n.value
+        return kept.value
+
+    def output_clipped(self, bb_min, bb_max, centre, threshold: float | None = None, average: bool = False, rgb: bool = False,
+                       packed_rgb: bool = False, count_only: bool = False):
+        """The sorted output's rows inside the closed box, moved to `centre`: x <- float32(float64(x) - centre[0]), the same for y
+        (builder/map_package.cc:191-197).  With average the averaged row is tested.  count_only: the number of rows, nothing written."""
+        thr = self.settings.prob_threshold if threshold is None else threshold
+        flags = (1 if average else 0) | (2 if rgb else 0)
+        lo, hi, c = (np.ascontiguousarray(v, dtype=np.float64).reshape(2) for v in (bb_min, bb_max, centre))
+        args = (lo.ctypes.data_as(_capi.c_double_p), hi.ctypes.data_as(_capi.c_double_p), c.ctypes.data_as(_capi.c_double_p))
+        n = ctypes.c_int32()
+        self._check(self._lib.smhip_mrvm_output_clipped(self._h, thr, flags, *args, None, 0, ctypes.byref(n)))
+        if count_only:
+            return n.value
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._check(self._lib.smhip_mrvm_output_clipped(self._h, thr, flags, *args, out.ctypes.data_as(_capi.c_float_p), len(out), ctypes.byref(n)))
+        out = out[:n.value]
+        if rgb and not packed_rgb:
+            out[:, 3] = (out[:, 3].copy().view(np.uint32) & 0xff).astype(np.float32)
+        return out
+
+    def clear(self):
+        """Empties the map on the device; the table keeps its current size."""
+        self._check(self._lib.smhip_mrvm_clear(self._h))
+        self.last_warning = ""
+        self.last_skipped = 0
+
     def voxel_count(self) -> int:
         n = ctypes.c_int32()
         self._check(self._lib.smhip_mrvm_voxel_count(self._h, ctypes.byref(n)))
