@@ -586,8 +586,11 @@ double smhip_m2dp_match(const float* P, const float* Q, int n);
  * minimised from the given poses by Gauss-Newton steps with damping on a rejected step; each step's linear system by conjugate
  * gradients preconditioned with the block-tridiagonal part of the matrix (block cyclic reduction).  All f64, and ONE kernel
  * launch per call: nothing is read back between iterations.  Two calls on the same input give the same bits.
- * Not restated: GPS / ENU factors and SolveGpsCorrdAlone, the odometry calibration factor, the Huber odometry model
- * (isam_optimizer.cc:84-93), IMU, ViewGraph's picture output, the multi-trajectory optimiser. */
+ * Beside the between-factor, smhip_pose_graph_*_factors take two more kinds, which carry the reference's GPS / ENU factors
+ * (isam_optimizer.cc:238-349): a PRIOR on one node, and a POINT between a frame node and an observed node.
+ * Not restated: the odometry calibration factor, the Huber odometry model (isam_optimizer.cc:84-93), IMU, ViewGraph's picture
+ * output, the multi-trajectory optimiser, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
+ * conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300). */
 #define SMHIP_POSE_GRAPH_MAX_NODES 8192
 #define SMHIP_POSE_GRAPH_MAX_EDGES 32768
 /* One launch runs at most this many conjugate-gradient iterations in all, whatever max_iterations and the per-solve cap allow, and
@@ -645,6 +648,37 @@ smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* pose
  * of fixed nodes are ignored and come back as zero), M = the block-tridiagonal part of H = J^T J.  SMHIP_ERR_NOT_READY when no
  * call got as far as the launch. */
 smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, double* residuals, double* A, double* B, double* gradient, const double* v, double* minv_v);
+/* Factor kinds.  Every factor has an index pair (i, j), 16 doubles of data, 6 sigmas, and 6 rows of whitened A (for node i), B (for
+ * node j) and residual:
+ *   BETWEEN  as above: data = Z, column-major 4x4.
+ *   PRIOR    on node i (j must equal i): data = a rigid pose P, column-major 4x4.  e = [Log_SO3(R_P^T R_i); R_P^T (t_i - t_P)],
+ *            de/dxi_i = [Jr^-1(e_w), 0; 0, R_P^T R_i] in A; B is zero.  It is the BETWEEN from a constant node at P measured as the
+ *            identity.  The node's list holds it once.
+ *   POINT    between a frame node i and an observed node j != i: data[0..2] = l, the lever arm in node j's frame; data[3..5] = z,
+ *            the measured point in the frame node i maps into; the rest is not read.  Three rows: r = R_i (R_j l + t_j) + t_i - z,
+ *            whitened by sigmas[0..2] (sigmas[3..5] are not read); with p = R_j l + t_j, A = R_i [-hat(p), I], B = R_i R_j [-hat(l), I];
+ *            rows 3..5 of A, B and the residual are zero.  The reference's transformFrom(compose(GPS_COORD, pose), lever) measured
+ *            as enu (isam_optimizer.cc:238-261), to first order in the residual. */
+#define SMHIP_POSE_GRAPH_FACTOR_BETWEEN 0
+#define SMHIP_POSE_GRAPH_FACTOR_PRIOR 1
+#define SMHIP_POSE_GRAPH_FACTOR_POINT 2
+/* smhip_pose_graph_plan for factors of any kind.  kinds: one byte per factor, NULL = all BETWEEN; sigmas: NULL = the defaults of a
+ * BETWEEN, refused when any other kind is present.  csr_edges: room for 2 n_factors indices; a PRIOR is listed once, so
+ * csr_offsets[n_nodes] of them are written.  The refusals of smhip_pose_graph_optimize, and SMHIP_ERR_INVALID_ARGUMENT for: a kind
+ * outside 0..2; a PRIOR with j != i or a P that is no rigid transform; a POINT with i == j or a non-finite l or z; a sigma that is
+ * read and is not finite and positive; a free node with no BETWEEN and no PRIOR (POINT factors alone leave its block at rank 3); a
+ * component -- connected by BETWEEN and POINT factors -- with neither a fixed node nor a PRIOR.  The non-chain edges of pcg_cap are
+ * the BETWEEN and POINT factors with |i - j| != 1. */
+smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds,
+                                           const int32_t* ij, const double* data, const double* sigmas, int32_t* csr_offsets,
+                                           int32_t* csr_edges, char* why, int why_len);
+/* smhip_pose_graph_optimize for factors of any kind: the same loop, constants, stop rules and limits (factors count as edges).  A
+ * graph that passes the plan but leaves the preconditioner singular -- a chain run held by one or two POINT factors alone -- ends
+ * as stop_reason NUMERIC / SMHIP_ERR_NO_MATCH with the poses left as given.  smhip_pose_graph_last serves whichever of the two
+ * optimise calls ran last, n_edges being that call's factor count. */
+smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
+                                               const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
+                                               const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

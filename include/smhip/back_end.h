@@ -134,6 +134,8 @@ struct LoopFrame {
   Matrix4d global_pose = Matrix4d::Identity();
   InnerCloudPtr cloud;                          // may stay empty until a CloseLoop needs it
   descriptor::M2dp::Descriptor descriptor;      // read when use_descriptor is set
+  bool has_enu = false;                         // FrameBase::related_enu_ (builder/frame_base.h:93-95): the GPS fix of the frame,
+  double enu[3] = {0.0, 0.0, 0.0};              // already in ENU metres; read by IsamOptimizer when use_gps is set
 };
 
 struct LoopCandidates {

@@ -8,21 +8,43 @@
 //   IsamOptimizer::AddFrame           :196-293                    the loop detector, the vertex, one factor per edge when
 //                                                                 close_succeed, the update, UpdateAllPose (:106-125)
 //   IsamOptimizer::RunFinalOptimazation :351-383, GetWholeGraph :385-387
+//   the GPS / ENU factors           :238-293                      use_gps: a frame's ENU fix is cached until gps_factor_init_num are there
+//                                                                 and the drive has turned by gps_factor_init_angle_rad
+//                                                                 (AnalyseAllFramePoseForMaxRotation, :175-194); the frame that
+//                                                                 finds both runs SolveGpsCorrdAlone, gives every cached frame its
+//                                                                 factor and is itself neither cached nor given one (:271-279);
+//                                                                 afterwards every gps_factor_sample_step-th frame gets a factor
+//   IsamOptimizer::SolveGpsCorrdAlone :295-349                    the main graph solved, then a graph of its own through the same
+//                                                                 device call: the cached poses with a prior of sigma 1e-2, the frame
+//                                                                 vertex (GPS_COORD_KEY: the map origin in the GPS frame) with a
+//                                                                 prior of (0.2, 0.2, 1.57, 20, 20, 20) at gps_coord_transform_, one
+//                                                                 factor per cached fix; its result enters the main graph with a
+//                                                                 prior of (0.1, 0.1, 0.2, 1, 1, 1).  The reference stops that
+//                                                                 Gauss-Newton at a relative error of 1e-6 (:330); here the stop
+//                                                                 rules of smhip_pose_graph_optimize apply, with max_iterations 100
+//   IsamOptimizer::GetGpsCoordTransform :370-383
 //
 // What differs from the reference, on purpose:
 //   * GTSAM's iSAM2 (incremental, dogleg, :70-76) is replaced by a batch solve from the current estimate on every update; the
 //     factor, its noise and the objective are DESIGN.md section 6 ("Pose graph").  Both end in the same local minimum of the same
 //     objective to first order in the residual (GTSAM's Pose3 chart is not pinned by the reference's text).
-//   * Not restated, and without an option here: GPS / ENU factors and SolveGpsCorrdAlone, the odometry calibration factor
-//     (ODOM_CALIB_KEY), the Huber odometry model (:84-93), IMU, ViewGraph's picture output (GetWholeGraph returns the plain list),
-//     the multi-trajectory optimiser.
+//   * The ENU factor is transformFrom(compose(GPS_COORD, pose), tracking_gps_translation) measured as enu (:238-261) to first order
+//     in the residual: the POINT factor of include/smhip.h.  AnalyseAllFramePoseForMaxRotation clamps the dot product to [-1, 1]
+//     before acos (the reference's can be NaN for two equal rotations, which compares as "not below the angle").  A
+//     SolveGpsCorrdAlone that fails leaves nothing behind: the next frame with a fix tries again.
+//   * Not restated, and without an option here: the odometry calibration factor (ODOM_CALIB_KEY), the Huber odometry model
+//     (:84-93), IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
+//     geodetic conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300).  The tf_error
+//     calibration point (GPS_CALIB_KEY) is not created: enable_extrinsic_calib = true is refused.
 #ifndef SMHIP_POSE_GRAPH_H_
 #define SMHIP_POSE_GRAPH_H_
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <map>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -36,11 +58,19 @@ namespace back_end {
 using Sigmas = std::array<double, 6>;                                      // rotation first, as gtsam::Pose3
 inline Sigmas FrameMatchSigmas() { return {0.1, 0.1, 0.1, 0.15, 0.15, 0.15}; }    // frame_match_noise_model_, :80-81
 inline Sigmas LoopClosureSigmas() { return {0.1, 0.1, 0.1, 0.15, 0.15, 0.15}; }   // loop_closure_noise_model_, :82-83
+inline std::array<double, 3> GpsSigmas() { return {0.15, 0.15, 0.15}; }            // gps_noise_model_, :79
+inline Sigmas GpsCoordPriorSigmas() { return {0.1, 0.1, 0.2, 1.0, 1.0, 1.0}; }     // :340-343
+inline Sigmas AloneGpsCoordPriorSigmas() { return {0.2, 0.2, 1.57, 20.0, 20.0, 20.0}; }   // :306-309
+inline Sigmas AlonePosePriorSigmas() { return {1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2}; }   // :310
 
-// The vertices and between-factors, in the arrays smhip_pose_graph_optimize takes.
+// The vertices and factors, in the arrays smhip_pose_graph_optimize / smhip_pose_graph_optimize_factors take.  The frame vertex (the
+// map origin in the GPS frame) is kept apart from the chain and emitted as the LAST node at every solve, so that chain vertices stay
+// index-adjacent and the preconditioner keeps solving the chain exactly.
 class PoseGraph {
  public:
   struct Edge { int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); };
+  // a PRIOR on vertex `index` around `pose`, or a POINT between the frame vertex and vertex `index`
+  struct Factor { int kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; int index = 0; Matrix4d pose = Matrix4d::Identity(); double lever[3] = {0, 0, 0}, point[3] = {0, 0, 0}; Sigmas sigmas = FrameMatchSigmas(); };
 
   // :140-173.  Vertices come in index order; vertex 0 is constant.
   void AddVertex(int index, const Matrix4d& pose, const Matrix4d& transform_from_last_pose, const Sigmas& odom_noise = FrameMatchSigmas()) {
@@ -53,10 +83,60 @@ class PoseGraph {
   void AddLoopCloseEdge(int target_index, int source_index, const Matrix4d& transform_tgt_to_src, const Sigmas& loop_close_noise = LoopClosureSigmas()) {
     AddEdge(target_index, source_index, transform_tgt_to_src, loop_close_noise);
   }
+  // A vertex that is neither constant nor tied to the previous one: what SolveGpsCorrdAlone's own graph is made of (:314-320)
+  int AddLooseVertex(const Matrix4d& pose) {
+    poses_.push_back(pose);
+    fixed_.push_back(0);
+    return static_cast<int>(poses_.size()) - 1;
+  }
+  void AddPriorFactor(int index, const Matrix4d& pose, const Sigmas& sigmas) {
+    SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a prior is on a vertex that exists");
+    Factor f;
+    f.kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; f.index = index; f.pose = pose; f.sigmas = sigmas;
+    factors_.push_back(f);
+  }
+  // The frame vertex at `pose` with a prior around it; set again, it moves and its prior with it.
+  void SetFrameVertex(const Matrix4d& pose, const Sigmas& prior_sigmas) {
+    has_frame_ = true; frame_pose_ = pose; frame_prior_ = pose; frame_prior_sigmas_ = prior_sigmas;
+  }
+  bool HasFrameVertex() const { return has_frame_; }
+  const Matrix4d& FrameVertexPose() const { return frame_pose_; }
+  // :238-261: frame * pose_index * lever = point, sigmas for the three rows
+  void AddPointFactor(int index, const double lever[3], const double point[3], const std::array<double, 3>& sigmas3) {
+    SMHIP_CHECK(has_frame_, "a point factor needs the frame vertex");
+    SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a point factor observes a vertex that exists");
+    Factor f;
+    f.kind = SMHIP_POSE_GRAPH_FACTOR_POINT; f.index = index;
+    for (int c = 0; c < 3; ++c) { f.lever[c] = lever[c]; f.point[c] = point[c]; }
+    f.sigmas = {sigmas3[0], sigmas3[1], sigmas3[2], 1.0, 1.0, 1.0};            // (the last three are not read)
+    factors_.push_back(f);
+  }
+  bool HasFactors() const { return has_frame_ || !factors_.empty(); }
+  const std::vector<Factor>& Factors() const { return factors_; }
+  int PointFactorCount() const {
+    int n = 0;
+    for (const Factor& f : factors_) n += f.kind == SMHIP_POSE_GRAPH_FACTOR_POINT;
+    return n;
+  }
+  int NodeCount() const { return static_cast<int>(poses_.size()) + (has_frame_ ? 1 : 0); }
   // One device solve from the current poses, which it replaces.  false (poses unchanged, the reason on stderr) when refused.
   bool Optimize(smhip_handle handle, smhip_pose_graph_stats* stats = nullptr, const smhip_pose_graph_options* options = nullptr) {
     SMHIP_CHECK(handle != nullptr, "PoseGraph::Optimize needs a device handle");
     if (poses_.empty()) return true;
+    if (HasFactors()) {
+      std::vector<double> poses, data, sigmas;
+      std::vector<int32_t> ij;
+      std::vector<uint8_t> fixed, kinds;
+      FlattenFactors(&poses, &fixed, &kinds, &ij, &data, &sigmas);
+      const smhip_status s = smhip_pose_graph_optimize_factors(handle, NodeCount(), poses.data(), fixed.data(), static_cast<int>(kinds.size()), kinds.data(),
+                                                               ij.data(), data.data(), sigmas.data(), options, stats);
+      if (s != SMHIP_OK) {
+        std::fprintf(stderr, "[ERROR] smhip_pose_graph_optimize_factors: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+        return false;
+      }
+      SetFlatNodePoses(poses);
+      return true;
+    }
     std::vector<double> poses, Z, sigmas;
     std::vector<int32_t> ij;
     Flatten(&poses, &ij, &Z, &sigmas);
@@ -78,6 +158,42 @@ class PoseGraph {
       Z->insert(Z->end(), e.transform.data(), e.transform.data() + 16);
       sigmas->insert(sigmas->end(), e.sigmas.begin(), e.sigmas.end());
     }
+  }
+  // The arrays of smhip_pose_graph_optimize_factors: the vertices and then the frame vertex (when set) as the last node; the
+  // between-factors in the order of Edges(), the frame vertex's prior, then Factors() in their order.
+  void FlattenFactors(std::vector<double>* poses, std::vector<uint8_t>* fixed, std::vector<uint8_t>* kinds, std::vector<int32_t>* ij, std::vector<double>* data,
+                      std::vector<double>* sigmas) const {
+    Flatten(poses, ij, data, sigmas);
+    *fixed = fixed_;
+    kinds->assign(edges_.size(), SMHIP_POSE_GRAPH_FACTOR_BETWEEN);
+    const int frame = static_cast<int>(poses_.size());
+    auto put = [&](int kind, int i, int j, const double* d16, const Sigmas& s) {
+      kinds->push_back(static_cast<uint8_t>(kind));
+      ij->push_back(i); ij->push_back(j);
+      data->insert(data->end(), d16, d16 + 16);
+      sigmas->insert(sigmas->end(), s.begin(), s.end());
+    };
+    if (has_frame_) {
+      poses->insert(poses->end(), frame_pose_.data(), frame_pose_.data() + 16);
+      fixed->push_back(0);
+      put(SMHIP_POSE_GRAPH_FACTOR_PRIOR, frame, frame, frame_prior_.data(), frame_prior_sigmas_);
+    }
+    for (const Factor& f : factors_) {
+      if (f.kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) {
+        put(f.kind, f.index, f.index, f.pose.data(), f.sigmas);
+      } else {
+        double d16[16] = {f.lever[0], f.lever[1], f.lever[2], f.point[0], f.point[1], f.point[2]};
+        put(f.kind, frame, f.index, d16, f.sigmas);
+      }
+    }
+  }
+  // NodeCount() poses back from a solve of FlattenFactors' arrays
+  void SetFlatNodePoses(const std::vector<double>& poses) {
+    SMHIP_CHECK(poses.size() == 16 * static_cast<size_t>(NodeCount()), "16 doubles per node");
+    for (size_t k = 0; k < poses_.size(); ++k)
+      for (int q = 0; q < 16; ++q) poses_[k].data()[q] = poses[16 * k + static_cast<size_t>(q)];
+    if (has_frame_)
+      for (int q = 0; q < 16; ++q) frame_pose_.data()[q] = poses[16 * poses_.size() + static_cast<size_t>(q)];
   }
   void SetFlatPoses(const std::vector<double>& poses) {
     SMHIP_CHECK(poses.size() == 16 * poses_.size(), "16 doubles per vertex");
@@ -101,10 +217,19 @@ class PoseGraph {
   std::vector<Matrix4d> poses_;
   std::vector<uint8_t> fixed_;
   std::vector<Edge> edges_;
+  std::vector<Factor> factors_;
+  bool has_frame_ = false;
+  Matrix4d frame_pose_ = Matrix4d::Identity(), frame_prior_ = Matrix4d::Identity();
+  Sigmas frame_prior_sigmas_ = GpsCoordPriorSigmas();
 };
 
 struct IsamOptimizerOptions {
   int max_iterations = 50;            // of one solve (smhip_pose_graph_options)
+  bool use_gps = false;               // isam_optimizer.h:61-66
+  int gps_factor_init_num = 25;
+  int gps_factor_sample_step = 1;
+  double gps_factor_init_angle_rad = 1.6;
+  bool enable_extrinsic_calib = false;   // true is refused: the tf_error point (GPS_CALIB_KEY) is not restated
 };
 
 // view_graph.h's GraphItem without the picture: what GetWholeGraph returns
@@ -121,10 +246,14 @@ class IsamOptimizer {
   using Solver = std::function<bool(PoseGraph*)>;
 
   IsamOptimizer(const IsamOptimizerOptions& options, const LoopDetectorSettings& l_d_setting, smhip_handle handle)
-      : loop_detector_(new LoopDetector(l_d_setting)), options_(options), handle_(handle) {}
+      : loop_detector_(new LoopDetector(l_d_setting)), options_(options), handle_(handle) {
+    SMHIP_CHECK(!options.enable_extrinsic_calib, "enable_extrinsic_calib is not restated: the GPS_CALIB_KEY point and the odometry calibration are out of scope");
+  }
   IsamOptimizer(const IsamOptimizer&) = delete;
   IsamOptimizer& operator=(const IsamOptimizer&) = delete;
   void SetSolver(Solver solver) { solver_ = std::move(solver); }
+  // tf_tracking_gps_: only its translation is used (:247-248), the antenna in the tracking frame
+  void SetTransformTrackingToGps(const Matrix4d& t) { for (int c = 0; c < 3; ++c) gps_lever_[c] = t(c, 3); }
 
   // :196-293.  `frame`: the submap as the detector sees it; `transform_from_last`: Submap::TransformFromLast(), the matched
   // transform from the previous submap (ignored for the first).  Every frame's global_pose is written back, which is what the
@@ -149,9 +278,45 @@ class IsamOptimizer {
       }
       ok = Update() && ok;
     }
+    if (options_.use_gps && frame->has_enu) {                                                   // :264-288
+      if (!calculated_first_gps_coord_) {
+        if (static_cast<int>(cached_enu_.size()) < options_.gps_factor_init_num ||
+            AnalyseAllFramePoseForMaxRotation() < options_.gps_factor_init_angle_rad) {
+          cached_enu_[frame_index] = {frame->enu[0], frame->enu[1], frame->enu[2]};
+        } else if (SolveGpsCorrdAlone()) {
+          for (const auto& index_enu : cached_enu_) AddEnuFactor(index_enu.first, index_enu.second);
+          ok = Update() && ok;
+          calculated_first_gps_coord_ = true;
+        } else {
+          ok = false;
+        }
+      } else if (options_.gps_factor_sample_step <= 1 || frame_index % options_.gps_factor_sample_step == 0) {
+        AddEnuFactor(frame_index, {frame->enu[0], frame->enu[1], frame->enu[2]});
+        ok = Update() && ok;
+      }
+    }
     if (ok) UpdateAllPose();                                                                    // :292
     return ok;
   }
+  // :175-194: the largest |acos(x_0 . x_f)| over the frames' global rotations
+  double AnalyseAllFramePoseForMaxRotation() const {
+    if (frames_.size() <= 1) return 0.0;
+    double most = 0.0;
+    const Matrix4d& first = frames_[0]->global_pose;
+    for (const auto& f : frames_) {
+      double dot = first(0, 0) * f->global_pose(0, 0) + first(1, 0) * f->global_pose(1, 0) + first(2, 0) * f->global_pose(2, 0);
+      dot = dot > 1.0 ? 1.0 : dot < -1.0 ? -1.0 : dot;
+      most = std::fmax(most, std::fabs(std::acos(dot)));
+    }
+    return most;
+  }
+  // :370-383: the frame vertex's pose -- the map origin in the GPS frame -- or identity without GPS
+  Matrix4d GetGpsCoordTransform() const {
+    return options_.use_gps && graph_.HasFrameVertex() ? graph_.FrameVertexPose() : Matrix4d::Identity();
+  }
+  int GpsFactorCount() const { return graph_.PointFactorCount(); }
+  int CachedEnuCount() const { return static_cast<int>(cached_enu_.size()); }
+  const smhip_pose_graph_stats& AloneStats() const { return alone_stats_; }
   bool RunFinalOptimazation() {                                                                 // :351-353
     const bool ok = Update();
     if (ok) UpdateAllPose();
@@ -185,6 +350,38 @@ class IsamOptimizer {
     if (ok) ++solves_;
     return ok;
   }
+  void AddEnuFactor(int index, const std::array<double, 3>& enu) {                              // add_enu_factor, :238-262
+    graph_.AddPointFactor(index, gps_lever_, enu.data(), GpsSigmas());
+  }
+  // :295-349
+  bool SolveGpsCorrdAlone() {
+    if (!Update()) return false;                                                                // :299-300
+    PoseGraph alone;
+    std::vector<int> at;
+    for (const auto& index_enu : cached_enu_) {
+      const Matrix4d& pose = graph_.Pose(index_enu.first);
+      const int k = alone.AddLooseVertex(pose);
+      alone.AddPriorFactor(k, pose, AlonePosePriorSigmas());
+      at.push_back(k);
+    }
+    alone.SetFrameVertex(gps_coord_transform_, AloneGpsCoordPriorSigmas());
+    size_t n = 0;
+    for (const auto& index_enu : cached_enu_) alone.AddPointFactor(at[n++], gps_lever_, index_enu.second.data(), GpsSigmas());
+    bool ok;
+    if (solver_) {
+      ok = solver_(&alone);
+    } else {
+      smhip_pose_graph_options o;
+      smhip_pose_graph_default_options(&o);
+      o.max_iterations = 100;                                                                   // :331
+      ok = alone.Optimize(handle_, &alone_stats_, &o);
+    }
+    if (!ok) return false;
+    ++solves_;
+    gps_coord_transform_ = alone.FrameVertexPose();                                             // :334
+    graph_.SetFrameVertex(gps_coord_transform_, GpsCoordPriorSigmas());                         // :339-343
+    return true;
+  }
   void UpdateAllPose() {                                                                        // :106-125
     for (size_t i = 0; i < frames_.size(); ++i) frames_[i]->global_pose = graph_.Pose(static_cast<int>(i));
   }
@@ -195,8 +392,12 @@ class IsamOptimizer {
   Solver solver_;
   PoseGraph graph_;
   std::vector<std::shared_ptr<LoopFrame>> frames_;
-  smhip_pose_graph_stats last_stats_{};
+  smhip_pose_graph_stats last_stats_{}, alone_stats_{};
   int loop_edges_ = 0, solves_ = 0;
+  std::map<int, std::array<double, 3>> cached_enu_;
+  bool calculated_first_gps_coord_ = false;
+  Matrix4d gps_coord_transform_ = Matrix4d::Identity();
+  double gps_lever_[3] = {0.0, 0.0, 0.0};
 };
 
 }  // namespace back_end

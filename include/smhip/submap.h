@@ -152,6 +152,11 @@ class Submap {
   }
   descriptor::M2dp::Descriptor GetDescriptor() const { return descriptor_; }
   void SetDescriptor(const descriptor::M2dp::Descriptor& d) { descriptor_ = d; }
+  // FrameBase::SetRelatedGpsInENU / GetRelatedGpsInENU / HasGps (builder/frame_base.h:60-66, 93-95): the fix of the submap's first
+  // frame, the frame whose pose is the submap's global pose, in ENU metres
+  void SetRelatedGpsInENU(double east, double north, double up) { enu_[0] = east; enu_[1] = north; enu_[2] = up; has_gps_ = true; }
+  const double* GetRelatedGpsInENU() const { return enu_; }
+  bool HasGps() const { return has_gps_; }
 
   // Device forms: the cloud is built on the matcher's own handle and becomes its source / its CalculateNormals target without
   // a download.  Return the number of points the matcher holds (0 when the device refused; Align then fails loudly).
@@ -170,6 +175,8 @@ class Submap {
   std::vector<Matrix4d> local_poses_, frame_global_poses_;
   InnerCloudPtr cloud_;
   descriptor::M2dp::Descriptor descriptor_;
+  bool has_gps_ = false;
+  double enu_[3] = {0.0, 0.0, 0.0};
 };
 
 // The pairs ConnectSubmaps matches, in its order: for k = 0, 1, ... source = submap k + 1 on target = submap k

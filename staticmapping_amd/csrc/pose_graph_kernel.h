@@ -8,7 +8,9 @@
 // bits in every thread, so all threads take the same branches and meet at the same barriers.  Every loop has a bound from the
 // sizes or the options; nothing waits on memory.
 //
-// Poses and measurements are 12 doubles here: the rotation row-major, then the translation.
+// Poses and measurements are 12 doubles here: the rotation row-major, then the translation.  A factor is a BETWEEN, a PRIOR or a
+// POINT (include/smhip.h, "Factor kinds"; tests/pose_graph_gps_ref.py); whatever its kind it has an index pair, 12 doubles of
+// data, 6 inverse sigmas and 6 rows of whitened A, B and residual, so only edge_cost and linearize_edge look at the kind.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -42,8 +44,9 @@ struct Dev {
   const int32_t *fixed = nullptr, *csr_off = nullptr, *csr_edge = nullptr;
   // per edge
   const int32_t* ij = nullptr;            // 2
-  const double* Z = nullptr;              // 12
-  const double* sinv = nullptr;           // 6: 1 / sigma
+  const int32_t* kind = nullptr;          // SMHIP_POSE_GRAPH_FACTOR_*; nullptr: every factor is a BETWEEN
+  const double* Z = nullptr;              // 12: BETWEEN the measurement, PRIOR the pose P, POINT the lever (0..2) and the point (3..5)
+  const double* sinv = nullptr;           // 6: 1 / sigma (POINT reads the first three)
   double *A = nullptr, *B = nullptr;      // 36, row-major, whitened
   double *rw = nullptr, *u = nullptr;     // 6: whitened residual; A p_i + B p_j
   // probe
@@ -127,23 +130,71 @@ PG_HD void edge_error(const double* Xi, const double* Xj, const double* Z, doubl
   log_so3(RE, e);
 }
 
+// POINT: r = R_i (R_j l + t_j) + t_i - z, with p = R_j l + t_j handed back
+PG_HD void point_error(const double* Xi, const double* Xj, const double* lz, double* r, double* p) {
+  for (int a = 0; a < 3; ++a) p[a] = Xj[3 * a] * lz[0] + Xj[3 * a + 1] * lz[1] + Xj[3 * a + 2] * lz[2] + Xj[9 + a];
+  for (int a = 0; a < 3; ++a) r[a] = Xi[3 * a] * p[0] + Xi[3 * a + 1] * p[1] + Xi[3 * a + 2] * p[2] + Xi[9 + a] - lz[3 + a];
+}
+
+// A PRIOR on node i around P is the BETWEEN from a constant node at P measured as the identity: the same residual, and that
+// factor's B is the PRIOR's only Jacobian.
 PG_HD double edge_cost(const Dev& d, const double* X, int e) {
-  double err[6], Rij[9], tij[3], RE[9];
-  edge_error(X + 12 * d.ij[2 * e], X + 12 * d.ij[2 * e + 1], d.Z + 12 * (size_t)e, err, Rij, tij, RE);
+  const int kind = d.kind ? d.kind[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
+  const double* Xi = X + 12 * (size_t)d.ij[2 * e];
+  const double* Xj = X + 12 * (size_t)d.ij[2 * e + 1];
+  const double* Z = d.Z + 12 * (size_t)e;
+  const double* sinv = d.sinv + 6 * (size_t)e;
   double s = 0.0;
-  for (int a = 0; a < 6; ++a) { const double w = err[a] * d.sinv[6 * (size_t)e + a]; s += w * w; }
+  if (kind == SMHIP_POSE_GRAPH_FACTOR_POINT) {
+    double r[3], p[3];
+    point_error(Xi, Xj, Z, r, p);
+    for (int a = 0; a < 3; ++a) { const double w = r[a] * sinv[a]; s += w * w; }
+    return s;
+  }
+  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+  const bool prior = kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR;
+  double err[6], Rij[9], tij[3], RE[9];
+  edge_error(prior ? Z : Xi, Xj, prior ? eye : Z, err, Rij, tij, RE);
+  for (int a = 0; a < 6; ++a) { const double w = err[a] * sinv[a]; s += w * w; }
   return s;
 }
 
 PG_HD void linearize_edge(const Dev& d, const double* X, int e) {
-  double err[6], Rij[9], tij[3], RE[9], J[9];
+  const int kind = d.kind ? d.kind[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
+  const double* Xi = X + 12 * (size_t)d.ij[2 * e];
+  const double* Xj = X + 12 * (size_t)d.ij[2 * e + 1];
   const double* Z = d.Z + 12 * (size_t)e;
-  edge_error(X + 12 * d.ij[2 * e], X + 12 * d.ij[2 * e + 1], Z, err, Rij, tij, RE);
-  jr_inv(err, J);
-  const double hat[9] = {0.0, -tij[2], tij[1], tij[2], 0.0, -tij[0], -tij[1], tij[0], 0.0};
+  const double* sinv = d.sinv + 6 * (size_t)e;
   double* A = d.A + 36 * (size_t)e;
   double* B = d.B + 36 * (size_t)e;
-  const double* sinv = d.sinv + 6 * (size_t)e;
+  if (kind == SMHIP_POSE_GRAPH_FACTOR_POINT) {
+    double r[3], p[3], RR[9];
+    point_error(Xi, Xj, Z, r, p);
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) RR[3 * a + b] = Xi[3 * a] * Xj[b] + Xi[3 * a + 1] * Xj[3 + b] + Xi[3 * a + 2] * Xj[6 + b];          // R_i R_j
+    const double hp[9] = {0.0, -p[2], p[1], p[2], 0.0, -p[0], -p[1], p[0], 0.0};
+    const double hl[9] = {0.0, -Z[2], Z[1], Z[2], 0.0, -Z[0], -Z[1], Z[0], 0.0};
+    for (int a = 0; a < 3; ++a) {
+      const double w = sinv[a];
+      for (int b = 0; b < 3; ++b) {
+        A[6 * a + b] = -w * (Xi[3 * a] * hp[b] + Xi[3 * a + 1] * hp[3 + b] + Xi[3 * a + 2] * hp[6 + b]);                            // -R_i hat(p)
+        A[6 * a + 3 + b] = w * Xi[3 * a + b];
+        B[6 * a + b] = -w * (RR[3 * a] * hl[b] + RR[3 * a + 1] * hl[3 + b] + RR[3 * a + 2] * hl[6 + b]);                            // -R_i R_j hat(l)
+        B[6 * a + 3 + b] = w * RR[3 * a + b];
+      }
+      d.rw[6 * (size_t)e + a] = r[a] * w;
+      d.rw[6 * (size_t)e + 3 + a] = 0.0;
+    }
+    for (int k = 18; k < 36; ++k) { A[k] = 0.0; B[k] = 0.0; }
+    return;
+  }
+  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+  const bool prior = kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR;
+  if (prior) { Xi = Z; Z = eye; double* t = A; A = B; B = t; }                  // (the constant twin's Jacobian is dropped below)
+  double err[6], Rij[9], tij[3], RE[9], J[9];
+  edge_error(Xi, Xj, Z, err, Rij, tij, RE);
+  jr_inv(err, J);
+  const double hat[9] = {0.0, -tij[2], tij[1], tij[2], 0.0, -tij[0], -tij[1], tij[0], 0.0};
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
       const double w = sinv[a], v = sinv[3 + a];
@@ -156,6 +207,7 @@ PG_HD void linearize_edge(const Dev& d, const double* X, int e) {
       B[6 * (3 + a) + b] = 0.0;
       B[6 * (3 + a) + 3 + b] = v * RE[3 * a + b];                                                                        // Rz^T Rij
     }
+  if (prior) for (int k = 0; k < 36; ++k) A[k] = 0.0;
   for (int a = 0; a < 6; ++a) d.rw[6 * (size_t)e + a] = err[a] * sinv[a];
 }
 

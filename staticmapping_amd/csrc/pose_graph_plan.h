@@ -19,8 +19,8 @@ constexpr double kOrthonormalTolerance = 1.0e-6;
 
 struct Plan {
   std::vector<int32_t> csr_offsets;      // n_nodes + 1
-  std::vector<int32_t> csr_edges;        // 2 n_edges: the edges of node k, ascending, at [csr_offsets[k], csr_offsets[k + 1])
-  int non_chain_edges = 0;               // |i - j| != 1
+  std::vector<int32_t> csr_edges;        // 2 n_edges less the PRIORs: the factors of node k, ascending, at [csr_offsets[k], csr_offsets[k + 1])
+  int non_chain_edges = 0;               // BETWEEN and POINT factors with |i - j| != 1
   int pcg_cap = 0;                       // 12 non_chain_edges + 64
   int levels = 0;                        // of the cyclic reduction: the smallest L with 2^L >= n_nodes
 };
@@ -39,50 +39,76 @@ inline const char* transform_problem(const double* m) {
   return nullptr;
 }
 
-// SMHIP_OK and the plan, or the refusal with its reason in *why.  Reads nothing beyond the sizes it has accepted.
-inline smhip_status check_and_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
-                                   const double* edge_sigmas, Plan* plan, std::string* why) {
+// SMHIP_OK and the plan, or the refusal with its reason in *why.  Reads nothing beyond the sizes it has accepted.  kinds: one
+// SMHIP_POSE_GRAPH_FACTOR_* per factor, nullptr = every factor a BETWEEN.  data: 16 doubles per factor -- BETWEEN the measurement and
+// PRIOR the pose, column-major 4x4; POINT the lever arm (0..2) and the measured point (3..5).
+inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                           const double* data, const double* sigmas, Plan* plan, std::string* why) {
   auto refuse = [&](smhip_status s, const std::string& text) { if (why) *why = "pose graph: " + text; return s; };
-  if (!poses || !fixed || (n_edges > 0 && (!edge_ij || !edge_Z))) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "null pointer");
-  if (n_nodes < 1 || n_edges < 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "at least one node and no negative edge count");
+  if (!poses || !fixed || (n_factors > 0 && (!ij || !data))) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "null pointer");
+  if (n_nodes < 1 || n_factors < 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "at least one node and no negative edge count");
   if (n_nodes > kMaxNodes) return refuse(SMHIP_ERR_CAPACITY, "more than " + std::to_string(kMaxNodes) + " nodes");
-  if (n_edges > kMaxEdges) return refuse(SMHIP_ERR_CAPACITY, "more than " + std::to_string(kMaxEdges) + " edges");
+  if (n_factors > kMaxEdges) return refuse(SMHIP_ERR_CAPACITY, "more than " + std::to_string(kMaxEdges) + " edges");
   for (int k = 0; k < n_nodes; ++k)
     if (const char* p = transform_problem(poses + 16 * (size_t)k)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "pose " + std::to_string(k) + " " + p);
   std::vector<int32_t> parent((size_t)n_nodes), degree((size_t)n_nodes, 0);
+  std::vector<uint8_t> held((size_t)n_nodes, 0), prior((size_t)n_nodes, 0);      // by a BETWEEN or a PRIOR: all six directions; by a PRIOR
   std::iota(parent.begin(), parent.end(), 0);
   auto root = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
   int non_chain = 0;
-  for (int e = 0; e < n_edges; ++e) {
-    const int i = edge_ij[2 * e], j = edge_ij[2 * e + 1];
+  for (int e = 0; e < n_factors; ++e) {
+    const int i = ij[2 * e], j = ij[2 * e + 1];
+    const int kind = kinds ? kinds[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
+    const double* dat = data + 16 * (size_t)e;
     const std::string name = "edge " + std::to_string(e);
+    if (kind != SMHIP_POSE_GRAPH_FACTOR_BETWEEN && kind != SMHIP_POSE_GRAPH_FACTOR_PRIOR && kind != SMHIP_POSE_GRAPH_FACTOR_POINT)
+      return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " has a kind that is none of BETWEEN, PRIOR and POINT");
     if (i < 0 || j < 0 || i >= n_nodes || j >= n_nodes) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " names a node out of range");
-    if (i == j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " joins a node to itself");
-    if (const char* p = transform_problem(edge_Z + 16 * (size_t)e)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + "'s measurement " + p);
-    if (edge_sigmas)
-      for (int c = 0; c < 6; ++c) {
-        const double s = edge_sigmas[6 * (size_t)e + c];
+    int read = 6;
+    if (kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) {
+      if (i != j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " is a prior whose j is not its i");
+      if (const char* p = transform_problem(dat)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + "'s prior pose " + p);
+    } else if (kind == SMHIP_POSE_GRAPH_FACTOR_POINT) {
+      if (i == j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " is a point factor that joins a node to itself");
+      for (int c = 0; c < 6; ++c)
+        if (!std::isfinite(dat[c])) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " has a lever arm or a point that is not finite");
+      read = 3;
+    } else {
+      if (i == j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " joins a node to itself");
+      if (const char* p = transform_problem(dat)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + "'s measurement " + p);
+    }
+    if (sigmas) {
+      for (int c = 0; c < read; ++c) {
+        const double s = sigmas[6 * (size_t)e + c];
         if (!std::isfinite(s) || !(s > 0.0)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " has a sigma that is not finite and positive");
       }
-    ++degree[i]; ++degree[j];
+    } else if (kind != SMHIP_POSE_GRAPH_FACTOR_BETWEEN) {
+      return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " is no BETWEEN and needs its sigmas: the defaults are those of a BETWEEN");
+    }
+    ++degree[i];
+    if (kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) { held[i] = 1; prior[i] = 1; continue; }       // listed once, diagonal: never a chain or non-chain edge
+    ++degree[j];
+    if (kind == SMHIP_POSE_GRAPH_FACTOR_BETWEEN) { held[i] = 1; held[j] = 1; }
     parent[root(i)] = root(j);
     if (i - j != 1 && j - i != 1) ++non_chain;
   }
   std::vector<uint8_t> anchored((size_t)n_nodes, 0);
   for (int k = 0; k < n_nodes; ++k) {
     if (!fixed[k] && degree[k] == 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "free node " + std::to_string(k) + " has no edge");
-    if (fixed[k]) anchored[root(k)] = 1;
+    if (!fixed[k] && !held[k])
+      return refuse(SMHIP_ERR_INVALID_ARGUMENT, "free node " + std::to_string(k) + " has point factors only, which leave its block at rank 3");
+    if (fixed[k] || prior[k]) anchored[root(k)] = 1;
   }
   for (int k = 0; k < n_nodes; ++k)
-    if (!anchored[root(k)]) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "the component of node " + std::to_string(k) + " has no fixed node");
+    if (!anchored[root(k)]) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "the component of node " + std::to_string(k) + " has no fixed node" + (kinds ? " and no prior" : ""));
   if (plan) {
     plan->csr_offsets.assign((size_t)n_nodes + 1, 0);
     for (int k = 0; k < n_nodes; ++k) plan->csr_offsets[k + 1] = plan->csr_offsets[k] + degree[k];
-    plan->csr_edges.assign(2 * (size_t)n_edges, 0);
+    plan->csr_edges.assign((size_t)plan->csr_offsets[n_nodes], 0);
     std::vector<int32_t> at(plan->csr_offsets.begin(), plan->csr_offsets.end() - 1);
-    for (int e = 0; e < n_edges; ++e) {                                       // ascending e: every node's list comes out sorted
-      plan->csr_edges[at[edge_ij[2 * e]]++] = e;
-      plan->csr_edges[at[edge_ij[2 * e + 1]]++] = e;
+    for (int e = 0; e < n_factors; ++e) {                                     // ascending e: every node's list comes out sorted
+      plan->csr_edges[at[ij[2 * e]]++] = e;
+      if (ij[2 * e + 1] != ij[2 * e]) plan->csr_edges[at[ij[2 * e + 1]]++] = e;      // (a PRIOR once)
     }
     plan->non_chain_edges = non_chain;
     plan->pcg_cap = 12 * non_chain + 64;
@@ -90,6 +116,11 @@ inline smhip_status check_and_plan(int n_nodes, const double* poses, const uint8
     while ((1 << plan->levels) < n_nodes) ++plan->levels;
   }
   return SMHIP_OK;
+}
+
+inline smhip_status check_and_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
+                                   const double* edge_sigmas, Plan* plan, std::string* why) {
+  return check_and_plan_factors(n_nodes, poses, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, plan, why);
 }
 
 }  // namespace pose_graph

@@ -27,6 +27,12 @@
 // odometry factors, loop edges, one device solve per update), and the frames' corrected poses are written to PATH in the pose
 // writer's format, one line per frame -- so --map --map-poses PATH builds the corrected map.  The detector's settings are the
 // --loop-* flags (back_end/loop_detector_options.h:29-40).  Without the flag nothing of this runs and every output is what it was.
+// With --gps-enu FILE (one line per scan in file order: east north up in metres, nan = no fix; the geodetic conversion is not
+// restated) a submap carries the fix of its first frame and IsamOptimizer adds the GPS / ENU factors of isam_optimizer.cc:238-349
+// (--gps-lever x,y,z: the antenna in the tracking frame; --gps-init-num, --gps-sample-step, --gps-init-angle: isam_optimizer.h:61-66);
+// --gps-output-enu premultiplies every submap pose by GetGpsCoordTransform() before UpdateInnerFramePose (map_builder.cc:748-762),
+// so PATH is in the ENU frame.  --gps-enu without --close-loops, or a FILE whose line count is not the scan count, ends the run
+// with exit 2 before any device work.
 //
 // --map-package DIR: the map package of MapBuilder::SaveMapPackage (builder/map_builder.cc:816-823, builder/map_package.cc): the
 // static map cut into overlapping square pieces, DIR/<prefix><x>_<y>.pcd centred on the piece and DIR/map_package.xml listing them
@@ -104,6 +110,14 @@ struct Args {
   // descriptor gate on as in the shipped KITTI config
   std::string close_loops;
   smhip::back_end::LoopDetectorSettings loop = [] { smhip::back_end::LoopDetectorSettings s; s.use_descriptor = true; return s; }();
+  // --gps-enu FILE: one line per scan in file order, three numbers already in ENU metres, nan = no fix (the geodetic conversion is
+  // not restated); the factors' settings (isam_optimizer.h:61-66) and the antenna in the tracking frame
+  std::string gps_enu;
+  std::vector<std::array<double, 3>> enu;
+  double gps_lever[3] = {0.0, 0.0, 0.0};
+  int gps_init_num = 25, gps_sample_step = 1;
+  double gps_init_angle = 1.6;
+  bool gps_output_enu = false;
 };
 
 [[noreturn]] void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -129,6 +143,28 @@ void Mul4(const double* a, const double* b, double* out) {              // row-m
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += a[4 * i + k] * b[4 * k + j]; r[4 * i + j] = s; }
   std::memcpy(out, r, sizeof(r));
+}
+
+// --gps-enu FILE into a->enu, before any device work: a line per scan of the listing, or the run ends here
+void ReadGpsEnu(Args* a) {
+  const size_t scans = ListScans(a->scans_dir).size();
+  std::ifstream in(a->gps_enu);
+  if (!in) Die("cannot read " + a->gps_enu);
+  std::string text;
+  while (std::getline(in, text)) {
+    if (text.find_first_not_of(" \t\r") == std::string::npos) continue;
+    std::array<double, 3> e;
+    const char* p = text.c_str();
+    for (int c = 0; c < 3; ++c) {
+      char* end = nullptr;
+      e[c] = std::strtod(p, &end);
+      if (end == p) Die(a->gps_enu + ": line " + std::to_string(a->enu.size() + 1) + " does not hold three numbers");
+      p = end;
+    }
+    a->enu.push_back(e);
+  }
+  if (a->enu.size() != scans)
+    Die(a->gps_enu + " holds " + std::to_string(a->enu.size()) + " lines for " + std::to_string(scans) + " scans in " + a->scans_dir);
 }
 
 Args Parse(int argc, char** argv) {
@@ -185,6 +221,12 @@ Args Parse(int argc, char** argv) {
     else if (k == "--loop-use-descriptor") a.loop.use_descriptor = std::atoi(val().c_str()) != 0;
     else if (k == "--loop-m2dp-score") a.loop.m2dp_match_score = static_cast<float>(std::atof(val().c_str()));
     else if (k == "--loop-accept-score") a.loop.accept_scan_match_score = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--gps-enu") a.gps_enu = val();
+    else if (k == "--gps-lever") { if (std::sscanf(val().c_str(), "%lf,%lf,%lf", &a.gps_lever[0], &a.gps_lever[1], &a.gps_lever[2]) != 3) Die("--gps-lever takes x,y,z"); }
+    else if (k == "--gps-init-num") a.gps_init_num = std::atoi(val().c_str());
+    else if (k == "--gps-sample-step") a.gps_sample_step = std::atoi(val().c_str());
+    else if (k == "--gps-init-angle") a.gps_init_angle = std::atof(val().c_str());
+    else if (k == "--gps-output-enu") a.gps_output_enu = true;
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
              "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
@@ -195,7 +237,9 @@ Args Parse(int argc, char** argv) {
              "[--package-border-offset 100] [--package-prefix part_] [--package-descript map_package.xml]\n"
              "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]\n"
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
-             "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75]");
+             "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75]\n"
+             "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
+             "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
   if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
@@ -209,6 +253,10 @@ Args Parse(int argc, char** argv) {
     Die("bad submap setting (--submap-frames >= 1, --submap-voxel >= 0)");
   if (!a.submap_edges.empty() && !a.map_poses.empty()) Die("--submap-edges needs the alignment run (not --map-poses)");
   if (!a.close_loops.empty() && !a.map_poses.empty()) Die("--close-loops needs the alignment run (not --map-poses)");
+  if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
+  if (a.gps_output_enu && a.gps_enu.empty()) Die("--gps-output-enu needs --gps-enu");
+  if (!std::isfinite(a.gps_lever[0]) || !std::isfinite(a.gps_lever[1]) || !std::isfinite(a.gps_lever[2]) || !std::isfinite(a.gps_init_angle) || a.gps_init_num < 0)
+    Die("bad GPS setting (--gps-lever finite, --gps-init-angle finite, --gps-init-num >= 0)");
   if (a.loop.nearest_history_pos_num < 1 || a.loop.loop_ignore_threshold < 0 || a.loop.trying_detect_loop_count < 1)
     Die("bad loop setting (--loop-history >= 1, --loop-ignore-threshold >= 0, --loop-detect-count >= 1)");
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
@@ -597,12 +645,22 @@ int BuildMapPackage(const Args& a, const std::vector<std::string>& files, int n_
 }
 
 // ---- --close-loops ------------------------------------------------------------------------------------------------------------
-struct LoopResult { int submaps = 0, loop_edges = 0, solves = 0, stop_reason = 0; double seconds = 0.0, final_cost = 0.0, moved_m = 0.0; };
+struct LoopResult {
+  int submaps = 0, loop_edges = 0, solves = 0, stop_reason = 0; double seconds = 0.0, final_cost = 0.0, moved_m = 0.0;
+  int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
+};
+
+std::string GpsJsonFields(const Args& a, const LoopResult& m) {
+  if (a.gps_enu.empty()) return "";
+  std::string s = Fmt(", \"gps_factors\": %d, \"gps_coord\": [", m.gps_factors);
+  for (int q = 0; q < 16; ++q) s += Fmt("%.17g%s", m.gps_coord[q], q == 15 ? "]" : ", ");
+  return s;
+}
 
 std::string LoopJsonFields(const Args& a, const LoopResult& m) {
   return Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
              "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), m.submaps,
-             m.loop_edges, m.solves, m.stop_reason, m.final_cost, m.moved_m, m.seconds);
+             m.loop_edges, m.solves, m.stop_reason, m.final_cost, m.moved_m, m.seconds) + GpsJsonFields(a, m);
 }
 
 // MapBuilder::ConnectAllSubmap (builder/map_builder.cc:448-613) over the submaps --submap-edges builds, from the poses as written:
@@ -660,7 +718,15 @@ int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frame
   settings.device = device;
   int rc = 0;
   {
-    be::IsamOptimizer optimizer(be::IsamOptimizerOptions(), settings, h);
+    be::IsamOptimizerOptions io;
+    io.use_gps = !a.gps_enu.empty();
+    io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
+    be::IsamOptimizer optimizer(io, settings, h);
+    {
+      Matrix4d tracking_to_gps = Matrix4d::Identity();
+      for (int c = 0; c < 3; ++c) tracking_to_gps(c, 3) = a.gps_lever[c];
+      optimizer.SetTransformTrackingToGps(tracking_to_gps);
+    }
     std::vector<std::shared_ptr<bld::Submap>> maps;
     std::vector<std::shared_ptr<be::LoopFrame>> frames;
     bld::SubmapOptions so;
@@ -718,6 +784,14 @@ int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frame
         frame->global_pose = maps[0]->GlobalPose();
       }
       if (k + 1 < S && smhip_filter_output_to_target(h, 0, &m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+      if (io.use_gps) {   // the fix of the submap's first frame, the frame whose pose is its global pose
+        const std::array<double, 3>& e = a.enu[static_cast<size_t>(k) * N];
+        if (std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2])) {
+          maps.back()->SetRelatedGpsInENU(e[0], e[1], e[2]);
+          frame->has_enu = true;
+          for (int c = 0; c < 3; ++c) frame->enu[c] = maps.back()->GetRelatedGpsInENU()[c];
+        }
+      }
       frames.push_back(frame);
       if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
     }
@@ -725,6 +799,11 @@ int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frame
     if (rc == 0) {
       res->loop_edges = optimizer.LoopEdgeCount(); res->solves = optimizer.SolveCount();
       res->stop_reason = optimizer.LastStats().stop_reason; res->final_cost = optimizer.LastStats().final_cost;
+      // MapBuilder::CalculateCoordTransformToGps (map_builder.cc:748-762): with --gps-output-enu every submap pose is premultiplied
+      // by the map origin's pose in the GPS frame before UpdateInnerFramePose, and the file is in the ENU frame
+      const Matrix4d to_enu = optimizer.GetGpsCoordTransform();
+      res->gps_factors = optimizer.GpsFactorCount();
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) res->gps_coord[4 * r + c] = to_enu(r, c);
       for (int k = 0; k < S; ++k) {
         maps[k]->SetGlobalPose(frames[k]->global_pose);
         maps[k]->UpdateInnerFramePose();                                   // map_builder.cc:598-601
@@ -733,11 +812,16 @@ int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frame
           const Pose& was = poses[k * N + f];
           res->moved_m = std::max(res->moved_m, std::sqrt((G(0, 3) - was[12]) * (G(0, 3) - was[12]) + (G(1, 3) - was[13]) * (G(1, 3) - was[13]) +
                                                           (G(2, 3) - was[14]) * (G(2, 3) - was[14])));
-          write_pose(G.data());
+          if (!a.gps_output_enu) write_pose(G.data());
+        }
+        if (a.gps_output_enu) {
+          maps[k]->SetGlobalPose(be::Multiply(to_enu, frames[k]->global_pose));
+          maps[k]->UpdateInnerFramePose();
+          for (int f = 0; f < N; ++f) write_pose(maps[k]->FrameGlobalPose(f).data());
         }
       }
       Pose last;
-      std::memcpy(last.data(), frames.back()->global_pose.data(), sizeof(double) * 16);
+      std::memcpy(last.data(), (a.gps_output_enu ? be::Multiply(to_enu, frames.back()->global_pose) : frames.back()->global_pose).data(), sizeof(double) * 16);
       const Pose carry = MulPose(last, AffineInverse(poses[(S - 1) * N]));
       for (int f = S * N; f < n_frames; ++f) write_pose(MulPose(carry, poses[f]).data());
     }
@@ -1078,6 +1162,7 @@ int main(int argc, char** argv) {
   // two of them share a queue and run one after the other (as bench.py does; must be set before the runtime starts)
   setenv("GPU_MAX_HW_QUEUES", "8", 0);
   Args a = Parse(argc, argv);
+  if (!a.gps_enu.empty()) ReadGpsEnu(&a);
   if (a.id_file.empty()) a.id_file = "/tmp/smhip_shard_id_" + std::to_string(a.rank >= 0 ? static_cast<long>(getppid()) : static_cast<long>(getpid()));
   if (!a.map_poses.empty()) return RunMapOnly(a);                       // the map alone: one process, no RCCL
   if (a.rank >= 0) {                                                     // one rank of a launched group

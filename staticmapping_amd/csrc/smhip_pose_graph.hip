@@ -5,7 +5,8 @@
 // conjugate-gradient iteration and every level of the preconditioner's cyclic reduction, with __syncthreads as the only barrier
 // and nothing read back in between (pose_graph_kernel.h holds the loop; it also compiles for a CPU).  The work between two
 // barriers is a few thousand 6x6 block operations at most, so a grid-wide seam would cost more than what it separates.
-//   linearise     one thread per edge: e, the whitened A and B
+//   linearise     one thread per factor: e, the whitened A and B; the only place that knows a factor's kind (BETWEEN, PRIOR, POINT:
+//                 include/smhip.h, "Factor kinds")
 //   assemble      one thread per node, its edges in index order (the host's CSR list): Hkk, g, the chain block -- no atomics
 //   factor        block cyclic reduction of M = the block-tridiagonal part of H + lambda blockdiag(H): two barriers per level
 //   pcg           H p matrix-free (per edge, then per node), M^-1 by one sweep up and one down the levels, dot products as
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_solve(const pg::Dev d) 
 
 // doubles and words of the device state per node / per edge, and of the staging the host fills
 constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6;
-constexpr int kNodeI = 2, kEdgeI = 4;           // fixed, csr_off (+1); ij, csr_edge
+constexpr int kNodeI = 2, kEdgeI = 5;           // fixed, csr_off (+1); ij, csr_edge, kind
 
 }  // namespace
 
@@ -96,11 +97,11 @@ smhip_status pg_ensure(smhip_context* h) {
   d.out_d = take(pg::kOutDoubles);
   int32_t* q = st->ints;
   auto takei = [&q](size_t count) { int32_t* r = q; q += count; return r; };
-  // (uploaded: fixed, csr_off, ij, csr_edge)
-  d.fixed = takei(N); d.csr_off = takei(N + 1); d.ij = takei(2 * M); d.csr_edge = takei(2 * M);
+  // (uploaded: fixed, csr_off, ij, csr_edge, kind)
+  d.fixed = takei(N); d.csr_off = takei(N + 1); d.ij = takei(2 * M); d.csr_edge = takei(2 * M); d.kind = takei(M);
   d.out_i = takei(pg::kOutInts);
   st->host_d.resize(12 * N + 12 * M + 6 * M);
-  st->host_i.resize(N + (N + 1) + 2 * M + 2 * M);
+  st->host_i.resize(N + (N + 1) + 2 * M + 2 * M + M);
   h->pose_graph = st;
   return SMHIP_OK;
 }
@@ -128,28 +129,39 @@ void smhip_pose_graph_default_options(smhip_pose_graph_options* o) {
   o->max_iterations = 50;
 }
 
-smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
-                                   const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                           const double* data, const double* sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
   pg::Plan plan;
   std::string text;
-  const smhip_status s = pg::check_and_plan(n_nodes, poses, fixed, n_edges, edge_ij, edge_Z, edge_sigmas, &plan, &text);
+  const smhip_status s = pg::check_and_plan_factors(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, &plan, &text);
   if (why && why_len > 0) { std::strncpy(why, text.c_str(), (size_t)why_len - 1); why[why_len - 1] = '\0'; }
   if (s) return s;
   if (csr_offsets) std::memcpy(csr_offsets, plan.csr_offsets.data(), sizeof(int32_t) * plan.csr_offsets.size());
-  if (csr_edges && n_edges > 0) std::memcpy(csr_edges, plan.csr_edges.data(), sizeof(int32_t) * plan.csr_edges.size());
+  if (csr_edges && !plan.csr_edges.empty()) std::memcpy(csr_edges, plan.csr_edges.data(), sizeof(int32_t) * plan.csr_edges.size());
   return SMHIP_OK;
+}
+
+smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
+                                   const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  return smhip_pose_graph_plan_factors(n_nodes, poses, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, csr_offsets, csr_edges, why, why_len);
 }
 
 smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const int32_t* edge_ij,
                                        const double* edge_Z, const double* edge_sigmas, const smhip_pose_graph_options* opts,
                                        smhip_pose_graph_stats* stats) {
+  return smhip_pose_graph_optimize_factors(h, n_nodes, poses_inout, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, opts, stats);
+}
+
+smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                               const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas,
+                                               const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   smhip_pose_graph_options o;
   smhip_pose_graph_default_options(&o);
   if (opts) o = *opts;
   if (o.max_iterations < 1) { h->err = "pose graph: max_iterations must be at least 1"; return SMHIP_ERR_INVALID_ARGUMENT; }
   pg::Plan plan;
-  if (const smhip_status s = pg::check_and_plan(n_nodes, poses_inout, fixed, n_edges, edge_ij, edge_Z, edge_sigmas, &plan, &h->err)) return s;
+  if (const smhip_status s = pg::check_and_plan_factors(n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, &plan, &h->err)) return s;
   HIPCHK(h, hipSetDevice(h->device));
   if (const smhip_status s = pg_ensure(h)) return s;
   smhip_pose_graph_state* st = h->pose_graph;
@@ -158,16 +170,26 @@ smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* pose
   const size_t N = pg::kMaxNodes, M = pg::kMaxEdges;
   double* hd = st->host_d.data();
   for (int k = 0; k < n_nodes; ++k) pack12(poses_inout + 16 * (size_t)k, hd + 12 * (size_t)k);
-  for (int e = 0; e < n_edges; ++e) {
-    pack12(edge_Z + 16 * (size_t)e, hd + 12 * N + 12 * (size_t)e);
-    for (int c = 0; c < 6; ++c) hd[12 * N + 12 * M + 6 * (size_t)e + c] = 1.0 / (edge_sigmas ? edge_sigmas[6 * (size_t)e + c] : pg::kDefaultSigmas[c]);
-  }
   int32_t* hi = st->host_i.data();
+  const size_t n_csr = plan.csr_edges.size();
+  for (int e = 0; e < n_edges; ++e) {
+    const int kind = kinds ? kinds[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
+    double* z = hd + 12 * N + 12 * (size_t)e;
+    double* sinv = hd + 12 * N + 12 * M + 6 * (size_t)e;
+    hi[N + N + 1 + 4 * M + (size_t)e] = kind;
+    if (kind == SMHIP_POSE_GRAPH_FACTOR_POINT) {                 // the lever arm, the point; three sigmas
+      for (int c = 0; c < 12; ++c) z[c] = c < 6 ? edge_Z[16 * (size_t)e + c] : 0.0;
+      for (int c = 0; c < 6; ++c) sinv[c] = c < 3 ? 1.0 / edge_sigmas[6 * (size_t)e + c] : 0.0;
+      continue;
+    }
+    pack12(edge_Z + 16 * (size_t)e, z);
+    for (int c = 0; c < 6; ++c) sinv[c] = 1.0 / (edge_sigmas ? edge_sigmas[6 * (size_t)e + c] : pg::kDefaultSigmas[c]);
+  }
   for (int k = 0; k < n_nodes; ++k) hi[k] = fixed[k] ? 1 : 0;
   std::memcpy(hi + N, plan.csr_offsets.data(), sizeof(int32_t) * ((size_t)n_nodes + 1));
   if (n_edges > 0) {
     std::memcpy(hi + N + N + 1, edge_ij, sizeof(int32_t) * 2 * (size_t)n_edges);
-    std::memcpy(hi + N + N + 1 + 2 * M, plan.csr_edges.data(), sizeof(int32_t) * 2 * (size_t)n_edges);
+    std::memcpy(hi + N + N + 1 + 2 * M, plan.csr_edges.data(), sizeof(int32_t) * n_csr);
   }
   hipStream_t s = h->stream;
   pg::Dev d = st->dev;
@@ -177,7 +199,8 @@ smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* pose
     HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.Z), hd + 12 * N, sizeof(double) * 12 * (size_t)n_edges, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.sinv), hd + 12 * N + 12 * M, sizeof(double) * 6 * (size_t)n_edges, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.ij), hi + N + N + 1, sizeof(int32_t) * 2 * (size_t)n_edges, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.csr_edge), hi + N + N + 1 + 2 * M, sizeof(int32_t) * 2 * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.csr_edge), hi + N + N + 1 + 2 * M, sizeof(int32_t) * n_csr, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.kind), hi + N + N + 1 + 4 * M, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, s));
   }
   HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.fixed), hi, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.csr_off), hi + N, sizeof(int32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));

@@ -1,6 +1,6 @@
 """ctypes view of the device pose-graph optimiser (include/smhip.h, `smhip_pose_graph_*`): what back_end::IsamOptimizer asks of GTSAM
-in the reference (back_end/isam_optimizer.{h,cc}) -- rigid poses, between-factors, fixed nodes -- as one kernel launch per
-optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
+in the reference (back_end/isam_optimizer.{h,cc}) -- rigid poses, between-factors, fixed nodes, and the PRIOR and POINT factors behind its GPS / ENU factors
+(*_factors below) -- as one kernel launch per optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
 from __future__ import annotations
 
 import ctypes
@@ -10,6 +10,7 @@ import numpy as np
 from . import _capi
 
 MAX_NODES, MAX_EDGES = 8192, 32768
+BETWEEN, PRIOR, POINT = 0, 1, 2
 STOP_REASONS = {1: "step", 2: "cost", 3: "max_iterations", 4: "damping", 5: "numeric"}
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -73,6 +74,69 @@ def optimize(matcher, poses, edges, Z, fixed=None, sigmas=None, max_iterations: 
     st = _capi.PoseGraphStats()
     matcher._check(lib.smhip_pose_graph_optimize(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(E, _capi.c_int32_p),
                                                  _ptr(Zc, _capi.c_double_p), _ptr(S, _capi.c_double_p), ctypes.byref(o), ctypes.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
+    stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
+
+
+def factor_data(kind, *parts):
+    """The 16 doubles of one factor: (BETWEEN, Z [4, 4]), (PRIOR, P [4, 4]) -- column-major -- or (POINT, lever [3], point [3])"""
+    out = np.zeros(16)
+    if kind == POINT:
+        out[:3], out[3:6] = parts
+    else:
+        out[:] = np.asarray(parts[0], np.float64).T.ravel()
+    return out
+
+
+def _factor_arrays(poses, fixed, kinds, ij, data, sigmas):
+    poses = np.asarray(poses, np.float64)
+    n = len(poses)
+    ij = np.ascontiguousarray(np.asarray(ij, np.int32).reshape(-1, 2))
+    data = np.ascontiguousarray(np.asarray(data, np.float64).reshape(-1, 16))
+    if kinds is not None:
+        kinds = np.ascontiguousarray(np.asarray(kinds, np.uint8).reshape(-1))
+    if poses.shape[1:] != (4, 4) or len(data) != len(ij) or (kinds is not None and len(kinds) != len(ij)):
+        raise ValueError("poses [N, 4, 4], kinds [F], ij [F, 2], data [F, 16]")
+    if fixed is None:
+        fixed = np.zeros(n, np.uint8)
+    fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8))
+    if len(fixed) != n:
+        raise ValueError("one fixed flag per pose")
+    if sigmas is not None:
+        sigmas = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas, np.float64), (len(ij), 6)))
+    return np.ascontiguousarray(poses.transpose(0, 2, 1)), fixed, kinds, ij, data, sigmas
+
+
+def plan_factors(poses, kinds, ij, data, fixed=None, sigmas=None):
+    """plan() for factors of any kind (include/smhip.h, "Factor kinds"): kinds [F] of BETWEEN / PRIOR / POINT or None for all BETWEEN,
+    ij [F, 2], data [F, 16] as factor_data() lays it out, fixed: N flags (default: none), sigmas [F, 6].  Returns (csr_offsets [N + 1],
+    csr_edges [csr_offsets[N]]: a PRIOR is listed once) or raises PoseGraphRefused."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    off = np.zeros(len(P) + 1, np.int32)
+    inc = np.zeros(max(2 * len(E), 1), np.int32)
+    why = ctypes.create_string_buffer(256)
+    s = _capi.load_library().smhip_pose_graph_plan_factors(len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                           _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                           off.ctypes.data_as(_capi.c_int32_p), inc.ctypes.data_as(_capi.c_int32_p), why, len(why))
+    if s != 0:
+        raise PoseGraphRefused(s, why.value.decode())
+    return off, inc[:off[-1]]
+
+
+def optimize_factors(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, max_iterations: int | None = None):
+    """optimize() for factors of any kind; the arguments of plan_factors().  Returns (poses [N, 4, 4], stats dict); last() serves
+    this call too, with n_edges = the factor count."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    lib = matcher._lib
+    o = _capi.PoseGraphOptions()
+    lib.smhip_pose_graph_default_options(ctypes.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = max_iterations
+    st = _capi.PoseGraphStats()
+    matcher._check(lib.smhip_pose_graph_optimize_factors(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                         _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                         ctypes.byref(o), ctypes.byref(st)))
     stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
     stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
     return np.ascontiguousarray(P.transpose(0, 2, 1)), stats

@@ -3,6 +3,7 @@ circle drive of 909 submaps (tests/pose_graph_ref.py circle_drive), once overlap
 chained odometry.  Median of --repeats calls after --warmup calls, a host clock around calls that end in a synchronise (the call uploads
 the graph, launches, and copies the poses back).  Beside it, as the yardstick on the same box, the restatement with scipy's sparse
 direct solve: its whole time (the linearisation there is a Python loop) and the time inside the sparse solves alone.
+--gps: instead, the same size as four laps with no loop edge and a GPS (ENU) factor on every submap (profiles/pose_graph_gps_probe.json).
 One JSON line on stdout (and in --out when given)."""
 import argparse
 import json
@@ -19,11 +20,43 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 N_NODES = 909
 
 
+def gps_case(m, a):
+    """909 submaps, four laps of a circle with no loop edge, a GPS factor on every submap (tests/pose_graph_gps_cases.py): the frame
+    node last, its prior at the alone-solve result of the first 25 submaps"""
+    import pose_graph_gps_cases as cases
+    import pose_graph_gps_ref as gps
+    from staticmapping_amd import pose_graph
+    g = cases.circle_gps(N_NODES, 1, loops=(), every=1, overlap=682)
+
+    def call():
+        return pose_graph.optimize_factors(m, g["poses"], g["kinds"], g["ij"], g["data"], fixed=g["fixed"], sigmas=g["sigmas"])
+    for _ in range(a.warmup):
+        call()
+    t = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        poses, stats = call()
+        t.append(time.perf_counter() - t0)
+    case = {"gps_factors": int((g["kinds"] == gps.POINT).sum()), "factors": int(len(g["kinds"])), "device_median_ms": round(float(np.median(t)) * 1e3, 4),
+            "device_min_ms": round(float(np.min(t)) * 1e3, 4), "outer_steps": stats["iterations"], "rejected_steps": stats["rejected_steps"],
+            "pcg_iterations": stats["pcg_iterations"], "pcg_longest_solve": stats["pcg_max_iterations"], "pcg_cap": stats["pcg_cap"],
+            "levels": stats["levels"], "stop": stats["stop"], "initial_cost": stats["initial_cost"], "final_cost": stats["final_cost"],
+            "enu_error_before_m": cases.enu_error(g, g["poses"]), "enu_error_after_m": cases.enu_error(g, poses)}
+    if not a.no_restatement:
+        t0 = time.perf_counter()
+        want, st = gps.optimize(g, solver="sparse")
+        case["restatement_sparse_total_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+        case["restatement_steps"] = st["accepted"] + st["rejected"]
+        case["difference_m"] = float(np.abs(poses[:, :3, 3] - want[:, :3, 3]).max())
+    return case
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-restatement", action="store_true")
+    ap.add_argument("--gps", action="store_true", help="the 909-submap drive that never closes a loop, with a GPS factor on every submap, instead of the two loop cases")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -35,7 +68,9 @@ def main():
     from staticmapping_amd import pose_graph
     m = sm.IcpFastHip(pair_slots=1, max_source_points=1024, max_target_points=1024)
     res = {"nodes": N_NODES, "repeats": a.repeats, "warmup": a.warmup, "cases": []}
-    for n_loops in (3, 60):
+    if a.gps:
+        res["cases"].append(gps_case(m, a))
+    for n_loops in (() if a.gps else (3, 60)):
         # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
         g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
 
