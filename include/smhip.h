@@ -394,7 +394,8 @@ typedef struct smhip_ndt_gicp_stats {
   int32_t gicp_iterations;             /* outer iterations (nr_iterations_) */
   int32_t gicp_function_evaluations;   /* functor evaluations of all BFGS runs */
   int32_t gicp_correspondences;        /* kept correspondences of the last outer iteration */
-  int32_t reserved;
+  int32_t gicp_covariances_on_demand;  /* target covariances this Align estimated in its correspondence steps, each matched
+                                          target point once (batches of >= 4 jobs; 0 where all were estimated up front) */
   double ndt_score;                    /* ndt_.getFitnessScore() (0.9 when use_ndt = 0) */
   double gicp_score;                   /* gicp_.getFitnessScore() (10 when skipped) */
 } smhip_ndt_gicp_stats;
@@ -427,7 +428,8 @@ smhip_status smhip_gicp_align(smhip_handle h, const double guess[16], double res
  * in that same order (or the upload order for smhip_gicp_align) */
 smhip_status smhip_ndt_gicp_get_downsampled(smhip_handle h, int which, float* xyz, int capacity, int* n_out);
 /* the GICP functor (value and 6-gradient, state x = tx ty tz roll pitch yaw) over the correspondences of the last outer
- * iteration of the last GICP run, with base_transformation_ = guess */
+ * iteration of the last GICP run, with base_transformation_ = guess.  SMHIP_ERR_NO_MATCH when that step kept no
+ * correspondence (the sums are divided by the kept count) */
 smhip_status smhip_gicp_evaluate(smhip_handle h, const double guess[16], const double x[6], double* f, double grad[6]);
 smhip_status smhip_gicp_get_covariances(smhip_handle h, int which, double* cov, int n);
 

@@ -67,7 +67,7 @@ class NdtGicpStats(ctypes.Structure):
     _fields_ = [("ok", ctypes.c_int32), ("n_source", ctypes.c_int32), ("n_target", ctypes.c_int32),
                 ("ndt_iterations", ctypes.c_int32), ("gicp_iterations", ctypes.c_int32),
                 ("gicp_function_evaluations", ctypes.c_int32), ("gicp_correspondences", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("ndt_score", ctypes.c_double), ("gicp_score", ctypes.c_double)]
+                ("gicp_covariances_on_demand", ctypes.c_int32), ("ndt_score", ctypes.c_double), ("gicp_score", ctypes.c_double)]
 
 
 class FilterDesc(ctypes.Structure):

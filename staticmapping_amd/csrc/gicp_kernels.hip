@@ -66,28 +66,34 @@ __device__ __forceinline__ void sym_inverse(const double* a, double* o) {
 // the x-extent of a grid row is one contiguous run of the cell-sorted target (row_slots).  A shell ends the
 // search once the k-th distance is within the distance to the nearest unexplored face (block_guarantee).
 // cov is indexed by the point's position in the pair's raw target array (tq.w), so it survives grid rebuilds.
+// The neighbour set holds positions in the slot's raw target array.  For a target that position IS the caller's index
+// (keys == nullptr).  A source is searched through its scratch slot, whose raw array is the job's Morton-ordered source: there
+// the caller's index is what the w of the raw point holds (gicp_copy_points copies it with the point), and `keys` is that array.
+__device__ __forceinline__ int knn_caller_index(const float4* keys, int pos) { return keys ? __float_as_int(keys[pos].w) : pos; }
 // the slow path of gicp_knn_cov's neighbour set (ties at the set's largest distance; kept out of line so that the loop over
 // the slots does not end up in the hot path's registers): among the members at distance `w`, the slot of the one with the
 // largest caller index, and that index
 template <int KMAX>
-__device__ __noinline__ int knn_largest_index_at(const float (*s_d)[kGicpKnnThreads], const int (*s_j)[kGicpKnnThreads], int t, float w, int* slot) {
+__device__ __noinline__ int knn_largest_index_at(const float (*s_d)[kGicpKnnThreads], const int (*s_j)[kGicpKnnThreads], int t, float w, int* slot,
+                                                 const float4* keys) {
   int wo = -1, wp = 0;
-  for (int m = 0; m < KMAX; ++m) if (s_d[m][t] == w) { const int o = s_j[m][t]; if (o > wo) { wo = o; wp = m; } }
+  for (int m = 0; m < KMAX; ++m) if (s_d[m][t] == w) { const int o = knn_caller_index(keys, s_j[m][t]); if (o > wo) { wo = o; wp = m; } }
   *slot = wp;
   return wo;
 }
 
 struct GicpKnnBatch {
-  int32_t n, pad;
+  int32_t n;
+  uint32_t sources;                      // bit e: cloud e is a source in its scratch slot (ties go by the w of its raw points)
   int32_t slot[kGicpKnnJobs];            // pair slot whose TARGET is the cloud (a job's slot, or its scratch slot = the source)
   double* cov[kGicpKnnJobs];             // where its covariances go
 };
 
 // the neighbourhood and covariance of target point j0 (its sorted position) of pair slot `pair`; the workgroup's set columns
-// s_d / s_j are the caller's
+// s_d / s_j are the caller's; by_w: the cloud is a source in its scratch slot (see knn_caller_index)
 template <int KMAX>
 __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int j0, int k, double gicp_epsilon, double* cov,
-                                                 float (*s_d)[kGicpKnnThreads], int (*s_j)[kGicpKnnThreads]) {
+                                                 float (*s_d)[kGicpKnnThreads], int (*s_j)[kGicpKnnThreads], bool by_w) {
   const PairState* st = &b.state[pair];
   const int t = threadIdx.x;
   const float4* tq = b.tq + (size_t)pair * b.nt_cap;
@@ -95,6 +101,8 @@ __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int 
   const uint32_t* cstart = b.cstart + (size_t)pair * (b.nt_cap + 1);
   const uint32_t* rowbits = b.have_rowbits ? b.rowbits + (size_t)pair * kMaxRowWords : nullptr;
   const float4 q = tq[j0];
+  const float4* raw = b.tgt_p + (size_t)pair * b.nt_cap;
+  const float4* keys = by_w ? raw : nullptr;
 #pragma unroll
   for (int m = 0; m < KMAX; ++m) { s_d[m][t] = m < k ? INFINITY : -2.0f; s_j[m][t] = -1; }   // entries >= k never hold the maximum
   float worst = INFINITY;                     // the largest distance of the set ...
@@ -107,8 +115,8 @@ __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int 
     row_slots(words, rowbase, xa, xb, sa, sb);
     if (sa == sb) return;                       // empty stretch of the row (most of a large shell): no run to fetch
     const uint32_t pa = cstart[sa], pb = cstart[sb];
-    // The set is the k smallest by (distance, index in the caller's cloud).  Two candidates at the same float distance from the
-    // query are not rare enough to ignore (a 37 k-point submap had one point whose 20th and 21st neighbours tie): with "first
+    // The set is the k smallest by (float distance between the centred points, index in the caller's cloud), for a target and
+    // for a source alike.  Two candidates at the same float distance from the query are not rare enough to ignore (a 37 k-point submap had one point whose 20th and 21st neighbours tie): with "first
     // visited stays" the set -- and that point's covariance, by 2e-2 -- followed the order of the points inside a grid cell,
     // which the builds of these grids leave to their atomics.  Ties only cost when they happen: a candidate AT the set's
     // largest distance, or an eviction that leaves another member at the evicted one's distance, takes the slow path.
@@ -119,8 +127,8 @@ __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int 
       if (d == worst) {
         if (!(worst < INFINITY)) return;
         int wp2;                                          // the member at this distance with the largest index ...
-        const int wo = knn_largest_index_at<KMAX>(s_d, s_j, t, worst, &wp2);
-        if (co < wo) s_j[wp2][t] = co;                    // ... makes way for a candidate with a smaller one (same distance: worst, wpos stand)
+        const int wo = knn_largest_index_at<KMAX>(s_d, s_j, t, worst, &wp2, keys);
+        if (knn_caller_index(keys, co) < wo) s_j[wp2][t] = co;   // ... makes way for a candidate with a smaller one (same distance: worst, wpos stand)
         return;
       }
       const float old = worst;
@@ -138,8 +146,8 @@ __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int 
       if (w == old && old < INFINITY) {
         // another member sat at the evicted one's distance: of all of them the one with the largest index is the one to go
         int wp2;
-        const int wo = knn_largest_index_at<KMAX>(s_d, s_j, t, w, &wp2);
-        if (old_o < wo) s_j[wp2][t] = old_o;              // the evicted member comes back in that one's place
+        const int wo = knn_largest_index_at<KMAX>(s_d, s_j, t, w, &wp2, keys);
+        if (knn_caller_index(keys, old_o) < wo) s_j[wp2][t] = old_o;   // the evicted member comes back in that one's place
       }
       worst = w; wpos = wp;
     };
@@ -205,8 +213,7 @@ __device__ __forceinline__ void gicp_knn_cov_one(const IcpDev& b, int pair, int 
   // covariance of the k neighbours from the RAW coordinates; the products pt.x * pt.y are float products (:95-103)
   // The set's slots are filled in visiting order, which follows the order of the points inside a grid cell: summed slot by
   // slot the covariance would differ in its last bits between two builds of the same grid.  The neighbours (s_j holds their
-  // indices in the caller's cloud) are summed in index order instead: k passes over the k slots.
-  const float4* raw = b.tgt_p + (size_t)pair * b.nt_cap;
+  // positions in the slot's raw array) are summed in the order of those positions instead: k passes over the k slots.
   double mean[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
   int last = -1;
   int kv = 0;                                   // members actually summed
@@ -257,7 +264,7 @@ __global__ __launch_bounds__(kGicpKnnThreads) void gicp_knn_cov(IcpDev b, GicpKn
   const int pair = L.slot[blockIdx.y];
   const int j0 = blockIdx.x * kGicpKnnThreads + threadIdx.x;
   if (j0 >= b.state[pair].nt) return;
-  gicp_knn_cov_one<KMAX>(b, pair, j0, k, gicp_epsilon, L.cov[blockIdx.y], s_d, s_j);
+  gicp_knn_cov_one<KMAX>(b, pair, j0, k, gicp_epsilon, L.cov[blockIdx.y], s_d, s_j, (L.sources >> blockIdx.y) & 1u);
 }
 
 // Target covariances on demand.  A GICP run consumes the covariance of a target point only when a source point is matched to it
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(kGicpKnnThreads) void gicp_knn_cov_listed(IcpDev b,
   const uint32_t e = blockIdx.x * kGicpKnnThreads + threadIdx.x;
   if (e >= g.need_count[J.job]) return;
   const int j0 = g.need_list[(size_t)J.job * b.ns_cap + e];
-  gicp_knn_cov_one<KMAX>(b, J.job, j0, L.k, L.gicp_epsilon, g.cov_t + (size_t)J.job * b.nt_cap * 6, s_d, s_j);
+  gicp_knn_cov_one<KMAX>(b, J.job, j0, L.k, L.gicp_epsilon, g.cov_t + (size_t)J.job * b.nt_cap * 6, s_d, s_j, false);
 }
 
 // per source point: keep the correspondence if d2 < threshold^2 and store (R C1 R^T + C2)^-1 and the raw target point

@@ -50,6 +50,7 @@ struct GicpHost {
   PrepWorkspace* prep_avg = nullptr;  // workspace of the batched voxel filter: every job's raw source + target at once (allocated on first use)
   double* out_pinned = nullptr;       // [jobs][kGicpCols] doubles, then the finished round's number
   uint32_t* count_pinned = nullptr;   // [jobs]
+  uint32_t* need_pinned = nullptr;    // [jobs] target covariances the last correspondence step listed
   int evals = 0;                      // functor evaluations of the last single-job run (parity hooks)
   unsigned long long seq = 0;         // evaluation rounds launched so far: the number gicp_fdf stores after the last job's sums
 };
@@ -94,7 +95,8 @@ smhip_status gicp_ensure(smhip_context* h) {
   A(dev_alloc(h, &g.ds_tmp, std::max(NS, NT)));
   if (s) return s;
   if (hipHostMalloc(reinterpret_cast<void**>(&g.out_pinned), sizeof(double) * ((size_t)J * kGicpCols + 1)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&g.count_pinned), sizeof(uint32_t) * (size_t)J) != hipSuccess) {
+      hipHostMalloc(reinterpret_cast<void**>(&g.count_pinned), sizeof(uint32_t) * (size_t)J) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&g.need_pinned), sizeof(uint32_t) * (size_t)J) != hipSuccess) {
     h->err = "hipHostMalloc failed (GICP)";
     return SMHIP_ERR_HIP;
   }
@@ -160,6 +162,7 @@ struct GicpTask {
   enum Req { kStart, kCorr, kFdf, kDone } req = kStart;
   double TRcm[16], R9[9];             // kCorr: transformation_ * guess (column-major) and its rotation (row-major)
   uint32_t ncorr = 0;                 // ... answered with the kept correspondences
+  uint32_t ncov = 0;                  // target covariances estimated on demand so far (gicp_need's lists, summed over the steps)
   GicpPose P;                         // kFdf: the pose; answered in the job's row of out_pinned
   smhip_status status = SMHIP_OK;
   int evals = 0, it = 0;
@@ -475,6 +478,7 @@ smhip_status gicp_round(smhip_context* h, int first, int K, const std::vector<Gi
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(G.count_pinned + first, G.dev.count + first, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, h->stream));
+    if (!lazy.empty()) HIPCHK(h, hipMemcpyAsync(G.need_pinned + first, G.dev.need_count + first, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, h->stream));
   }
   unsigned long long seq = 0;
   if (!fdf.empty()) {
@@ -523,7 +527,10 @@ smhip_status gicp_round(smhip_context* h, int first, int K, const std::vector<Gi
     h->err = "GICP: a correspondence / functor launch failed";
     return SMHIP_ERR_HIP;
   }
-  for (GicpTask* t : corr) t->ncorr = G.count_pinned[t->job];
+  for (GicpTask* t : corr) {
+    t->ncorr = G.count_pinned[t->job];
+    if (!G.job[t->job].cov_full) t->ncov += G.need_pinned[t->job];
+  }
   return SMHIP_OK;
 }
 
@@ -533,7 +540,7 @@ void GicpTask::body() {
   float T[16], prev[16];                                   // transformation_, previous_transformation_
   for (int i = 0; i < 16; ++i) T[i] = prev[i] = (i % 5 == 0) ? 1.f : 0.f;
   GicpFunctor fn{this};
-  it = 0; evals = 0; ncorr = 0;
+  it = 0; evals = 0; ncorr = 0; ncov = 0;
   const bool dbg = std::getenv("SMHIP_GICP_DEBUG") != nullptr;
   for (;;) {
     // transform_R = transformation_ * guess in double (:425-429); the search uses the same product
@@ -653,7 +660,7 @@ smhip_status gicp_align_jobs(smhip_context* h, int first, int K, const char* run
       // the set's LDS footprint follows k (the default 20 fits 20 entries per thread: 20 KiB per workgroup instead of 32)
       if (k <= 20) hipLaunchKernelGGL(gicp_knn_cov<20>, dim3(ceil_div(nmax, kGicpKnnThreads), L.n), dim3(kGicpKnnThreads), 0, h->stream, dk, L, k, o.gicp_epsilon);
       else hipLaunchKernelGGL(gicp_knn_cov<kGicpKMax>, dim3(ceil_div(nmax, kGicpKnnThreads), L.n), dim3(kGicpKnnThreads), 0, h->stream, dk, L, k, o.gicp_epsilon);
-      L.n = 0; nmax = 0;
+      L.n = 0; L.sources = 0; nmax = 0;
     };
     // Target covariances.  A batch estimates them on demand (gicp_need / gicp_knn_cov_listed in the correspondence steps: a
     // twelfth of the neighbourhoods); a single Align estimates them all up front, as computeCovariances does (:391-402): the
@@ -683,7 +690,7 @@ smhip_status gicp_align_jobs(smhip_context* h, int first, int K, const char* run
         jh.cov_gen = h->tgt_gen[first + e]; jh.cov_k = k; jh.cov_eps = o.gicp_epsilon;
       }
       // the source's covariances: all of them, every Align (every source point is a query)
-      L.slot[L.n] = sfirst + e; L.cov[L.n] = G.dev.cov_s + (size_t)(first + e) * h->dev.ns_cap * 6; ++L.n;
+      L.slot[L.n] = sfirst + e; L.cov[L.n] = G.dev.cov_s + (size_t)(first + e) * h->dev.ns_cap * 6; L.sources |= 1u << L.n; ++L.n;
       nmax = std::max(nmax, h->ns[first + e]);
       if (L.n == kGicpKnnJobs) flush();
     }
@@ -704,7 +711,7 @@ smhip_status gicp_align_jobs(smhip_context* h, int first, int K, const char* run
     if (!run[e]) continue;
     const GicpTask& t = tasks[e];
     for (int i = 0; i < 16; ++i) fin[16 * e + i] = t.fin[i];
-    if (stats) { stats[e].gicp_iterations = t.it; stats[e].gicp_function_evaluations = t.evals; stats[e].gicp_correspondences = (int32_t)t.ncorr; }
+    if (stats) { stats[e].gicp_iterations = t.it; stats[e].gicp_function_evaluations = t.evals; stats[e].gicp_correspondences = (int32_t)t.ncorr; stats[e].gicp_covariances_on_demand = (int32_t)t.ncov; }
     G.evals = t.evals;
   }
   return SMHIP_OK;
@@ -1029,6 +1036,8 @@ smhip_status smhip_gicp_evaluate(smhip_handle h, const double guess[16], const d
   if (s) return s;
   const double* o = g.out_pinned;
   const double m = o[13];
+  // (a run that kept no correspondence ends before its first evaluation, :494-498; here the division would hand back NaN)
+  if (!(m > 0)) { h->err = "GICP: the last correspondence step kept no correspondence, the functor is undefined"; return SMHIP_ERR_NO_MATCH; }
   *f = o[0] / m;
   for (int i = 0; i < 3; ++i) grad[i] = o[1 + i] * (2.0 / m);
   double R[9];
@@ -1109,6 +1118,7 @@ extern "C" void smhip_internal_free_gicp(smhip_context* h) {
   GicpHost& g = h->gicp->g;
   if (g.out_pinned) (void)hipHostFree(g.out_pinned);
   if (g.count_pinned) (void)hipHostFree(g.count_pinned);
+  if (g.need_pinned) (void)hipHostFree(g.need_pinned);
   if (g.prep_avg) prep_destroy(g.prep_avg);
   delete h->gicp;
   h->gicp = nullptr;
