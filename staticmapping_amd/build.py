@@ -62,19 +62,25 @@ def _stale(unit: str) -> bool:
 
 
 def build_shard_driver(force: bool = False, verbose: bool = False) -> str:
-    """The C++ host program of BASELINE config #4: links libsmhip.so + librccl.so (no device code of its own)."""
-    src = os.path.join(CSRC, "shard_driver.cc")
-    deps = [src, os.path.join(ROOT, "include", "smhip.h"), os.path.join(ROOT, "include", "smhip", "kitti_scans.h"),
-            os.path.join(ROOT, "include", "smhip", "pcd.h"), os.path.join(ROOT, "include", "smhip", "back_end.h"), os.path.join(ROOT, "include", "smhip", "pose_graph.h"),
-            os.path.join(ROOT, "include", "smhip", "submap.h"), os.path.join(ROOT, "include", "smhip", "map_package.h"),
-            os.path.join(ROOT, "include", "smhip", "registrator.h"), LIB_PATH]
-    if not force and os.path.exists(SHARD_EXE) and all(os.path.getmtime(d) <= os.path.getmtime(SHARD_EXE) for d in deps):
-        return SHARD_EXE
-    cmd = [_hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", SHARD_EXE,
+    """The C++ host program of BASELINE config #4: links libsmhip.so + librccl.so (no device code of its own).  One command compiles and
+    links it; it runs again when a file its dependency file names, or the library, is newer than the program."""
+    unit = "shard_driver.cc"
+    deps = unit_deps(unit)
+    if not force and deps and os.path.exists(SHARD_EXE):
+        t = os.path.getmtime(SHARD_EXE)
+        if all(os.path.exists(p) and os.path.getmtime(p) <= t for p in deps + [LIB_PATH]):
+            return SHARD_EXE
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    cmd = [_hipcc(), "-O2", "-std=c++17", "-I", "include", os.path.relpath(os.path.join(CSRC, unit), ROOT), "-o", SHARD_EXE, "-MD", "-MF", dep_path(unit),
            "-L", LIB_DIR, "-lsmhip", "-L", "/opt/rocm/lib", "-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    try:
+        subprocess.check_call(cmd, cwd=ROOT)
+    except BaseException:
+        if os.path.exists(dep_path(unit)):          # no dependency file without the program it describes
+            os.remove(dep_path(unit))
+        raise
     return SHARD_EXE
 
 

@@ -15,40 +15,9 @@
 // All arithmetic happens behind the C ABI of include/smhip.h; the gather is ncclAllGather on the doubles
 // smhip_icp_export_results_device leaves in device memory -- the poses never visit the host before the collective.
 //
-// --map PATH: the static map of MapBuilder::SaveMaps (builder/map_builder.cc:825-910).  Once kitti_pose.txt is written and the
-// matchers are gone, rank 0 reads the scans again in order and inserts frame k under pose k into one device
-// MultiResolutionVoxelMap (ApplyTransformToOutput on the device, origin = the pose's translation), then writes PATH as a PCD
-// file with rows in voxel-key order.  The poses are the ones AS WRITTEN to the pose file (8 significant digits, parsed back),
-// so the map is a function of that file: --map-poses FILE builds the same map, byte for byte, with no alignment, no RCCL and
-// one process -- also from poses that came from elsewhere.
-//
-// --close-loops PATH: the pose graph over those submaps (MapBuilder::ConnectAllSubmap, builder/map_builder.cc:448-613): every submap
-// with its device descriptor goes through back_end::IsamOptimizer (smhip/pose_graph.h: the loop detector, consecutive matches as
-// odometry factors, loop edges, one device solve per update), and the frames' corrected poses are written to PATH in the pose
-// writer's format, one line per frame -- so --map --map-poses PATH builds the corrected map.  The detector's settings are the
-// --loop-* flags (back_end/loop_detector_options.h:29-40).  Without the flag nothing of this runs and every output is what it was.
-// With --gps-enu FILE (one line per scan in file order: east north up in metres, nan = no fix; the geodetic conversion is not
-// restated) a submap carries the fix of its first frame and IsamOptimizer adds the GPS / ENU factors of isam_optimizer.cc:238-349
-// (--gps-lever x,y,z: the antenna in the tracking frame; --gps-init-num, --gps-sample-step, --gps-init-angle: isam_optimizer.h:61-66);
-// --gps-output-enu premultiplies every submap pose by GetGpsCoordTransform() before UpdateInnerFramePose (map_builder.cc:748-762),
-// so PATH is in the ENU frame.  --gps-enu without --close-loops, or a FILE whose line count is not the scan count, ends the run
-// with exit 2 before any device work.
-//
-// --map-package DIR: the map package of MapBuilder::SaveMapPackage (builder/map_builder.cc:816-823, builder/map_package.cc): the
-// static map cut into overlapping square pieces, DIR/<prefix><x>_<y>.pcd centred on the piece and DIR/map_package.xml listing them
-// (smhip/map_package.h).  Like --map it is a function of the pose file as written, so --map-poses FILE builds it too -- also from the
-// file --close-loops wrote.  Frames [kN, (k + 1)N) form submap k (--submap-frames N; a trailing group that is not full is dropped),
-// built once on the device at --submap-voxel with local poses first^-1 * frame; its global pose is its first frame's.  The pieces'
-// voxel maps take the --map-* settings.
-//
-// --submap-edges PATH: the submaps of the sequence and the match of every pair of consecutive ones (Submap::InsertFrame,
-// builder/submap.cc:76-163; MapBuilder::SubmapPairMatch, builder/map_builder.cc:399-446).  Like --map, rank 0 works from the poses
-// AS WRITTEN to the pose file once the matchers are gone.  Frames [kN, (k + 1)N) form submap k (--submap-frames N); a trailing
-// group that is not full has no cloud (submap.cc:98) and is dropped.  Each submap is built on the device from its raw scans
-// (smhip_submap_build_f32: local pose = first pose^-1 * pose, VoxelGrid of --submap-voxel, 0 = none) and never leaves it: it
-// becomes the source against the previous submap's CalculateNormals target, then the target of the next.  IcpFast runs under
-// --iterations and --early-exit.  PATH holds one line per edge: `k k+1 accepted score` and the twelve numbers of
-// transform_to_next in the pose writer's format -- the match when score >= --submap-min-score, else the guess (:436-444).
+// This file: the arguments, the id exchange, the alignment run (RunRank) and the launcher.  What rank 0 does after the run (--map,
+// --submap-edges, --close-loops, --map-package) is shard_passes.h, each flag described at its pass; the poses, their product and the
+// pose file's lines are shard_poses.h.
 #include <dirent.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -58,69 +27,13 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <cstdarg>
-#include <chrono>
-#include <condition_variable>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../include/smhip.h"
-#include "../../include/smhip/kitti_scans.h"
-#include "../../include/smhip/pcd.h"
-#include "../../include/smhip/back_end.h"
-#include "../../include/smhip/pose_graph.h"
-#include "../../include/smhip/map_package.h"
+#include "shard_passes.h"     // (and the standard headers)
 
 namespace {
 
+using namespace shard;
+
 constexpr int kPoseDoubles = 18;                 // 16 column-major transform + score + iterations
-using smhip::kitti::kMaxFloatsPerFile;
-using smhip::kitti::ScanPrefetcher;
-
-struct Args {
-  std::string scans_dir, out_path = "kitti_pose.txt", id_file;
-  unsigned long long nonce = 0;             // identifies this run's id file (launcher: pid and start time; else MASTER_PORT)
-  int gpus = 1, rank = -1, world = -1, local_rank = -1;
-  int batch = 256, iterations = 20, early_exit = 0, max_pairs = -1, readers = 8, matchers = 1, warmup = 1, parts = 0;
-  double guess_tx = 0.0;
-  bool quiet = false;
-  // the static map (--map); the MRVM settings are MrvmSettings' (multi_resolution_voxel_map.h:54-65), whose defaults these are
-  std::string map_path, map_poses;
-  int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
-  float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
-  bool map_average = false, map_rgb = false;
-  // the map package (--map-package); defaults: MapPackageOptions, builder/map_package.h:36-41
-  std::string map_package;
-  smhip::MapPackageOptions package;
-  // consecutive submaps (--submap-edges); defaults: builder/submap_options.h:30-38 and accepted_min_score of the configs
-  std::string submap_edges;
-  int submap_frames = 5;
-  float submap_voxel = 0.1f, submap_min_score = 0.7f;
-  // --close-loops: the pose graph over those submaps; the detector's settings (back_end/loop_detector_options.h:29-40), with the
-  // descriptor gate on as in the shipped KITTI config
-  std::string close_loops;
-  smhip::back_end::LoopDetectorSettings loop = [] { smhip::back_end::LoopDetectorSettings s; s.use_descriptor = true; return s; }();
-  // --gps-enu FILE: one line per scan in file order, three numbers already in ENU metres, nan = no fix (the geodetic conversion is
-  // not restated); the factors' settings (isam_optimizer.h:61-66) and the antenna in the tracking frame
-  std::string gps_enu;
-  std::vector<std::array<double, 3>> enu;
-  double gps_lever[3] = {0.0, 0.0, 0.0};
-  int gps_init_num = 25, gps_sample_step = 1;
-  double gps_init_angle = 1.6;
-  bool gps_output_enu = false;
-};
-
-[[noreturn]] void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
 
 #define HIPOK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) Die(std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
 #define NCCLOK(e) do { ncclResult_t r_ = (e); if (r_ != ncclSuccess) Die(std::string(#e) + ": " + ncclGetErrorString(r_)); } while (0)
@@ -136,13 +49,6 @@ std::vector<std::string> ListScans(const std::string& dir) {            // kitti
   closedir(d);
   std::sort(files.begin(), files.end());
   return files;
-}
-
-void Mul4(const double* a, const double* b, double* out) {              // row-major 4x4
-  double r[16];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += a[4 * i + k] * b[4 * k + j]; r[4 * i + j] = s; }
-  std::memcpy(out, r, sizeof(r));
 }
 
 // --gps-enu FILE into a->enu, before any device work: a line per scan of the listing, or the run ends here
@@ -303,536 +209,6 @@ ncclUniqueId ExchangeId(const Args& a, int rank) {
   Die("timed out waiting for " + a.id_file + " (no file with this run's nonce appeared)");
 }
 
-std::string Fmt(const char* fmt, ...) {
-  va_list ap, aq;
-  va_start(ap, fmt);
-  va_copy(aq, ap);
-  const int n = std::vsnprintf(nullptr, 0, fmt, ap);
-  va_end(ap);
-  std::string out(static_cast<size_t>(std::max(n, 0)) + 1, '\0');
-  std::vsnprintf(&out[0], out.size(), fmt, aq);
-  va_end(aq);
-  out.resize(static_cast<size_t>(std::max(n, 0)));
-  return out;
-}
-
-// kitti_pose.txt (map_builder.cc:626-641): 12 numbers per line, the row-major top 3x4 -> column-major 4x4.  Reading stops at the
-// first line that does not hold 12 numbers.  false: the file cannot be opened.
-using Pose = std::array<double, 16>;
-bool ReadPoses(const std::string& path, std::vector<Pose>* poses) {
-  std::ifstream f(path);
-  if (!f) return false;
-  std::string text;
-  while (std::getline(f, text)) {
-    double v[12];
-    const char* p = text.c_str();
-    int got = 0;
-    for (; got < 12; ++got) {
-      char* end = nullptr;
-      v[got] = std::strtod(p, &end);
-      if (end == p) break;
-      p = end;
-    }
-    if (got < 12) break;
-    Pose m{};
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m[4 * c + r] = v[4 * r + c];
-    m[15] = 1.0;
-    poses->push_back(m);
-  }
-  return true;
-}
-
-// the frames --map inserts: 0, K, 2K, ... below n_frames (--map-every K stands in for the reference's key-frame selection)
-std::vector<int> MapFrames(const Args& a, int n_frames) {
-  std::vector<int> v;
-  for (int k = 0; k < n_frames; k += a.map_every) v.push_back(k);
-  return v;
-}
-
-struct MapResult { int frames = 0, parts = 0; long long voxels = 0, points = 0; double seconds = 0.0; };
-
-std::string MapJsonFields(const Args& a, const MapResult& m) {
-  return Fmt(", \"map_file\": \"%s\", \"map_frames\": %d, \"map_voxels\": %lld, \"map_points\": %lld, \"map_parts\": %d, \"map_seconds\": %.4f, "
-             "\"map_ms_per_frame\": %.3f", a.map_path.c_str(), m.frames, m.voxels, m.points, m.parts, m.seconds,
-             m.frames > 0 ? 1e3 * m.seconds / m.frames : 0.0);
-}
-
-// SaveMaps (map_builder.cc:825-910) over `frames`: frame k's raw rows (intensity x 255, kitti_reader.cc:113) inserted under
-// poses[k] into one device map.  --map-part-every N writes <stem>_part_<i>.pcd after every N inserted frames and starts a fresh
-// map (separate_output / separate_step, :860-890, counted in frames rather than submaps); otherwise the whole map goes to --map
-// PATH.  Every file has its rows in voxel-key order (SMHIP_MRVM_SORTED).  Returns 0, or 3 when the map refused a frame: the
-// files of this run are then removed.  map_voxels / map_points are summed over the parts.
-int BuildMap(const Args& a, const std::vector<std::string>& files, const std::vector<int>& frames, const std::vector<Pose>& poses, int device,
-             MapResult* res) {
-  const auto t0 = std::chrono::steady_clock::now();
-  size_t max_bytes = 16;
-  for (int k : frames) { struct stat sb; if (stat(files[k].c_str(), &sb) == 0) max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
-  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
-  smhip_mrvm_settings set;
-  smhip_mrvm_default_settings(&set);
-  set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution; set.hit_prob = a.map_hit; set.miss_prob = a.map_miss;
-  set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
-  const int flags = SMHIP_MRVM_SORTED | (a.map_average ? SMHIP_MRVM_AVERAGE : 0) | (a.map_rgb ? SMHIP_MRVM_RGB : 0);
-  std::string stem = a.map_path;
-  if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".pcd") == 0) stem.resize(stem.size() - 4);
-  std::vector<std::string> written;
-  smhip_mrvm_handle h = nullptr;
-  auto fresh_map = [&]() {
-    if (h) smhip_mrvm_destroy(h);
-    h = nullptr;
-    const smhip_status st = smhip_mrvm_create(device, std::min(22, a.map_max_table_log2), static_cast<int>(slot_floats / 4), &set, &h);
-    if (st != SMHIP_OK) Die(std::string("smhip_mrvm_create: ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
-    if (smhip_mrvm_set_max_table_log2(h, a.map_max_table_log2) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
-  };
-  auto write_map = [&](const std::string& path) {     // OutputToPointCloud(threshold, filename), multi_resolution_voxel_map.cc:217-242
-    int v = 0, n = 0, m = 0;
-    if (smhip_mrvm_voxel_count(h, &v) != SMHIP_OK || smhip_mrvm_output_ex(h, a.map_threshold, flags, nullptr, 0, &n) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
-    std::vector<float> rows(4 * static_cast<size_t>(n));
-    if (n > 0 && smhip_mrvm_output_ex(h, a.map_threshold, flags, rows.data(), n, &m) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
-    if (m != n) Die("map: output changed size between two calls");
-    res->voxels += v;
-    if (smhip::pcd::SaveBinary(path, n > 0 ? rows.data() : nullptr, static_cast<size_t>(n), a.map_rgb)) {
-      written.push_back(path);
-      res->points += n;
-      ++res->parts;
-    }
-  };
-  fresh_map();
-  smhip::kitti::ScanPrefetcher scans(files, frames, a.readers, 2 * std::max(1, a.readers) + 2, /*hold_until_release=*/false, slot_floats);
-  int in_part = 0, part = 0, rc = 0;
-  for (size_t i = 0; i < frames.size(); ++i) {
-    int n = 0, fi = -1;
-    const float* rows = scans.Next(&n, &fi);
-    if (!rows || fi != frames[i]) Die("map: prefetcher out of step");
-    if (n < 0) Die("cannot read " + files[fi]);
-    if (n == 0) {
-      std::fprintf(stderr, "smhip_shard: map: %s is empty, skipped\n", files[fi].c_str());     // InsertPointCloud: "cloud is empty.", :61-64
-    } else {
-      const smhip_status st = smhip_mrvm_insert_transformed_f32(h, rows, 4, n, poses[fi].data(), 255.f);
-      if (st != SMHIP_OK) {
-        std::fprintf(stderr, "smhip_shard: map: frame %d refused: %s\n", fi, smhip_mrvm_last_error(h));
-        rc = 3;
-        break;
-      }
-      if (smhip_mrvm_last_error(h)[0]) std::fprintf(stderr, "smhip_shard: map: frame %d: %s\n", fi, smhip_mrvm_last_error(h));
-    }
-    ++res->frames;
-    if (a.map_part_every > 0 && ++in_part == a.map_part_every) {
-      write_map(stem + "_part_" + std::to_string(part++) + ".pcd");
-      fresh_map();
-      in_part = 0;
-    }
-  }
-  if (rc == 0) {
-    if (a.map_part_every == 0) write_map(a.map_path);
-    else if (in_part > 0) write_map(stem + "_part_" + std::to_string(part) + ".pcd");
-  } else {
-    for (const auto& f : written) std::remove(f.c_str());
-  }
-  smhip_mrvm_destroy(h);
-  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-// ---- --submap-edges -------------------------------------------------------------------------------------------------------
-// inverse of an affine 4x4 (column-major), what Eigen's inverse() gives for a pose: the 3x3 block by its adjugate
-Pose AffineInverse(const Pose& p) {
-  auto m = [&](int r, int c) { return p[4 * c + r]; };
-  const double c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1), c01 = m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2), c02 = m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0);
-  const double det = m(0, 0) * c00 + m(0, 1) * c01 + m(0, 2) * c02;
-  double inv[3][3] = {{c00 / det, (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) / det, (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) / det},
-                      {c01 / det, (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) / det, (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) / det},
-                      {c02 / det, (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) / det, (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) / det}};
-  Pose out{};
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) out[4 * c + r] = inv[r][c];
-    out[12 + r] = -(inv[r][0] * m(0, 3) + inv[r][1] * m(1, 3) + inv[r][2] * m(2, 3));
-  }
-  out[15] = 1.0;
-  return out;
-}
-Pose MulPose(const Pose& a, const Pose& b) {                              // column-major a * b
-  Pose out{};
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) { double s = 0; for (int k = 0; k < 4; ++k) s += a[4 * k + r] * b[4 * c + k]; out[4 * c + r] = s; }
-  return out;
-}
-
-struct SubmapResult { int submaps = 0, edges = 0, accepted = 0; double seconds = 0.0, score_sum = 0.0; };
-
-std::string SubmapJsonFields(const Args& a, const SubmapResult& m) {
-  return Fmt(", \"submap_edges_file\": \"%s\", \"submaps\": %d, \"submap_edges\": %d, \"submap_edges_accepted\": %d, \"submap_mean_score\": %.6f, "
-             "\"submap_seconds\": %.4f", a.submap_edges.c_str(), m.submaps, m.edges, m.accepted, m.edges > 0 ? m.score_sum / m.edges : 0.0, m.seconds);
-}
-
-// The submaps of frames [0, n_frames) under `poses` and the match of consecutive ones; one line per edge to --submap-edges.
-// Returns 0, or 3 when the device refused a submap (the file is then removed).
-int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, SubmapResult* res) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
-  std::ofstream out(a.submap_edges);
-  if (!out) Die("cannot write " + a.submap_edges);
-  out.precision(8);
-  res->submaps = S;
-  if (S < 2) { res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); return 0; }
-  // capacity: the largest submap's rows together (every scan of a group is read whole)
-  long long cap = 16;
-  size_t max_bytes = 16;
-  for (int k = 0; k < S; ++k) {
-    long long rows = 0;
-    for (int f = k * N; f < (k + 1) * N; ++f) {
-      struct stat sb;
-      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
-    }
-    cap = std::max(cap, rows);
-  }
-  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
-  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
-  smhip_handle h = nullptr;
-  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
-  if (st != SMHIP_OK) Die(std::string("smhip_create (submaps): ") + smhip_status_string(st));
-  smhip_icp_options o;
-  smhip_icp_default_options(&o);
-  o.max_iteration = a.iterations;
-  o.early_exit = a.early_exit;
-  if (smhip_icp_set_options(h, &o) != SMHIP_OK) Die(smhip_last_error(h));
-  // the six-decimal trip of the voxel size through the filter's text (submap.cc:148-154)
-  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
-
-  std::vector<int> order(static_cast<size_t>(S) * N);
-  for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
-  smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
-  int rc = 0;
-  for (int k = 0; k < S && rc == 0; ++k) {
-    std::vector<const float*> rows(N);
-    std::vector<int> n(N);
-    std::vector<double> local(16 * static_cast<size_t>(N));
-    const Pose first_inv = AffineInverse(poses[k * N]);
-    for (int f = 0; f < N; ++f) {
-      int fi = -1;
-      rows[f] = scans.Next(&n[f], &fi);
-      if (!rows[f] || fi != k * N + f) Die("submaps: prefetcher out of step");
-      if (n[f] < 0) Die("cannot read " + files[fi]);
-      const Pose lp = f == 0 ? Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} : MulPose(first_inv, poses[k * N + f]);   // submap.cc:83-87
-      std::memcpy(&local[16 * static_cast<size_t>(f)], lp.data(), sizeof(double) * 16);
-    }
-    int m = 0;
-    st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
-    scans.ReleaseHeld();                                                  // the call returned: the rows have left the host buffers
-    if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-    if (k > 0) {
-      // SubmapPairMatch(source = submap k, target = submap k - 1), map_builder.cc:399-446
-      if (smhip_filter_output_to_source(h, 0) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as source: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-      const Pose guess = MulPose(AffineInverse(poses[(k - 1) * N]), poses[k * N]);                  // :426-428
-      double result[16], score = 0.0;
-      smhip_icp_stats stats;
-      st = smhip_icp_align(h, guess.data(), result, &score, &stats);
-      if (st != SMHIP_OK) {                                              // no correspondence: an edge that keeps the guess
-        std::fprintf(stderr, "smhip_shard: submaps %d -> %d: %s (%s)\n", k - 1, k, smhip_status_string(st), smhip_last_error(h));
-        score = 0.0;
-      }
-      smhip::registrator::Matrix4d T;
-      std::memcpy(T.data(), result, sizeof(result));
-      smhip::back_end::NormalizeRotation(T);                             // :434
-      const bool accepted = st == SMHIP_OK && score >= a.submap_min_score;                           // :436-444
-      const double* e = accepted ? T.data() : guess.data();
-      out << (k - 1) << " " << k << " " << (accepted ? 1 : 0) << " " << score;
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out << " " << e[4 * c + r];
-      out << "\n";
-      ++res->edges; res->accepted += accepted ? 1 : 0; res->score_sum += score;
-    }
-    // the cloud is still resident: it becomes the target of the next pair (Submap::Cloud() carries normals, submap.cc:160-161)
-    if (k + 1 < S && smhip_filter_output_to_target(h, 0, &m) != SMHIP_OK) {
-      std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h));
-      rc = 3;
-    }
-  }
-  out.close();
-  smhip_destroy(h);
-  if (rc != 0) std::remove(a.submap_edges.c_str());
-  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-// ---- --map-package ----------------------------------------------------------------------------------------------------------
-struct PackageResult { int pieces = 0, submaps = 0; long long points = 0; double seconds = 0.0; };
-
-std::string PackageJsonFields(const Args& a, const PackageResult& m) {
-  return Fmt(", \"package_dir\": \"%s\", \"package_pieces\": %d, \"package_submaps\": %d, \"package_points\": %lld, \"package_seconds\": %.4f",
-             a.map_package.c_str(), m.pieces, m.submaps, m.points, m.seconds);
-}
-
-// The submaps of frames [0, n_frames) under `poses`, each built once on the device and downloaded, then
-// smhip::SaveTrajectoriesAsMapPackage over them.  The plan is made from the poses alone before any device work: a refused plan ends
-// the run with 2, and so does a directory the description cannot be written into.  Returns 0, or 3 when the device refused a submap or
-// an insert or a piece could not be written (this run's files are then removed).
-int BuildMapPackage(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, PackageResult* res) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
-  if (S < 1) Die("--map-package: " + std::to_string(n_frames) + " frames hold no full submap of " + std::to_string(N));
-  {
-    std::vector<std::array<double, 3>> translations(static_cast<size_t>(S));
-    for (int k = 0; k < S; ++k) translations[k] = {poses[k * N][12], poses[k * N][13], poses[k * N][14]};
-    smhip::MapPackagePlan plan;
-    std::string why;
-    if (!smhip::PlanMapPackage(translations, a.package, &plan, &why)) Die("--map-package refused: " + why);
-  }
-  std::string dir = a.map_package;
-  if (dir.back() != '/') dir += '/';
-  // the description's place is taken before any device work: a directory that is missing or cannot be written ends the run here
-  if (!std::ofstream(dir + a.package.descript_filename)) Die("cannot write " + dir + a.package.descript_filename);
-  long long cap = 16;
-  size_t max_bytes = 16;
-  for (int k = 0; k < S; ++k) {
-    long long rows = 0;
-    for (int f = k * N; f < (k + 1) * N; ++f) {
-      struct stat sb;
-      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
-    }
-    cap = std::max(cap, rows);
-  }
-  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
-  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
-  smhip_handle h = nullptr;
-  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
-  if (st != SMHIP_OK) Die(std::string("smhip_create (map package): ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
-  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
-  std::vector<smhip::MapPackageSubmap> submaps(static_cast<size_t>(S));
-  int rc = 0;
-  {
-    std::vector<int> order(static_cast<size_t>(S) * N);
-    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
-    smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
-    for (int k = 0; k < S && rc == 0; ++k) {
-      std::vector<const float*> rows(N);
-      std::vector<int> n(N);
-      std::vector<double> local(16 * static_cast<size_t>(N));
-      const Pose first_inv = AffineInverse(poses[k * N]);
-      for (int f = 0; f < N; ++f) {
-        int fi = -1;
-        rows[f] = scans.Next(&n[f], &fi);
-        if (!rows[f] || fi != k * N + f) Die("map package: prefetcher out of step");
-        if (n[f] < 0) Die("cannot read " + files[fi]);
-        const Pose lp = f == 0 ? Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} : MulPose(first_inv, poses[k * N + f]);   // submap.cc:83-87
-        std::memcpy(&local[16 * static_cast<size_t>(f)], lp.data(), sizeof(double) * 16);
-      }
-      int m = 0;
-      st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
-      scans.ReleaseHeld();
-      if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-      smhip::MapPackageSubmap& sub = submaps[static_cast<size_t>(k)];
-      std::memcpy(sub.global_pose.data(), poses[k * N].data(), sizeof(double) * 16);
-      sub.cloud.resize(static_cast<size_t>(m));
-      if (m > 0 && smhip_filter_get_output(h, &sub.cloud[0].x, nullptr, m) != SMHIP_OK) {
-        std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break;
-      }
-    }
-  }
-  smhip_destroy(h);
-  if (rc == 0) {
-    smhip::MrvmSettings set;
-    set.output_average = a.map_average; set.output_rgb = a.map_rgb; set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution;
-    set.hit_prob = a.map_hit; set.miss_prob = a.map_miss; set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
-    smhip::MapPackageResult pr;
-    // raw KITTI rows: intensity x 255 on the way into the map, as --map inserts them (kitti_reader.cc:113)
-    if (!smhip::SaveTrajectoriesAsMapPackage(submaps, a.package, set, dir, &pr, device, 255.f, a.map_max_table_log2)) rc = 3;
-    res->pieces = pr.pieces; res->submaps = pr.submaps; res->points = pr.points;
-  } else {
-    std::remove((dir + a.package.descript_filename).c_str());
-  }
-  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-// ---- --close-loops ------------------------------------------------------------------------------------------------------------
-struct LoopResult {
-  int submaps = 0, loop_edges = 0, solves = 0, stop_reason = 0; double seconds = 0.0, final_cost = 0.0, moved_m = 0.0;
-  int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
-};
-
-std::string GpsJsonFields(const Args& a, const LoopResult& m) {
-  if (a.gps_enu.empty()) return "";
-  std::string s = Fmt(", \"gps_factors\": %d, \"gps_coord\": [", m.gps_factors);
-  for (int q = 0; q < 16; ++q) s += Fmt("%.17g%s", m.gps_coord[q], q == 15 ? "]" : ", ");
-  return s;
-}
-
-std::string LoopJsonFields(const Args& a, const LoopResult& m) {
-  return Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
-             "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), m.submaps,
-             m.loop_edges, m.solves, m.stop_reason, m.final_cost, m.moved_m, m.seconds) + GpsJsonFields(a, m);
-}
-
-// MapBuilder::ConnectAllSubmap (builder/map_builder.cc:448-613) over the submaps --submap-edges builds, from the poses as written:
-// every submap is built on the device, described where it lies (M2DP), matched against the previous one (the odometry factor:
-// the match when its score reaches --submap-min-score, else the guess) and handed to back_end::IsamOptimizer -- the loop detector,
-// the factors, one device solve of the pose graph per update, every submap's pose written back.  A submap enters at the previous
-// submap's corrected pose times its odometry factor.  After RunFinalOptimazation the frames get submap pose x local pose
-// (Submap::UpdateInnerFramePose) and go to --close-loops in the pose writer's format, one line per frame of the sequence (the
-// frames of a trailing group that is not full ride on the last submap), so --map-poses on that file builds the corrected map.
-// Returns 0, or 3 when the device refused something (the file is then removed).
-int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, LoopResult* res) {
-  namespace be = smhip::back_end;
-  namespace bld = smhip::builder;
-  using smhip::registrator::Matrix4d;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int N = a.submap_frames, S = n_frames / N;
-  res->submaps = S;
-  std::ofstream out(a.close_loops);
-  if (!out) Die("cannot write " + a.close_loops);
-  out.precision(8);
-  auto write_pose = [&out](const double* m) {                             // column-major in, the top 3 x 4 row by row out
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out << m[4 * c + r] << ((r == 2 && c == 3) ? "\n" : " ");
-  };
-  if (S < 1) {
-    for (int f = 0; f < n_frames; ++f) write_pose(poses[f].data());
-    res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return 0;
-  }
-  long long cap = 16;
-  size_t max_bytes = 16;
-  for (int k = 0; k < S; ++k) {
-    long long rows = 0;
-    for (int f = k * N; f < (k + 1) * N; ++f) {
-      struct stat sb;
-      if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
-    }
-    cap = std::max(cap, rows);
-  }
-  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
-  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
-  smhip_handle h = nullptr;
-  smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
-  if (st != SMHIP_OK) Die(std::string("smhip_create (loop closing): ") + smhip_status_string(st));
-  smhip_icp_options o;
-  smhip_icp_default_options(&o);
-  o.max_iteration = a.iterations;
-  o.early_exit = a.early_exit;
-  if (smhip_icp_set_options(h, &o) != SMHIP_OK) Die(smhip_last_error(h));
-  const float voxel = a.submap_voxel > 0.f ? static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str())) : 0.f;
-  smhip_m2dp_options mo;
-  smhip_m2dp_default_options(&mo);
-  const int dlen = smhip_m2dp_length(&mo);
-
-  be::LoopDetectorSettings settings = a.loop;
-  settings.device = device;
-  int rc = 0;
-  {
-    be::IsamOptimizerOptions io;
-    io.use_gps = !a.gps_enu.empty();
-    io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
-    be::IsamOptimizer optimizer(io, settings, h);
-    {
-      Matrix4d tracking_to_gps = Matrix4d::Identity();
-      for (int c = 0; c < 3; ++c) tracking_to_gps(c, 3) = a.gps_lever[c];
-      optimizer.SetTransformTrackingToGps(tracking_to_gps);
-    }
-    std::vector<std::shared_ptr<bld::Submap>> maps;
-    std::vector<std::shared_ptr<be::LoopFrame>> frames;
-    bld::SubmapOptions so;
-    so.frame_count = N;
-    const smhip::data::InnerCloudType::Ptr no_points(new smhip::data::InnerCloudType);   // the Submap objects keep the poses' books only
-    std::vector<int> order(static_cast<size_t>(S) * N);
-    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
-    smhip::kitti::ScanPrefetcher scans(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, slot_floats);
-    for (int k = 0; k < S && rc == 0; ++k) {
-      std::vector<const float*> rows(N);
-      std::vector<int> n(N);
-      std::vector<double> local(16 * static_cast<size_t>(N));
-      maps.emplace_back(new bld::Submap(so));
-      for (int f = 0; f < N; ++f) {
-        int fi = -1;
-        rows[f] = scans.Next(&n[f], &fi);
-        if (!rows[f] || fi != k * N + f) Die("loop closing: prefetcher out of step");
-        if (n[f] < 0) Die("cannot read " + files[fi]);
-        Matrix4d P;
-        std::memcpy(P.data(), poses[k * N + f].data(), sizeof(double) * 16);
-        maps.back()->InsertFrame(no_points, P);
-        std::memcpy(&local[16 * static_cast<size_t>(f)], maps.back()->LocalPose(f).data(), sizeof(double) * 16);   // submap.cc:83-87
-      }
-      int m = 0;
-      st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local.data(), voxel, &m);
-      scans.ReleaseHeld();
-      if (st != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-      std::shared_ptr<be::LoopFrame> frame(new be::LoopFrame);
-      frame->descriptor.resize(static_cast<size_t>(dlen));
-      if (smhip_m2dp_from_filter_output(h, &mo, frame->descriptor.data(), dlen) != SMHIP_OK) {
-        std::fprintf(stderr, "smhip_shard: descriptor of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break;
-      }
-      {   // the cloud CloseLoop matches (Submap::Cloud(): normals calculated, submap.cc:160-161)
-        std::vector<smhip::data::InnerPointType> pts(static_cast<size_t>(m));
-        if (smhip_filter_get_output(h, &pts[0].x, nullptr, m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-        frame->cloud.reset(new smhip::data::InnerPointCloudData(pts));
-        frame->cloud->CalculateNormals();
-      }
-      Matrix4d from_last = Matrix4d::Identity();
-      if (k > 0) {
-        // SubmapPairMatch(source = submap k, target = submap k - 1), map_builder.cc:399-446, as --submap-edges does it
-        if (smhip_filter_output_to_source(h, 0) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as source: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-        const Pose guess = MulPose(AffineInverse(poses[(k - 1) * N]), poses[k * N]);
-        double result[16], score = 0.0;
-        smhip_icp_stats stats;
-        st = smhip_icp_align(h, guess.data(), result, &score, &stats);
-        if (st != SMHIP_OK) score = 0.0;
-        Matrix4d T;
-        std::memcpy(T.data(), result, sizeof(result));
-        be::NormalizeRotation(T);
-        if (st == SMHIP_OK && score >= a.submap_min_score) from_last = T;
-        else std::memcpy(from_last.data(), guess.data(), sizeof(double) * 16);
-        frame->global_pose = be::Multiply(frames.back()->global_pose, from_last);
-      } else {
-        frame->global_pose = maps[0]->GlobalPose();
-      }
-      if (k + 1 < S && smhip_filter_output_to_target(h, 0, &m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h)); rc = 3; break; }
-      if (io.use_gps) {   // the fix of the submap's first frame, the frame whose pose is its global pose
-        const std::array<double, 3>& e = a.enu[static_cast<size_t>(k) * N];
-        if (std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2])) {
-          maps.back()->SetRelatedGpsInENU(e[0], e[1], e[2]);
-          frame->has_enu = true;
-          for (int c = 0; c < 3; ++c) frame->enu[c] = maps.back()->GetRelatedGpsInENU()[c];
-        }
-      }
-      frames.push_back(frame);
-      if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
-    }
-    if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
-    if (rc == 0) {
-      res->loop_edges = optimizer.LoopEdgeCount(); res->solves = optimizer.SolveCount();
-      res->stop_reason = optimizer.LastStats().stop_reason; res->final_cost = optimizer.LastStats().final_cost;
-      // MapBuilder::CalculateCoordTransformToGps (map_builder.cc:748-762): with --gps-output-enu every submap pose is premultiplied
-      // by the map origin's pose in the GPS frame before UpdateInnerFramePose, and the file is in the ENU frame
-      const Matrix4d to_enu = optimizer.GetGpsCoordTransform();
-      res->gps_factors = optimizer.GpsFactorCount();
-      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) res->gps_coord[4 * r + c] = to_enu(r, c);
-      for (int k = 0; k < S; ++k) {
-        maps[k]->SetGlobalPose(frames[k]->global_pose);
-        maps[k]->UpdateInnerFramePose();                                   // map_builder.cc:598-601
-        for (int f = 0; f < N; ++f) {
-          const Matrix4d& G = maps[k]->FrameGlobalPose(f);
-          const Pose& was = poses[k * N + f];
-          res->moved_m = std::max(res->moved_m, std::sqrt((G(0, 3) - was[12]) * (G(0, 3) - was[12]) + (G(1, 3) - was[13]) * (G(1, 3) - was[13]) +
-                                                          (G(2, 3) - was[14]) * (G(2, 3) - was[14])));
-          if (!a.gps_output_enu) write_pose(G.data());
-        }
-        if (a.gps_output_enu) {
-          maps[k]->SetGlobalPose(be::Multiply(to_enu, frames[k]->global_pose));
-          maps[k]->UpdateInnerFramePose();
-          for (int f = 0; f < N; ++f) write_pose(maps[k]->FrameGlobalPose(f).data());
-        }
-      }
-      Pose last;
-      std::memcpy(last.data(), (a.gps_output_enu ? be::Multiply(to_enu, frames.back()->global_pose) : frames.back()->global_pose).data(), sizeof(double) * 16);
-      const Pose carry = MulPose(last, AffineInverse(poses[(S - 1) * N]));
-      for (int f = S * N; f < n_frames; ++f) write_pose(MulPose(carry, poses[f]).data());
-    }
-  }
-  out.close();
-  smhip_destroy(h);
-  if (rc != 0) std::remove(a.close_loops.c_str());
-  res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
 // --map-poses FILE: the map alone, one process, no alignment and no RCCL.  The pose file is checked before any GPU work: it needs
 // a pose for every frame the map inserts.
 int RunMapOnly(const Args& a) {
@@ -850,17 +226,7 @@ int RunMapOnly(const Args& a) {
   if (!a.map_package.empty() && static_cast<int>(poses.size()) < package_frames)
     Die(a.map_poses + " holds " + std::to_string(poses.size()) + " poses; the map package needs one for each of the first " + std::to_string(package_frames) + " frames");
   std::string fields;
-  int rc = 0;
-  if (!a.map_path.empty()) {
-    MapResult m;
-    rc = BuildMap(a, files, frames, poses, 0, &m);
-    if (rc == 0) fields += MapJsonFields(a, m);
-  }
-  if (rc == 0 && !a.map_package.empty()) {
-    PackageResult m;
-    rc = BuildMapPackage(a, files, n_frames, poses, 0, &m);
-    if (rc == 0) fields += PackageJsonFields(a, m);
-  }
+  const int rc = RunPasses(a, files, n_frames, poses, 0, &fields);     // (Parse left --map and --map-package only)
   if (rc == 0 && !a.quiet)
     std::printf("%s}\n", (Fmt("{\"driver\": \"smhip_shard (map only)\", \"poses_file\": \"%s\", \"poses_in_file\": %d", a.map_poses.c_str(),
                               static_cast<int>(poses.size())) + fields).c_str());
@@ -899,7 +265,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
   // batch holds as its source already.
   size_t max_bytes = 16;
   for (const auto& f : files) { struct stat sb; if (stat(f.c_str(), &sb) == 0) max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
-  const size_t slot_floats = std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4);
+  const size_t slot_floats = SlotFloats(max_bytes);
   const int cap = static_cast<int>(slot_floats / 4);
   for (int k = 0; k < NH; ++k) {
     const smhip_status s = smhip_create(device, streams[k], 2 * B, cap, cap, &hs[k]);
@@ -1014,7 +380,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
   };
   double upload_s = 0.0, wait_s = 0.0, set_s = 0.0, prep_s = 0.0;   // rank 0's host-side split: blocked on the readers / uploads / target preparation
   auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  int done = 0, my_pairs = 0;
+  int my_pairs = 0;
   // the batch period once the pipeline is full: from the first batch's alignments being enqueued to the last batch's, over the pairs of
   // the batches after the first (a run of four batches spends a quarter of its time filling and draining)
   double first_enq_s = 0.0, last_enq_s = 0.0;
@@ -1072,10 +438,8 @@ int RunRank(const Args& a, int rank, int world, int device) {
     mark("alignments enqueued", base);
     if (turn == 0) { first_enq_s = since(t0); first_enq_pairs = nb; }
     last_enq_s = since(t0); enq_pairs += nb;
-    done = base + nb;
     my_pairs += nb;
   }
-  (void)done;
   for (int k = 1; k < NH; ++k) HIPOK(hipStreamSynchronize(streams[k]));     // (the gather goes to the first matcher's stream)
   // the ONE collective of the path: every rank's padded block of poses, device to device over xGMI
   NCCLOK(ncclAllGather(local_dev, all_dev, static_cast<size_t>(kPoseDoubles) * per, ncclDouble, comm, stream));
@@ -1091,20 +455,17 @@ int RunRank(const Args& a, int rank, int world, int device) {
     std::ofstream out(a.out_path);
     if (!out) Die("cannot write " + a.out_path);
     out.precision(8);
-    double pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    auto write_pose = [&]() {
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out << pose[4 * r + c] << ((r == 2 && c == 3) ? "\n" : " ");
-    };
-    write_pose();
+    Pose pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    WritePoseLine(out, pose.data());
     double score_sum = 0.0, iter_sum = 0.0;
     int bad = 0;
     for (int pair = 0; pair < n_pairs; ++pair) {
       const double* row = &all[static_cast<size_t>(kPoseDoubles) * (static_cast<size_t>(pair % world) * per + pair / world)];
-      double T[16];
-      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = row[4 * c + r];   // column-major -> row-major
+      Pose T;
+      std::copy(row, row + 16, T.begin());
       if (!(row[17] >= 1.0)) ++bad;                                      // a pair that never ran left zeros; one that failed exports 0 iterations (smhip.h)
-      Mul4(pose, T, pose);
-      write_pose();
+      pose = MulPose(pose, T);
+      WritePoseLine(out, pose.data());
       score_sum += row[16]; iter_sum += row[17];
     }
     out.close();
@@ -1115,7 +476,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
                   "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
-      if (a.map_path.empty() && a.submap_edges.empty() && a.close_loops.empty() && a.map_package.empty()) { std::printf("%s}\n", line.c_str()); line.clear(); }
+      if (!AnyPass(a)) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;
   }
@@ -1124,32 +485,12 @@ int RunRank(const Args& a, int rank, int world, int device) {
   if (pinned) for (float* b : ring_buffers) (void)hipHostFree(b);
   NCCLOK(ncclCommDestroy(comm));
   for (int k = 0; k < NH; ++k) (void)hipStreamDestroy(streams[k]);
-  if (rank == 0 && (!a.map_path.empty() || !a.submap_edges.empty() || !a.close_loops.empty() || !a.map_package.empty())) {
-    // the static map and the submap edges from the poses as written: the pose file read back (--map-poses on that file builds
-    // the same map)
+  if (rank == 0 && AnyPass(a)) {
+    // from the poses as written: the pose file read back (--map-poses on that file builds the same map)
     std::string fields;
     std::vector<Pose> poses;
     if (rc == 0 && (!ReadPoses(a.out_path, &poses) || static_cast<int>(poses.size()) != n_pairs + 1)) Die("cannot read back " + a.out_path);
-    if (rc == 0 && !a.map_path.empty()) {
-      MapResult m;
-      rc = BuildMap(a, files, MapFrames(a, n_pairs + 1), poses, device, &m);
-      if (rc == 0) fields += MapJsonFields(a, m);
-    }
-    if (rc == 0 && !a.submap_edges.empty()) {
-      SubmapResult m;
-      rc = BuildSubmapEdges(a, files, n_pairs + 1, poses, device, &m);
-      if (rc == 0) fields += SubmapJsonFields(a, m);
-    }
-    if (rc == 0 && !a.close_loops.empty()) {
-      LoopResult m;
-      rc = CloseLoops(a, files, n_pairs + 1, poses, device, &m);
-      if (rc == 0) fields += LoopJsonFields(a, m);
-    }
-    if (rc == 0 && !a.map_package.empty()) {
-      PackageResult m;
-      rc = BuildMapPackage(a, files, n_pairs + 1, poses, device, &m);
-      if (rc == 0) fields += PackageJsonFields(a, m);
-    }
+    if (rc == 0) rc = RunPasses(a, files, n_pairs + 1, poses, device, &fields);
     if (!line.empty()) std::printf("%s%s}\n", line.c_str(), rc == 0 ? fields.c_str() : "");
   }
   return rc;

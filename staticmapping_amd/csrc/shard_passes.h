@@ -1,0 +1,534 @@
+// shard_passes.h -- what rank 0 of smhip_shard does once the pose file is written: --map, --submap-edges, --close-loops and
+// --map-package, each from the poses AS WRITTEN, run by RunPasses in that order.
+// The three passes over submaps are loops over one SubmapFeed: the submaps of the sequence, one after the other, resident on the device.
+#pragma once
+
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/smhip.h"
+#include "../../include/smhip/kitti_scans.h"
+#include "../../include/smhip/pcd.h"
+#include "../../include/smhip/back_end.h"
+#include "../../include/smhip/pose_graph.h"
+#include "../../include/smhip/map_package.h"
+#include "shard_poses.h"
+
+namespace shard {
+
+using smhip::kitti::kMaxFloatsPerFile;
+using smhip::kitti::ScanPrefetcher;
+
+struct Args {
+  std::string scans_dir, out_path = "kitti_pose.txt", id_file;
+  unsigned long long nonce = 0;             // identifies this run's id file (launcher: pid and start time; else MASTER_PORT)
+  int gpus = 1, rank = -1, world = -1, local_rank = -1;
+  int batch = 256, iterations = 20, early_exit = 0, max_pairs = -1, readers = 8, matchers = 1, warmup = 1, parts = 0;
+  double guess_tx = 0.0;
+  bool quiet = false;
+  // the static map (--map); the MRVM settings are MrvmSettings' (multi_resolution_voxel_map.h:54-65), whose defaults these are
+  std::string map_path, map_poses;
+  int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
+  float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
+  bool map_average = false, map_rgb = false;
+  // the map package (--map-package); defaults: MapPackageOptions, builder/map_package.h:36-41
+  std::string map_package;
+  smhip::MapPackageOptions package;
+  // consecutive submaps (--submap-edges); defaults: builder/submap_options.h:30-38 and accepted_min_score of the configs
+  std::string submap_edges;
+  int submap_frames = 5;
+  float submap_voxel = 0.1f, submap_min_score = 0.7f;
+  // --close-loops: the pose graph over those submaps; the detector's settings (back_end/loop_detector_options.h:29-40), with the
+  // descriptor gate on as in the shipped KITTI config
+  std::string close_loops;
+  smhip::back_end::LoopDetectorSettings loop = [] { smhip::back_end::LoopDetectorSettings s; s.use_descriptor = true; return s; }();
+  // --gps-enu FILE: one line per scan in file order, three numbers already in ENU metres, nan = no fix (the geodetic conversion is
+  // not restated); the factors' settings (isam_optimizer.h:61-66) and the antenna in the tracking frame
+  std::string gps_enu;
+  std::vector<std::array<double, 3>> enu;
+  double gps_lever[3] = {0.0, 0.0, 0.0};
+  int gps_init_num = 25, gps_sample_step = 1;
+  double gps_init_angle = 1.6;
+  bool gps_output_enu = false;
+};
+
+[[noreturn]] inline void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
+
+inline std::string Fmt(const char* fmt, ...) {
+  va_list ap, aq;
+  va_start(ap, fmt);
+  va_copy(aq, ap);
+  const int n = std::vsnprintf(nullptr, 0, fmt, ap);
+  va_end(ap);
+  std::string out(static_cast<size_t>(std::max(n, 0)) + 1, '\0');
+  std::vsnprintf(&out[0], out.size(), fmt, aq);
+  va_end(aq);
+  out.resize(static_cast<size_t>(std::max(n, 0)));
+  return out;
+}
+
+inline double Since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
+
+// room per read buffer for files of at most max_bytes: a row is 16 bytes, the reader stops at kMaxFloatsPerFile
+inline size_t SlotFloats(size_t max_bytes) { return std::min(kMaxFloatsPerFile, (max_bytes / 16 + 1) * 4); }
+
+// the frames --map inserts: 0, K, 2K, ... below n_frames (--map-every K stands in for the reference's key-frame selection)
+inline std::vector<int> MapFrames(const Args& a, int n_frames) {
+  std::vector<int> v;
+  for (int k = 0; k < n_frames; k += a.map_every) v.push_back(k);
+  return v;
+}
+
+// --map PATH: the static map of MapBuilder::SaveMaps (builder/map_builder.cc:825-910).  Once kitti_pose.txt is written and the matchers
+// are gone, rank 0 reads the scans of `frames` again in order and inserts frame k's raw rows (intensity x 255, kitti_reader.cc:113)
+// under poses[k] into one device MultiResolutionVoxelMap (ApplyTransformToOutput on the device, origin = the pose's translation).
+// The poses are the ones AS WRITTEN to the pose file (8 significant digits, parsed back), so the map is a function of that file:
+// --map-poses FILE builds the same map, byte for byte, with no alignment, no RCCL and one process -- also from poses that came from
+// elsewhere.  --map-part-every N writes <stem>_part_<i>.pcd after every N inserted frames and starts a fresh map (separate_output /
+// separate_step, :860-890, counted in frames rather than submaps); otherwise the whole map goes to PATH.  Every file is a PCD file
+// with its rows in voxel-key order (SMHIP_MRVM_SORTED).  Returns 0, or 3 when the map refused a frame: the files of this run are then
+// removed.  map_voxels / map_points are summed over the parts.  Like every pass, it appends its fields of the summary line when it returns 0.
+inline int BuildMap(const Args& a, const std::vector<std::string>& files, const std::vector<int>& frames, const std::vector<Pose>& poses, int device,
+                    std::string* fields) {
+  const auto t0 = std::chrono::steady_clock::now();
+  struct { int frames = 0, parts = 0; long long voxels = 0, points = 0; } res;
+  size_t max_bytes = 16;
+  for (int k : frames) { struct stat sb; if (stat(files[k].c_str(), &sb) == 0) max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+  const size_t slot_floats = SlotFloats(max_bytes);
+  smhip_mrvm_settings set;
+  smhip_mrvm_default_settings(&set);
+  set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution; set.hit_prob = a.map_hit; set.miss_prob = a.map_miss;
+  set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
+  const int flags = SMHIP_MRVM_SORTED | (a.map_average ? SMHIP_MRVM_AVERAGE : 0) | (a.map_rgb ? SMHIP_MRVM_RGB : 0);
+  std::string stem = a.map_path;
+  if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".pcd") == 0) stem.resize(stem.size() - 4);
+  std::vector<std::string> written;
+  smhip_mrvm_handle h = nullptr;
+  auto fresh_map = [&]() {
+    if (h) smhip_mrvm_destroy(h);
+    h = nullptr;
+    const smhip_status st = smhip_mrvm_create(device, std::min(22, a.map_max_table_log2), static_cast<int>(slot_floats / 4), &set, &h);
+    if (st != SMHIP_OK) Die(std::string("smhip_mrvm_create: ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
+    if (smhip_mrvm_set_max_table_log2(h, a.map_max_table_log2) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+  };
+  auto write_map = [&](const std::string& path) {     // OutputToPointCloud(threshold, filename), multi_resolution_voxel_map.cc:217-242
+    int v = 0, n = 0, m = 0;
+    if (smhip_mrvm_voxel_count(h, &v) != SMHIP_OK || smhip_mrvm_output_ex(h, a.map_threshold, flags, nullptr, 0, &n) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+    std::vector<float> rows(4 * static_cast<size_t>(n));
+    if (n > 0 && smhip_mrvm_output_ex(h, a.map_threshold, flags, rows.data(), n, &m) != SMHIP_OK) Die(smhip_mrvm_last_error(h));
+    if (m != n) Die("map: output changed size between two calls");
+    res.voxels += v;
+    if (smhip::pcd::SaveBinary(path, n > 0 ? rows.data() : nullptr, static_cast<size_t>(n), a.map_rgb)) {
+      written.push_back(path);
+      res.points += n;
+      ++res.parts;
+    }
+  };
+  fresh_map();
+  ScanPrefetcher scans(files, frames, a.readers, 2 * std::max(1, a.readers) + 2, /*hold_until_release=*/false, slot_floats);
+  int in_part = 0, part = 0, rc = 0;
+  for (size_t i = 0; i < frames.size(); ++i) {
+    int n = 0, fi = -1;
+    const float* rows = scans.Next(&n, &fi);
+    if (!rows || fi != frames[i]) Die("map: prefetcher out of step");
+    if (n < 0) Die("cannot read " + files[fi]);
+    if (n == 0) {
+      std::fprintf(stderr, "smhip_shard: map: %s is empty, skipped\n", files[fi].c_str());     // InsertPointCloud: "cloud is empty.", :61-64
+    } else {
+      const smhip_status st = smhip_mrvm_insert_transformed_f32(h, rows, 4, n, poses[fi].data(), 255.f);
+      if (st != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: map: frame %d refused: %s\n", fi, smhip_mrvm_last_error(h));
+        rc = 3;
+        break;
+      }
+      if (smhip_mrvm_last_error(h)[0]) std::fprintf(stderr, "smhip_shard: map: frame %d: %s\n", fi, smhip_mrvm_last_error(h));
+    }
+    ++res.frames;
+    if (a.map_part_every > 0 && ++in_part == a.map_part_every) {
+      write_map(stem + "_part_" + std::to_string(part++) + ".pcd");
+      fresh_map();
+      in_part = 0;
+    }
+  }
+  if (rc == 0) {
+    if (a.map_part_every == 0) write_map(a.map_path);
+    else if (in_part > 0) write_map(stem + "_part_" + std::to_string(part) + ".pcd");
+  } else {
+    for (const auto& f : written) std::remove(f.c_str());
+  }
+  smhip_mrvm_destroy(h);
+  const double seconds = Since(t0);
+  if (rc == 0)
+    *fields += Fmt(", \"map_file\": \"%s\", \"map_frames\": %d, \"map_voxels\": %lld, \"map_points\": %lld, \"map_parts\": %d, \"map_seconds\": %.4f, "
+                   "\"map_ms_per_frame\": %.3f", a.map_path.c_str(), res.frames, res.voxels, res.points, res.parts, seconds,
+                   res.frames > 0 ? 1e3 * seconds / res.frames : 0.0);
+  return rc;
+}
+
+// ---- the submaps of the sequence, one after the other, resident on the device ------------------------------------------------
+struct PairMatch { smhip_status status = SMHIP_OK; double score = 0.0; bool accepted = false; Pose transform_to_next{}; };
+
+// Frames [kN, (k + 1)N) form submap k < S (--submap-frames N; Submap::InsertFrame, builder/submap.cc:76-163); a trailing group that is
+// not full has no cloud (submap.cc:98) and is dropped.  Build(k, local) reads the N scans and builds the submap's cloud on the device
+// from the raw rows under N local poses (smhip_submap_build_f32: VoxelGrid of --submap-voxel, 0 = none).  The cloud never leaves the
+// device: it is the filter output of `h`, becomes the source against the previous submap's CalculateNormals target (MatchToPrevious),
+// then the target of the next (KeepAsTarget).  The local poses are the caller's: the passes do not all invert the first pose the
+// same way.  `label` names the pass in messages.
+struct SubmapFeed {
+  const Args& a;
+  const std::vector<std::string>& files;
+  const int N;
+  const std::string label;
+  float voxel = 0.f;
+  smhip_handle h = nullptr;
+  std::unique_ptr<ScanPrefetcher> scans;
+
+  SubmapFeed(const Args& a, const std::vector<std::string>& files, int S, int N, int device, const char* label) : a(a), files(files), N(N), label(label) {
+    // capacity: the largest submap's rows together (every scan of a group is read whole)
+    long long cap = 16;
+    size_t max_bytes = 16;
+    for (int k = 0; k < S; ++k) {
+      long long rows = 0;
+      for (int f = k * N; f < (k + 1) * N; ++f) {
+        struct stat sb;
+        if (stat(files[f].c_str(), &sb) == 0) { rows += std::min<long long>(sb.st_size / 16, kMaxFloatsPerFile / 4); max_bytes = std::max(max_bytes, static_cast<size_t>(sb.st_size)); }
+      }
+      cap = std::max(cap, rows);
+    }
+    if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304 (lower --submap-frames)");
+    const smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
+    if (st != SMHIP_OK) Die("smhip_create (" + this->label + "): " + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
+    // the six-decimal trip of the voxel size through the filter's text (submap.cc:148-154)
+    if (a.submap_voxel > 0.f) voxel = static_cast<float>(std::atof(std::to_string(a.submap_voxel).c_str()));
+    std::vector<int> order(static_cast<size_t>(S) * N);
+    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
+    scans.reset(new ScanPrefetcher(files, order, a.readers, N + std::max(1, a.readers) + 2, /*hold_until_release=*/true, SlotFloats(max_bytes)));
+  }
+  ~SubmapFeed() { scans.reset(); smhip_destroy(h); }
+
+  void SetIcpOptions() {                                                  // IcpFast under --iterations and --early-exit, for the passes that match
+    smhip_icp_options o;
+    smhip_icp_default_options(&o);
+    o.max_iteration = a.iterations;
+    o.early_exit = a.early_exit;
+    if (smhip_icp_set_options(h, &o) != SMHIP_OK) Die(smhip_last_error(h));
+  }
+
+  // Submap k under local[16 * f] (column-major).  Returns its point count, or -1 when the device refused it (said on stderr).
+  int Build(int k, const double* local) {
+    std::vector<const float*> rows(N);
+    std::vector<int> n(N);
+    for (int f = 0; f < N; ++f) {
+      int fi = -1;
+      rows[f] = scans->Next(&n[f], &fi);
+      if (!rows[f] || fi != k * N + f) Die(label + ": prefetcher out of step");
+      if (n[f] < 0) Die("cannot read " + files[fi]);
+    }
+    int m = 0;
+    const smhip_status st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local, voxel, &m);
+    scans->ReleaseHeld();                                                 // the call returned: the rows have left the host buffers
+    if (st == SMHIP_OK) return m;
+    std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h));
+    return -1;
+  }
+
+  // SubmapPairMatch(source = the resident submap k, target = submap k - 1), map_builder.cc:399-446: the guess from the two first
+  // frames' poses (:426-428), NormalizeRotation of the result (:434), transform_to_next = the match when its score reaches
+  // --submap-min-score, else the guess (:436-444).  An align that fails (no correspondence) is an edge that keeps the guess, score 0.
+  // false: the device refused the cloud as source (said on stderr).
+  bool MatchToPrevious(int k, const std::vector<Pose>& poses, PairMatch* pm) {
+    if (smhip_filter_output_to_source(h, 0) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: submap %d as source: %s\n", k, smhip_last_error(h)); return false; }
+    const Pose guess = MulPose(AffineInverse(poses[(k - 1) * N]), poses[k * N]);
+    smhip::registrator::Matrix4d T;
+    smhip_icp_stats stats;
+    pm->status = smhip_icp_align(h, guess.data(), T.data(), &pm->score, &stats);
+    if (pm->status != SMHIP_OK) {
+      std::fprintf(stderr, "smhip_shard: submaps %d -> %d: %s (%s)\n", k - 1, k, smhip_status_string(pm->status), smhip_last_error(h));
+      pm->score = 0.0;
+    }
+    pm->accepted = pm->status == SMHIP_OK && pm->score >= a.submap_min_score;
+    pm->transform_to_next = guess;
+    if (pm->accepted) {
+      smhip::back_end::NormalizeRotation(T);
+      std::copy(T.data(), T.data() + 16, pm->transform_to_next.begin());
+    }
+    return true;
+  }
+
+  // the resident cloud becomes the target of the next pair (Submap::Cloud() carries normals, submap.cc:160-161)
+  bool KeepAsTarget(int k) {
+    int m = 0;
+    if (smhip_filter_output_to_target(h, 0, &m) == SMHIP_OK) return true;
+    std::fprintf(stderr, "smhip_shard: submap %d as target: %s\n", k, smhip_last_error(h));
+    return false;
+  }
+};
+
+// the local poses of submap k as --submap-edges and --map-package take them: first^-1 * frame, the first frame's the identity itself
+// (submap.cc:83-87)
+inline std::vector<double> LocalPosesAsWritten(const std::vector<Pose>& poses, int k, int N) {
+  std::vector<double> local(16 * static_cast<size_t>(N));
+  const Pose first_inv = AffineInverse(poses[k * N]);
+  for (int f = 0; f < N; ++f) {
+    const Pose lp = f == 0 ? Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} : MulPose(first_inv, poses[k * N + f]);
+    std::memcpy(&local[16 * static_cast<size_t>(f)], lp.data(), sizeof(double) * 16);
+  }
+  return local;
+}
+
+// ---- --submap-edges -------------------------------------------------------------------------------------------------------
+// --submap-edges PATH: the submaps of frames [0, n_frames) under the poses as written and the match of every pair of consecutive ones
+// (MapBuilder::SubmapPairMatch), IcpFast under --iterations and --early-exit.  PATH holds one line per edge: `k k+1 accepted score`
+// and the twelve numbers of transform_to_next in the pose writer's format.  Returns 0, or 3 when the device refused a submap (the
+// file is then removed).
+inline int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
+  std::ofstream out(a.submap_edges);
+  if (!out) Die("cannot write " + a.submap_edges);
+  out.precision(8);
+  int rc = 0, edges = 0, accepted = 0;
+  double score_sum = 0.0;
+  if (S >= 2) {
+    SubmapFeed feed(a, files, S, N, device, "submaps");
+    feed.SetIcpOptions();
+    for (int k = 0; k < S && rc == 0; ++k) {
+      PairMatch pm;
+      if (feed.Build(k, LocalPosesAsWritten(poses, k, N).data()) < 0 || (k > 0 && !feed.MatchToPrevious(k, poses, &pm))) { rc = 3; break; }
+      if (k > 0) {
+        out << (k - 1) << " " << k << " " << (pm.accepted ? 1 : 0) << " " << pm.score << " ";
+        WritePoseLine(out, pm.transform_to_next.data());
+        ++edges; accepted += pm.accepted ? 1 : 0; score_sum += pm.score;
+      }
+      if (k + 1 < S && !feed.KeepAsTarget(k)) rc = 3;
+    }
+  }
+  out.close();
+  if (rc != 0) std::remove(a.submap_edges.c_str());
+  else *fields += Fmt(", \"submap_edges_file\": \"%s\", \"submaps\": %d, \"submap_edges\": %d, \"submap_edges_accepted\": %d, \"submap_mean_score\": %.6f, "
+                      "\"submap_seconds\": %.4f", a.submap_edges.c_str(), S, edges, accepted, edges > 0 ? score_sum / edges : 0.0, Since(t0));
+  return rc;
+}
+
+// ---- --map-package ----------------------------------------------------------------------------------------------------------
+// --map-package DIR: the map package of MapBuilder::SaveMapPackage (builder/map_builder.cc:816-823, builder/map_package.cc): the
+// static map cut into overlapping square pieces, DIR/<prefix><x>_<y>.pcd centred on the piece and DIR/map_package.xml listing them
+// (smhip/map_package.h).  Like --map it is a function of the pose file as written, so --map-poses FILE builds it too -- also from the
+// file --close-loops wrote.  Every submap (local poses first^-1 * frame; its global pose is its first frame's) is built once on the
+// device and downloaded, then smhip::SaveTrajectoriesAsMapPackage over them; the pieces' voxel maps take the --map-* settings.  The
+// plan is made from the poses alone before any device work: a refused plan ends the run with 2, and so does a directory the
+// description cannot be written into.  Returns 0, or 3 when the device refused a submap or an insert or a piece could not be written
+// (this run's files are then removed).
+inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
+  if (S < 1) Die("--map-package: " + std::to_string(n_frames) + " frames hold no full submap of " + std::to_string(N));
+  {
+    std::vector<std::array<double, 3>> translations(static_cast<size_t>(S));
+    for (int k = 0; k < S; ++k) translations[k] = {poses[k * N][12], poses[k * N][13], poses[k * N][14]};
+    smhip::MapPackagePlan plan;
+    std::string why;
+    if (!smhip::PlanMapPackage(translations, a.package, &plan, &why)) Die("--map-package refused: " + why);
+  }
+  std::string dir = a.map_package;
+  if (dir.back() != '/') dir += '/';
+  // the description's place is taken before any device work: a directory that is missing or cannot be written ends the run here
+  if (!std::ofstream(dir + a.package.descript_filename)) Die("cannot write " + dir + a.package.descript_filename);
+  std::vector<smhip::MapPackageSubmap> submaps(static_cast<size_t>(S));
+  int rc = 0;
+  {
+    SubmapFeed feed(a, files, S, N, device, "map package");     // (gone, with its device memory, before the pieces' maps are made)
+    for (int k = 0; k < S; ++k) {
+      const int m = feed.Build(k, LocalPosesAsWritten(poses, k, N).data());
+      if (m < 0) { rc = 3; break; }
+      smhip::MapPackageSubmap& sub = submaps[static_cast<size_t>(k)];
+      std::memcpy(sub.global_pose.data(), poses[k * N].data(), sizeof(double) * 16);
+      sub.cloud.resize(static_cast<size_t>(m));
+      if (m > 0 && smhip_filter_get_output(feed.h, &sub.cloud[0].x, nullptr, m) != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(feed.h)); rc = 3; break;
+      }
+    }
+  }
+  smhip::MapPackageResult pr;
+  if (rc == 0) {
+    smhip::MrvmSettings set;
+    set.output_average = a.map_average; set.output_rgb = a.map_rgb; set.prob_threshold = a.map_threshold; set.high_resolution = a.map_resolution;
+    set.hit_prob = a.map_hit; set.miss_prob = a.map_miss; set.z_offset = a.map_z_offset; set.max_point_num_in_cell = a.map_points_per_cell;
+    // raw KITTI rows: intensity x 255 on the way into the map, as --map inserts them (kitti_reader.cc:113)
+    if (!smhip::SaveTrajectoriesAsMapPackage(submaps, a.package, set, dir, &pr, device, 255.f, a.map_max_table_log2)) rc = 3;
+  } else {
+    std::remove((dir + a.package.descript_filename).c_str());
+  }
+  if (rc == 0)
+    *fields += Fmt(", \"package_dir\": \"%s\", \"package_pieces\": %d, \"package_submaps\": %d, \"package_points\": %lld, \"package_seconds\": %.4f",
+                   a.map_package.c_str(), pr.pieces, pr.submaps, pr.points, Since(t0));
+  return rc;
+}
+
+// ---- --close-loops ------------------------------------------------------------------------------------------------------------
+// --close-loops PATH: the pose graph over those submaps, MapBuilder::ConnectAllSubmap (builder/map_builder.cc:448-613), from the poses
+// as written: every submap is built on the device, described where it lies (M2DP), matched against the previous one (the odometry
+// factor) and handed to back_end::IsamOptimizer (smhip/pose_graph.h) -- the loop detector with the --loop-* settings
+// (back_end/loop_detector_options.h:29-40), the factors, one device solve of the pose graph per update, every submap's pose written
+// back.  A submap enters at the previous submap's corrected pose times its odometry factor.  After RunFinalOptimazation the frames
+// get submap pose x local pose (Submap::UpdateInnerFramePose) and go to PATH in the pose writer's format, one line per frame of the
+// sequence (the frames of a trailing group that is not full ride on the last submap), so --map --map-poses PATH builds the corrected
+// map.  Without the flag nothing of this runs and every output is what it was.
+// With --gps-enu FILE (one line per scan in file order: east north up in metres, nan = no fix; the geodetic conversion is not
+// restated) a submap carries the fix of its first frame and IsamOptimizer adds the GPS / ENU factors of isam_optimizer.cc:238-349
+// (--gps-lever x,y,z: the antenna in the tracking frame; --gps-init-num, --gps-sample-step, --gps-init-angle: isam_optimizer.h:61-66);
+// --gps-output-enu premultiplies every submap pose by GetGpsCoordTransform() before UpdateInnerFramePose (map_builder.cc:748-762),
+// so PATH is in the ENU frame.  --gps-enu without --close-loops, or a FILE whose line count is not the scan count, ends the run
+// with exit 2 before any device work.  Returns 0, or 3 when the device refused something (the file is then removed).
+inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
+  namespace be = smhip::back_end;
+  namespace bld = smhip::builder;
+  using smhip::registrator::Matrix4d;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = a.submap_frames, S = n_frames / N;
+  struct {
+    int loop_edges = 0, solves = 0, stop_reason = 0; double final_cost = 0.0, moved_m = 0.0;
+    int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
+  } res;
+  std::ofstream out(a.close_loops);
+  if (!out) Die("cannot write " + a.close_loops);
+  out.precision(8);
+  int rc = 0;
+  if (S < 1) {
+    for (int f = 0; f < n_frames; ++f) WritePoseLine(out, poses[f].data());
+  } else {
+    SubmapFeed feed(a, files, S, N, device, "loop closing");
+    feed.SetIcpOptions();
+    const smhip_handle h = feed.h;
+    smhip_m2dp_options mo;
+    smhip_m2dp_default_options(&mo);
+    const int dlen = smhip_m2dp_length(&mo);
+    be::LoopDetectorSettings settings = a.loop;
+    settings.device = device;
+    be::IsamOptimizerOptions io;
+    io.use_gps = !a.gps_enu.empty();
+    io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
+    be::IsamOptimizer optimizer(io, settings, h);
+    {
+      Matrix4d tracking_to_gps = Matrix4d::Identity();
+      for (int c = 0; c < 3; ++c) tracking_to_gps(c, 3) = a.gps_lever[c];
+      optimizer.SetTransformTrackingToGps(tracking_to_gps);
+    }
+    std::vector<std::shared_ptr<bld::Submap>> maps;
+    std::vector<std::shared_ptr<be::LoopFrame>> frames;
+    bld::SubmapOptions so;
+    so.frame_count = N;
+    const smhip::data::InnerCloudType::Ptr no_points(new smhip::data::InnerCloudType);   // the Submap objects keep the poses' books only
+    for (int k = 0; k < S && rc == 0; ++k) {
+      std::vector<double> local(16 * static_cast<size_t>(N));
+      maps.emplace_back(new bld::Submap(so));
+      for (int f = 0; f < N; ++f) {
+        Matrix4d P;
+        std::memcpy(P.data(), poses[k * N + f].data(), sizeof(double) * 16);
+        maps.back()->InsertFrame(no_points, P);
+        std::memcpy(&local[16 * static_cast<size_t>(f)], maps.back()->LocalPose(f).data(), sizeof(double) * 16);   // submap.cc:83-87
+      }
+      const int m = feed.Build(k, local.data());
+      if (m < 0) { rc = 3; break; }
+      std::shared_ptr<be::LoopFrame> frame(new be::LoopFrame);
+      frame->descriptor.resize(static_cast<size_t>(dlen));
+      if (smhip_m2dp_from_filter_output(h, &mo, frame->descriptor.data(), dlen) != SMHIP_OK) {
+        std::fprintf(stderr, "smhip_shard: descriptor of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break;
+      }
+      {   // the cloud CloseLoop matches (Submap::Cloud(): normals calculated, submap.cc:160-161)
+        std::vector<smhip::data::InnerPointType> pts(static_cast<size_t>(m));
+        if (smhip_filter_get_output(h, &pts[0].x, nullptr, m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break; }
+        frame->cloud.reset(new smhip::data::InnerPointCloudData(pts));
+        frame->cloud->CalculateNormals();
+      }
+      Matrix4d from_last = Matrix4d::Identity();
+      if (k > 0) {
+        PairMatch pm;
+        if (!feed.MatchToPrevious(k, poses, &pm)) { rc = 3; break; }
+        std::memcpy(from_last.data(), pm.transform_to_next.data(), sizeof(double) * 16);
+        frame->global_pose = be::Multiply(frames.back()->global_pose, from_last);
+      } else {
+        frame->global_pose = maps[0]->GlobalPose();
+      }
+      if (k + 1 < S && !feed.KeepAsTarget(k)) { rc = 3; break; }
+      if (io.use_gps) {   // the fix of the submap's first frame, the frame whose pose is its global pose
+        const std::array<double, 3>& e = a.enu[static_cast<size_t>(k) * N];
+        if (std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2])) {
+          maps.back()->SetRelatedGpsInENU(e[0], e[1], e[2]);
+          frame->has_enu = true;
+          for (int c = 0; c < 3; ++c) frame->enu[c] = maps.back()->GetRelatedGpsInENU()[c];
+        }
+      }
+      frames.push_back(frame);
+      if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
+    }
+    if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
+    if (rc == 0) {
+      res.loop_edges = optimizer.LoopEdgeCount(); res.solves = optimizer.SolveCount();
+      res.stop_reason = optimizer.LastStats().stop_reason; res.final_cost = optimizer.LastStats().final_cost;
+      // MapBuilder::CalculateCoordTransformToGps (map_builder.cc:748-762): with --gps-output-enu every submap pose is premultiplied
+      // by the map origin's pose in the GPS frame before UpdateInnerFramePose, and the file is in the ENU frame
+      const Matrix4d to_enu = optimizer.GetGpsCoordTransform();
+      res.gps_factors = optimizer.GpsFactorCount();
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) res.gps_coord[4 * r + c] = to_enu(r, c);
+      for (int k = 0; k < S; ++k) {
+        maps[k]->SetGlobalPose(frames[k]->global_pose);
+        maps[k]->UpdateInnerFramePose();                                   // map_builder.cc:598-601
+        for (int f = 0; f < N; ++f) {
+          const Matrix4d& G = maps[k]->FrameGlobalPose(f);
+          const Pose& was = poses[k * N + f];
+          res.moved_m = std::max(res.moved_m, std::sqrt((G(0, 3) - was[12]) * (G(0, 3) - was[12]) + (G(1, 3) - was[13]) * (G(1, 3) - was[13]) +
+                                                          (G(2, 3) - was[14]) * (G(2, 3) - was[14])));
+          if (!a.gps_output_enu) WritePoseLine(out, G.data());
+        }
+        if (a.gps_output_enu) {
+          maps[k]->SetGlobalPose(be::Multiply(to_enu, frames[k]->global_pose));
+          maps[k]->UpdateInnerFramePose();
+          for (int f = 0; f < N; ++f) WritePoseLine(out, maps[k]->FrameGlobalPose(f).data());
+        }
+      }
+      Pose last;
+      std::memcpy(last.data(), (a.gps_output_enu ? be::Multiply(to_enu, frames.back()->global_pose) : frames.back()->global_pose).data(), sizeof(double) * 16);
+      const Pose carry = MulPose(last, AffineInverse(poses[(S - 1) * N]));
+      for (int f = S * N; f < n_frames; ++f) WritePoseLine(out, MulPose(carry, poses[f]).data());
+    }
+  }
+  out.close();
+  if (rc != 0) { std::remove(a.close_loops.c_str()); return rc; }
+  *fields += Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
+                 "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), S,
+                 res.loop_edges, res.solves, res.stop_reason, res.final_cost, res.moved_m, Since(t0));
+  if (!a.gps_enu.empty()) {
+    *fields += Fmt(", \"gps_factors\": %d, \"gps_coord\": [", res.gps_factors);
+    for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.gps_coord[q], q == 15 ? "]" : ", ");
+  }
+  return 0;
+}
+
+// ---- the passes, in their order ----------------------------------------------------------------------------------------------
+inline bool AnyPass(const Args& a) { return !a.map_path.empty() || !a.submap_edges.empty() || !a.close_loops.empty() || !a.map_package.empty(); }
+
+// map, submap edges, close loops, map package: each when its flag is set, from frames [0, n_frames) under `poses`; stops at the
+// first pass that fails and returns its status.  Every pass that returns 0 has appended its fields of the summary line.
+inline int RunPasses(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
+  int rc = 0;
+  if (rc == 0 && !a.map_path.empty()) rc = BuildMap(a, files, MapFrames(a, n_frames), poses, device, fields);
+  if (rc == 0 && !a.submap_edges.empty()) rc = BuildSubmapEdges(a, files, n_frames, poses, device, fields);
+  if (rc == 0 && !a.close_loops.empty()) rc = CloseLoops(a, files, n_frames, poses, device, fields);
+  if (rc == 0 && !a.map_package.empty()) rc = BuildMapPackage(a, files, n_frames, poses, device, fields);
+  return rc;
+}
+
+}  // namespace shard

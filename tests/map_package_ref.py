@@ -178,7 +178,7 @@ def package(submaps, make_map, border_offset=100.0, piece_width=500.0, prefix="p
 
 
 # ---- not the reference's: the double arithmetic smhip_shard makes a submap's local poses with, restated operation by operation so
-# that a test can build the very clouds the driver builds (csrc/shard_driver.cc AffineInverse, MulPose; 4x4 numpy arrays in and out)
+# that a test can build the very clouds the driver builds (csrc/shard_poses.h AffineInverse, MulPose; 4x4 numpy arrays in and out)
 def affine_inverse(P):
     m = [[float(P[r][c]) for c in range(4)] for r in range(4)]
     c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1]

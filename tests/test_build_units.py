@@ -1,8 +1,10 @@
-"""The per-unit build of libsmhip.so: every source file belongs to a unit, and an edit recompiles exactly the units whose
-compiler-written dependency files name the edited file (no GPU needed: hipcc cross-compiles for gfx950)."""
+"""The per-unit build of libsmhip.so and of the smhip_shard driver: every source file belongs to a unit or to the driver, and an edit
+recompiles exactly what the compiler-written dependency files say reads the edited file (no GPU needed: hipcc cross-compiles for gfx950)."""
 import os
 
 from staticmapping_amd import build
+
+DRIVER = "shard_driver.cc"
 
 
 def _compiled_at():
@@ -11,10 +13,11 @@ def _compiled_at():
 
 def test_no_orphan_sources():
     build.build()
-    named = {p for u in build.UNITS for p in build.unit_deps(u)}
+    named = {p for u in build.UNITS + [DRIVER] for p in build.unit_deps(u)}
     units = {os.path.join(build.CSRC, u) for u in build.UNITS}
     assert units <= named                                        # a unit's dependency file names the unit itself
-    orphans = [f for f in sorted(os.listdir(build.CSRC)) if f != "shard_driver.cc" and os.path.join(build.CSRC, f) not in named]
+    assert os.path.join(build.CSRC, DRIVER) in build.unit_deps(DRIVER)   # and so does the driver's
+    orphans = [f for f in sorted(os.listdir(build.CSRC)) if os.path.join(build.CSRC, f) not in named]
     assert orphans == []
 
 
@@ -43,3 +46,21 @@ def test_touched_header_recompiles_its_units_only():
     after = _compiled_at()
     assert {u for u in build.UNITS if after[u] > before[u]} == users
     assert os.path.getmtime(build.LIB_PATH) >= max(after.values())
+
+
+def test_touched_header_relinks_the_driver_and_no_library_unit():
+    build.build()
+    exe = build.build_shard_driver()
+    header = os.path.join(build.ROOT, "include", "smhip", "m2dp.h")     # the driver reads it through other headers only
+    assert header in build.unit_deps(DRIVER)
+    before, linked = _compiled_at(), os.stat(exe).st_mtime_ns
+    build.build_shard_driver()
+    assert os.stat(exe).st_mtime_ns == linked                    # nothing is newer than the program: no second link
+    st = os.stat(header)
+    try:
+        os.utime(header)                                         # now: later than the program
+        build.build_shard_driver()
+    finally:
+        os.utime(header, ns=(st.st_atime_ns, st.st_mtime_ns))
+    assert os.stat(exe).st_mtime_ns > linked
+    assert _compiled_at() == before and os.path.getmtime(build.LIB_PATH) <= os.path.getmtime(exe)
