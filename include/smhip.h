@@ -290,6 +290,21 @@ smhip_status smhip_icp_get_matches(smhip_handle h, int slot, int32_t* ids, float
  * the structure holds -- SMHIP_ERR_CAPACITY with the geometry already written; no grid in the slot -- SMHIP_ERR_NOT_READY. */
 smhip_status smhip_icp_debug_get_grid(smhip_handle h, int slot, double mu[3], float cell_origin[4], int32_t dims[7],
                                       uint32_t* words, int words_cap, uint32_t* cstart, int cstart_cap, float* tq, float* tn, int points_cap);
+/* Debugging / tests: the libnabo kd-tree resident in `slot` (nn_mode = SMHIP_NN_NABO: the structure the last Align or find_closests
+ * on it built or kept), copied to host buffers after a synchronisation.  mu[3]: the target mean; max_error2: (1 + nn_epsilon)^2, the
+ * float the search multiplies by; dims[4]: node count, nt (points), leaf blocks, ns (source points).  nodes: pairs of words -- inner
+ * node {cut value bits, (left child << 2) | cut dimension}, the right child behind the left one; leaf {first, (count << 2) | 3}.
+ * tq: nt rows of 4 floats, the centred point with the caller's index as the bits of w, in final bucket order.  leaf: blocks of 24
+ * floats x[8] y[8] z[8], the bucket that starts at tq position `first` in block first >> 2, unused entries +inf (blocks no bucket
+ * starts in are unspecified).  work / lb: per source point in the CALLER's order, the buckets its last walk scanned (saturating at
+ * 255) and the stored certificate word (the slack plus the pair's motion potential at the time of the walk).  work / lb are
+ * meaningful only for the source the slot's last find_closests / Align in this mode walked: after a new source was set, or before
+ * any such call, they are whatever the arrays hold, returned with SMHIP_OK -- the caller sees to the order.  Any pointer may be
+ * NULL; a capacity (in nodes, rows, blocks, queries) below what the structure holds -- SMHIP_ERR_CAPACITY with mu, max_error2 and
+ * dims already written; no kd-tree in the slot -- SMHIP_ERR_NOT_READY.  Changes no state. */
+smhip_status smhip_icp_debug_get_kd_tree(smhip_handle h, int slot, double mu[3], float* max_error2, int32_t dims[4],
+                                         uint32_t* nodes, int nodes_cap, float* tq, int points_cap, float* leaf, int leaf_cap,
+                                         uint8_t* work, float* lb, int queries_cap);
 /* One FindClosests pass only: transform the slot's source by T (column-major 4x4, applied AFTER
  * centring exactly as Align does) and return ids / d2 without running ICP. */
 smhip_status smhip_icp_find_closests(smhip_handle h, int slot, const double T[16], int32_t* ids, float* d2, int n);

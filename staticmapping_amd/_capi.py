@@ -152,6 +152,9 @@ SIGNATURES = {
     "smhip_icp_debug_get_grid": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_float_p, c_int32_p,
                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
                                                 c_float_p, c_float_p, ctypes.c_int]),
+    "smhip_icp_debug_get_kd_tree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_float_p, c_int32_p,
+                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_uint8), c_float_p, ctypes.c_int]),
     "smhip_icp_find_closests": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_int32_p, c_float_p,
                                                ctypes.c_int]),
     "smhip_ndt_default_options": (None, [ctypes.POINTER(NdtOptions)]),

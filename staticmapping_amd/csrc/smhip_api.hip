@@ -268,14 +268,19 @@ static plan::Inputs plan_inputs(const smhip_context* h) {
   return in;
 }
 
+// (1 + epsilon)^2 as the searches of nn_mode NABO multiply by it
+static float kd_max_error2(const smhip_context* h) {
+  const float e = h->opts.nn_epsilon >= 0.f ? h->opts.nn_epsilon : 3.16f;
+  return (1.0f + e) * (1.0f + e);
+}
+
 // launches what a plan names, in its order, on the part's stream
 static smhip_status enqueue_launches(smhip_context* h, const Half& f, const plan::Iteration& it) {
   using K = plan::Kernel;
   const IcpDev& d = f.d;
   hipStream_t st = f.stream;
   KdDev kd = h->kd;
-  const float e = h->opts.nn_epsilon >= 0.f ? h->opts.nn_epsilon : 3.16f;
-  kd.max_error2 = (1.0f + e) * (1.0f + e);
+  kd.max_error2 = kd_max_error2(h);
   constexpr int kShallow = plan::kNaboShallowLevels;
   const dim3 nn(kNnThreads), acc(kAccThreads), t256(256);
   std::optional<Bracket> br;
@@ -1401,6 +1406,56 @@ smhip_status smhip_icp_debug_get_grid(smhip_handle h, int slot, double mu[3], fl
     if (points_cap < st.nt) { h->err = "debug_get_grid: points_cap below nt"; return SMHIP_ERR_CAPACITY; }
     if (tq) HIPCHK(h, hipMemcpy(tq, h->dev.tq + (size_t)slot * nt_cap, sizeof(float4) * (size_t)st.nt, hipMemcpyDeviceToHost));
     if (tn) HIPCHK(h, hipMemcpy(tn, h->dev.tn + (size_t)slot * nt_cap, sizeof(float4) * (size_t)st.nt, hipMemcpyDeviceToHost));
+  }
+  return SMHIP_OK;
+}
+
+smhip_status smhip_icp_debug_get_kd_tree(smhip_handle h, int slot, double mu[3], float* max_error2, int32_t dims[4],
+                                         uint32_t* nodes, int nodes_cap, float* tq, int points_cap, float* leaf, int leaf_cap,
+                                         uint8_t* work, float* lb, int queries_cap) {
+  smhip_status s = check_slot(h, slot);
+  if (s) return s;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!h->kd_allocated || h->grid_mode[slot] != SMHIP_NN_NABO) { h->err = "debug_get_kd_tree: no kd-tree is resident in the slot"; return SMHIP_ERR_NOT_READY; }
+  PairState st;
+  HIPCHK(h, hipMemcpy(&st, h->dev.state + slot, sizeof(PairState), hipMemcpyDeviceToHost));
+  if (st.nt < 0 || st.nt > h->dev.nt_cap || st.nocc < 0 || st.nocc > h->kd.node_cap || st.ns < 0 || st.ns > h->dev.ns_cap) {
+    h->err = "debug_get_kd_tree: the slot's geometry is out of range"; return SMHIP_ERR_NOT_READY;
+  }
+  const int blocks = st.nocc > 0 ? (st.nt >> 2) + 1 : 0;        // block index = bucket start >> 2
+  if (mu) for (int d = 0; d < 3; ++d) mu[d] = st.mu[d];
+  if (max_error2) *max_error2 = kd_max_error2(h);
+  if (dims) { dims[0] = st.nocc; dims[1] = st.nt; dims[2] = blocks; dims[3] = st.ns; }
+  const size_t nt_cap = (size_t)h->dev.nt_cap, ns_cap = (size_t)h->dev.ns_cap;
+  if (nodes) {
+    if (nodes_cap < st.nocc) { h->err = "debug_get_kd_tree: nodes_cap below the node count"; return SMHIP_ERR_CAPACITY; }
+    HIPCHK(h, hipMemcpy(nodes, h->kd.nodes + (size_t)slot * h->kd.node_cap, sizeof(uint2) * (size_t)st.nocc, hipMemcpyDeviceToHost));
+  }
+  if (tq) {
+    if (points_cap < st.nt) { h->err = "debug_get_kd_tree: points_cap below nt"; return SMHIP_ERR_CAPACITY; }
+    HIPCHK(h, hipMemcpy(tq, h->dev.tq + (size_t)slot * nt_cap, sizeof(float4) * (size_t)st.nt, hipMemcpyDeviceToHost));
+  }
+  if (leaf) {
+    if (leaf_cap < blocks || blocks > h->kd.leaf_cap) { h->err = "debug_get_kd_tree: leaf_cap below the block count"; return SMHIP_ERR_CAPACITY; }
+    HIPCHK(h, hipMemcpy(leaf, h->kd.leaf + (size_t)slot * h->kd.leaf_cap * 24, sizeof(float) * 24 * (size_t)blocks, hipMemcpyDeviceToHost));
+  }
+  if (work || lb) {
+    if (queries_cap < st.ns) { h->err = "debug_get_kd_tree: queries_cap below ns"; return SMHIP_ERR_CAPACITY; }
+    // the device holds the source in its own order: row i came from caller index src.w
+    std::vector<float4> src((size_t)st.ns);
+    std::vector<uint8_t> w((size_t)st.ns);
+    std::vector<float> l((size_t)st.ns);
+    HIPCHK(h, hipMemcpy(src.data(), h->dev.src + (size_t)slot * ns_cap, sizeof(float4) * (size_t)st.ns, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(w.data(), h->dev.nabo_work + (size_t)slot * ns_cap, (size_t)st.ns, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(l.data(), h->dev.lb + (size_t)slot * ns_cap, sizeof(float) * (size_t)st.ns, hipMemcpyDeviceToHost));
+    for (int i = 0; i < st.ns; ++i) {
+      int32_t orig;
+      std::memcpy(&orig, &src[(size_t)i].w, sizeof(orig));
+      if (orig < 0 || orig >= st.ns) { h->err = "debug_get_kd_tree: a source row carries no caller index"; return SMHIP_ERR_NOT_READY; }
+      if (work) work[orig] = w[(size_t)i];
+      if (lb) lb[orig] = l[(size_t)i];
+    }
   }
   return SMHIP_OK;
 }

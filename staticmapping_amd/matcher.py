@@ -260,6 +260,22 @@ class IcpFastHip:
         return dict(mu=mu, h=ho[0], origin=ho[1:].copy(), nx=nx, ny=ny, nz=nz, wx=wx, nw=nw, nocc=nocc, nt=nt,
                     words=words, cstart=cstart, tq=tq, tn=tn)
 
+    def debug_get_kd_tree(self, slot: int = 0) -> dict:
+        """The libnabo kd-tree resident in `slot` (smhip_icp_debug_get_kd_tree, nn_mode NABO): mu, max_error2 and the arrays nodes
+        [n_nodes, 2] uint32, tq [nt, 4] float32 (tq[:, 3] holds the caller index as int32 bits), leaf [blocks, 3, 8] float32 (the
+        bucket starting at tq position f in block f >> 2), and per source point in the caller's order work [ns] uint8 and lb [ns]."""
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        mu = np.zeros(3); e2 = np.zeros(1, np.float32); dims = np.zeros(4, np.int32)
+        head = (mu.ctypes.data_as(_capi.c_double_p), e2.ctypes.data_as(_capi.c_float_p), dims.ctypes.data_as(_capi.c_int32_p))
+        self._check(self._lib.smhip_icp_debug_get_kd_tree(self._h, slot, *head, None, 0, None, 0, None, 0, None, None, 0))
+        nn, nt, nb, ns = (int(v) for v in dims)
+        nodes = np.zeros((nn, 2), np.uint32); tq = np.zeros((nt, 4), np.float32); leaf = np.zeros((nb, 3, 8), np.float32)
+        work = np.zeros(ns, np.uint8); lb = np.zeros(ns, np.float32)
+        self._check(self._lib.smhip_icp_debug_get_kd_tree(self._h, slot, *head, nodes.ctypes.data_as(u32p), nn, tq.ctypes.data_as(_capi.c_float_p), nt,
+                                                          leaf.ctypes.data_as(_capi.c_float_p), nb, work.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                          lb.ctypes.data_as(_capi.c_float_p), ns))
+        return dict(mu=mu, max_error2=e2[0], n_nodes=nn, nt=nt, ns=ns, nodes=nodes, tq=tq, leaf=leaf, work=work, lb=lb)
+
     def search_counts(self, slot: int = 0):
         """Queries that went through a search in iterations 0..11 of the slot's last Align."""
         c = (ctypes.c_uint32 * 12)()

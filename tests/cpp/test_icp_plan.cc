@@ -355,12 +355,60 @@ void pinned() {
   }
 }
 
+// The launch shapes tests/test_nabo_exact_gpu.py names, as the plan decides them (tests/nabo_cases.py holds the same sizes: 32 slots,
+// 7 700 queries, targets of 8 << 12 and 8 << 12 + 1 points): which nn_nabo instantiation walks and how the list walk is laid out.
+void nabo_exact_cases() {
+  constexpr int NS = 7700, SLOTS = 32;
+  for (int nt : {8 << 12, (8 << 12) + 1}) {
+    const bool shallow = nt <= 8 << 12;
+    Inputs in = inputs_for(NS);
+    in.nn_mode = SMHIP_NN_NABO;
+    {
+      g_case = "nabo exact: find_closests, a search outside an Align -- four rounds per workgroup whatever the size";
+      for (int ns : {1, 400, 1025, 4096, 20000}) {
+        const Iteration it = plan_search_only(in, whole_part(1, nt), ns);
+        expect(it, {{shallow ? Kernel::NaboFourShallow : Kernel::NaboFourDeep, ceil_div(ns, 1024) * 8, 1}});
+      }
+    }
+    {
+      g_case = "nabo exact: one pair's Align -- one round per workgroup, the list walk on as many workgroups";
+      const Batch b = plan_batch(in, 1, NS, nt);
+      CHECK(b.nparts == 1 && b.part[0].small && !b.one_launch);
+      const Iteration i0 = plan_iteration(in, b.part[0], NS, 0, -1), i1 = plan_iteration(in, b.part[0], NS, 1, -1);
+      CHECK(i0.n == 3 && i0.launch[0].kernel == (shallow ? Kernel::NaboOneShallow : Kernel::NaboOneDeep) && i0.launch[0].nb == 31);
+      CHECK(i1.n == 4 && i1.launch[0].kernel == Kernel::NaboCertifyOne && i1.launch[0].nb == 31);
+      CHECK(i1.launch[1].kernel == (shallow ? Kernel::NaboListedShallow : Kernel::NaboListedDeep) && i1.launch[1].nb == 31 && !i1.fused);
+    }
+    {
+      g_case = "nabo exact: 32 pairs with the default overlap -- two parts of 16 pairs, 256 workgroups each: the small forms again";
+      const Batch b = plan_batch(in, SLOTS, NS, nt);
+      CHECK(b.nparts == 2 && b.part[0].np == 16 && b.part[1].np == 16 && b.part[0].small && b.part[1].small);
+      const Iteration i0 = plan_iteration(in, b.part[1], NS, 0, -1), i1 = plan_iteration(in, b.part[1], NS, 1, -1);
+      CHECK(i0.launch[0].kernel == (shallow ? Kernel::NaboOneShallow : Kernel::NaboOneDeep));
+      CHECK(i1.launch[0].kernel == Kernel::NaboCertifyOne && i1.launch[1].nb == 31);
+    }
+    for (int listed : {96, 8}) {
+      g_case = "nabo exact: 32 pairs as one part (no_overlap) -- 512 workgroups: four rounds, the batch certificate pass, the strided list walk";
+      in.no_overlap = 1;
+      in.nabo_listed_blocks = listed;              // 96: kNaboListedBlocks; 8: SMHIP_NABO_LISTED_BLOCKS=8, 2 048 queries a trip
+      const Batch b = plan_batch(in, SLOTS, NS, nt);
+      CHECK(b.nparts == 1 && b.part[0].np == SLOTS && !b.part[0].small && SLOTS * ceil_div(NS, 512) == 512);
+      const Iteration i0 = plan_iteration(in, b.part[0], NS, 0, -1), i1 = plan_iteration(in, b.part[0], NS, 1, -1);
+      CHECK(i0.n == 3 && i0.launch[0].kernel == (shallow ? Kernel::NaboFourShallow : Kernel::NaboFourDeep) && i0.launch[0].nb == 8);
+      CHECK(i1.n == 4 && i1.launch[0].kernel == Kernel::NaboCertify && i1.launch[0].nb == certify_blocks(NS) && !i1.fused);
+      CHECK(i1.launch[1].kernel == (shallow ? Kernel::NaboListedShallow : Kernel::NaboListedDeep) && i1.launch[1].nb == listed);
+      in.no_overlap = 0;
+    }
+  }
+}
+
 }  // namespace
 
 int main() {
   capacities();
   history();
   pinned();
+  nabo_exact_cases();
   parts_and_one_launch();
   sweep();
   std::printf("%ld checks, %ld failed\n", g_checks, g_failures);
