@@ -605,8 +605,10 @@ double smhip_m2dp_match(const float* P, const float* Q, int n);
  * launch per call: nothing is read back between iterations.  Two calls on the same input give the same bits.
  * Beside the between-factor, smhip_pose_graph_*_factors take two more kinds, which carry the reference's GPS / ENU factors
  * (isam_optimizer.cc:238-349): a PRIOR on one node, and a POINT between a frame node and an observed node.
- * Not restated: the odometry calibration factor, the Huber odometry model (isam_optimizer.cc:84-93), IMU, ViewGraph's picture
- * output, the multi-trajectory optimiser, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
+ * smhip_pose_graph_*_robust give any factor a Huber threshold ("Robust factors" below): the reference's Robust(Huber(1), ...) of
+ * isam_optimizer.cc:90-93 and of the multi-trajectory optimiser's between-factors (multi_trajectory_optimizer.cc:68-81).
+ * Not restated: the odometry calibration factor (and with it the place the reference's IsamOptimizer puts its Huber model, :84-93),
+ * IMU, ViewGraph's picture output, the multi-trajectory optimiser itself, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
  * conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300). */
 #define SMHIP_POSE_GRAPH_MAX_NODES 8192
 #define SMHIP_POSE_GRAPH_MAX_EDGES 32768
@@ -696,6 +698,28 @@ smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, con
 smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
                                                const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
                                                const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
+/* Robust factors ("Robust factors"; tests/pose_graph_robust_ref.py).  A factor f of any kind may have a Huber
+ * threshold k_f >= 0.  With s_f^2 = sum (e / sigma)^2 over its rows, its cost term is s_f^2 when k_f == 0 or s_f^2 <= k_f^2 and
+ * 2 k_f s_f - k_f^2 otherwise (twice the Huber loss), and its weight w_f is 1 or k_f / s_f.  Linearisation makes the whitened rows as
+ * without thresholds and multiplies them by sqrt(w_f) where w_f < 1 (GTSAM's Robust::WhitenSystem): J^T r is the exact gradient of
+ * half the cost, H = sum w J^T J.  Damping, acceptance, stop rules, preconditioner and limits are untouched.  huber: one threshold
+ * per factor, NULL = none; with NULL, zeros or thresholds never exceeded every output has the bits of the *_factors call.
+ * Refused beside the refusals of the *_factors forms, before anything is touched: a threshold that is negative or not finite,
+ * SMHIP_ERR_INVALID_ARGUMENT.
+ * Two limits of the method: thresholds on the chain edges make the loop converge slowly (k = 1 on every factor of a 64-node ring with
+ * one wrong loop edge: 50 steps without a stop), which is why smhip::back_end::IsamOptimizer offers them on loop edges only; and an
+ * edge that claims two places 80 m apart coincide folds the ring with or without them -- the detector's distance gate comes first. */
+smhip_status smhip_pose_graph_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds,
+                                          const int32_t* ij, const double* data, const double* sigmas, const double* huber,
+                                          int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len);
+smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
+                                              const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
+                                              const double* huber, const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
+/* The report of the last optimise call on the handle, whichever of the three it was, by one launch (one thread takes one factor):
+ * per factor s_f (norm), w_f (weight) and the cost term (cost) at the poses that call's loop ENDED at.  Any pointer may be NULL.
+ * After a call without thresholds every weight is 1.  SMHIP_ERR_INVALID_ARGUMENT when n_factors is not that call's count,
+ * SMHIP_ERR_NOT_READY when no call got as far as the launch. */
+smhip_status smhip_pose_graph_last_robust(smhip_handle h, int n_factors, double* norm, double* weight, double* cost);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

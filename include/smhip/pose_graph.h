@@ -32,8 +32,12 @@
 //     in the residual: the POINT factor of include/smhip.h.  AnalyseAllFramePoseForMaxRotation clamps the dot product to [-1, 1]
 //     before acos (the reference's can be NaN for two equal rotations, which compares as "not below the angle").  A
 //     SolveGpsCorrdAlone that fails leaves nothing behind: the next frame with a fix tries again.
-//   * Not restated, and without an option here: the odometry calibration factor (ODOM_CALIB_KEY), the Huber odometry model
-//     (:84-93), IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
+//   * The reference's IsamOptimizer puts its Robust(Huber(1), ...) on the odometry calibration factor alone (:84-93), which is not
+//     restated; its loop edges are plain.  The multi-trajectory optimiser puts Huber(1) on every between-factor, its
+//     loop_closure_model_ among them (multi_trajectory_optimizer.cc:68-81).  IsamOptimizerOptions::loop_closure_huber offers that
+//     model for the loop edges here: 0 (the default) is the reference's IsamOptimizer, 1.0 the multi-trajectory optimiser's loop
+//     model.  The chain edges have no option: thresholds there make the loop converge slowly (include/smhip.h, "Robust factors").
+//   * Not restated, and without an option here: the odometry calibration factor (ODOM_CALIB_KEY), IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
 //     geodetic conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300).  The tf_error
 //     calibration point (GPS_CALIB_KEY) is not created: enable_extrinsic_calib = true is refused.
 #ifndef SMHIP_POSE_GRAPH_H_
@@ -68,20 +72,21 @@ inline Sigmas AlonePosePriorSigmas() { return {1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2, 1
 // index-adjacent and the preconditioner keeps solving the chain exactly.
 class PoseGraph {
  public:
-  struct Edge { int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); };
+  struct Edge { int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };   // huber: the factor's Huber threshold, 0 = none
   // a PRIOR on vertex `index` around `pose`, or a POINT between the frame vertex and vertex `index`
-  struct Factor { int kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; int index = 0; Matrix4d pose = Matrix4d::Identity(); double lever[3] = {0, 0, 0}, point[3] = {0, 0, 0}; Sigmas sigmas = FrameMatchSigmas(); };
+  struct Factor { int kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; int index = 0; Matrix4d pose = Matrix4d::Identity(); double lever[3] = {0, 0, 0}, point[3] = {0, 0, 0}; Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };
 
   // :140-173.  Vertices come in index order; vertex 0 is constant.
   void AddVertex(int index, const Matrix4d& pose, const Matrix4d& transform_from_last_pose, const Sigmas& odom_noise = FrameMatchSigmas()) {
     SMHIP_CHECK(index == static_cast<int>(poses_.size()), "vertices are added in index order");
     poses_.push_back(pose);
     fixed_.push_back(index == 0 ? 1 : 0);
-    if (index > 0) AddEdge(index - 1, index, transform_from_last_pose, odom_noise);
+    if (index > 0) AddEdge(index - 1, index, transform_from_last_pose, odom_noise, 0.0);
   }
   // :127-138
-  void AddLoopCloseEdge(int target_index, int source_index, const Matrix4d& transform_tgt_to_src, const Sigmas& loop_close_noise = LoopClosureSigmas()) {
-    AddEdge(target_index, source_index, transform_tgt_to_src, loop_close_noise);
+  void AddLoopCloseEdge(int target_index, int source_index, const Matrix4d& transform_tgt_to_src, const Sigmas& loop_close_noise = LoopClosureSigmas(),
+                        double huber = 0.0) {
+    AddEdge(target_index, source_index, transform_tgt_to_src, loop_close_noise, huber);
   }
   // A vertex that is neither constant nor tied to the previous one: what SolveGpsCorrdAlone's own graph is made of (:314-320)
   int AddLooseVertex(const Matrix4d& pose) {
@@ -89,10 +94,11 @@ class PoseGraph {
     fixed_.push_back(0);
     return static_cast<int>(poses_.size()) - 1;
   }
-  void AddPriorFactor(int index, const Matrix4d& pose, const Sigmas& sigmas) {
+  void AddPriorFactor(int index, const Matrix4d& pose, const Sigmas& sigmas, double huber = 0.0) {
     SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a prior is on a vertex that exists");
+    SMHIP_CHECK(std::isfinite(huber) && huber >= 0.0, "a Huber threshold is finite and not negative");
     Factor f;
-    f.kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; f.index = index; f.pose = pose; f.sigmas = sigmas;
+    f.kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; f.index = index; f.pose = pose; f.sigmas = sigmas; f.huber = huber;
     factors_.push_back(f);
   }
   // The frame vertex at `pose` with a prior around it; set again, it moves and its prior with it.
@@ -102,11 +108,12 @@ class PoseGraph {
   bool HasFrameVertex() const { return has_frame_; }
   const Matrix4d& FrameVertexPose() const { return frame_pose_; }
   // :238-261: frame * pose_index * lever = point, sigmas for the three rows
-  void AddPointFactor(int index, const double lever[3], const double point[3], const std::array<double, 3>& sigmas3) {
+  void AddPointFactor(int index, const double lever[3], const double point[3], const std::array<double, 3>& sigmas3, double huber = 0.0) {
     SMHIP_CHECK(has_frame_, "a point factor needs the frame vertex");
     SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a point factor observes a vertex that exists");
+    SMHIP_CHECK(std::isfinite(huber) && huber >= 0.0, "a Huber threshold is finite and not negative");
     Factor f;
-    f.kind = SMHIP_POSE_GRAPH_FACTOR_POINT; f.index = index;
+    f.kind = SMHIP_POSE_GRAPH_FACTOR_POINT; f.index = index; f.huber = huber;
     for (int c = 0; c < 3; ++c) { f.lever[c] = lever[c]; f.point[c] = point[c]; }
     f.sigmas = {sigmas3[0], sigmas3[1], sigmas3[2], 1.0, 1.0, 1.0};            // (the last three are not read)
     factors_.push_back(f);
@@ -119,10 +126,41 @@ class PoseGraph {
     return n;
   }
   int NodeCount() const { return static_cast<int>(poses_.size()) + (has_frame_ ? 1 : 0); }
-  // One device solve from the current poses, which it replaces.  false (poses unchanged, the reason on stderr) when refused.
+  // the factors of one solve: the between-factors, the frame vertex's prior, Factors()
+  int FactorCount() const { return static_cast<int>(edges_.size() + factors_.size()) + (has_frame_ ? 1 : 0); }
+  // some factor has a Huber threshold
+  bool HasHuber() const {
+    for (const Edge& e : edges_) if (e.huber != 0.0) return true;
+    for (const Factor& f : factors_) if (f.huber != 0.0) return true;
+    return false;
+  }
+  // the thresholds in the order of FlattenFactors' factors (the frame vertex's prior has none)
+  void FlattenHuber(std::vector<double>* huber) const {
+    huber->clear();
+    for (const Edge& e : edges_) huber->push_back(e.huber);
+    if (has_frame_) huber->push_back(0.0);
+    for (const Factor& f : factors_) huber->push_back(f.huber);
+  }
+  // One device solve from the current poses, which it replaces.  false (poses unchanged, the reason on stderr) when refused.  The
+  // robust entry is called only when some threshold is not zero: without one the calls are those made before thresholds existed.
   bool Optimize(smhip_handle handle, smhip_pose_graph_stats* stats = nullptr, const smhip_pose_graph_options* options = nullptr) {
     SMHIP_CHECK(handle != nullptr, "PoseGraph::Optimize needs a device handle");
     if (poses_.empty()) return true;
+    if (HasHuber()) {
+      std::vector<double> poses, data, sigmas, huber;
+      std::vector<int32_t> ij;
+      std::vector<uint8_t> fixed, kinds;
+      FlattenFactors(&poses, &fixed, &kinds, &ij, &data, &sigmas);
+      FlattenHuber(&huber);
+      const smhip_status s = smhip_pose_graph_optimize_robust(handle, NodeCount(), poses.data(), fixed.data(), static_cast<int>(kinds.size()), kinds.data(),
+                                                              ij.data(), data.data(), sigmas.data(), huber.data(), options, stats);
+      if (s != SMHIP_OK) {
+        std::fprintf(stderr, "[ERROR] smhip_pose_graph_optimize_robust: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+        return false;
+      }
+      SetFlatNodePoses(poses);
+      return true;
+    }
     if (HasFactors()) {
       std::vector<double> poses, data, sigmas;
       std::vector<int32_t> ij;
@@ -147,6 +185,23 @@ class PoseGraph {
       return false;
     }
     SetFlatPoses(poses);
+    return true;
+  }
+  // smhip_pose_graph_last_robust for the solve Optimize ran last on `handle`, with this graph as it was then: per factor, in the
+  // order of FlattenFactors, s_f, w_f and the cost term at the poses the solve ended at.  Any pointer may be null.  false (the reason
+  // on stderr) when refused.
+  bool Report(smhip_handle handle, std::vector<double>* norm, std::vector<double>* weight, std::vector<double>* cost = nullptr) const {
+    SMHIP_CHECK(handle != nullptr, "PoseGraph::Report needs a device handle");
+    const size_t m = static_cast<size_t>(FactorCount());
+    if (norm) norm->assign(m, 0.0);
+    if (weight) weight->assign(m, 0.0);
+    if (cost) cost->assign(m, 0.0);
+    const smhip_status s = smhip_pose_graph_last_robust(handle, static_cast<int>(m), norm ? norm->data() : nullptr, weight ? weight->data() : nullptr,
+                                                        cost ? cost->data() : nullptr);
+    if (s != SMHIP_OK) {
+      std::fprintf(stderr, "[ERROR] smhip_pose_graph_last_robust: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+      return false;
+    }
     return true;
   }
   // the C ABI's arrays: 16 doubles per pose and per measurement (column-major), index pairs, 6 sigmas per edge
@@ -207,11 +262,12 @@ class PoseGraph {
   const std::vector<Edge>& Edges() const { return edges_; }
 
  private:
-  void AddEdge(int i, int j, const Matrix4d& transform, const Sigmas& sigmas) {
+  void AddEdge(int i, int j, const Matrix4d& transform, const Sigmas& sigmas, double huber) {
     const int n = static_cast<int>(poses_.size());
     SMHIP_CHECK(i >= 0 && j >= 0 && i < n && j < n && i != j, "an edge joins two different vertices that exist");
+    SMHIP_CHECK(std::isfinite(huber) && huber >= 0.0, "a Huber threshold is finite and not negative");
     Edge e;
-    e.i = i; e.j = j; e.transform = transform; e.sigmas = sigmas;
+    e.i = i; e.j = j; e.transform = transform; e.sigmas = sigmas; e.huber = huber;
     edges_.push_back(e);
   }
   std::vector<Matrix4d> poses_;
@@ -230,6 +286,15 @@ struct IsamOptimizerOptions {
   int gps_factor_sample_step = 1;
   double gps_factor_init_angle_rad = 1.6;
   bool enable_extrinsic_calib = false;   // true is refused: the tf_error point (GPS_CALIB_KEY) is not restated
+  double loop_closure_huber = 0.0;    // the Huber threshold of every loop edge, and of nothing else.  0: none, the reference's
+                                      // IsamOptimizer (:82-83); 1.0: the multi-trajectory optimiser's loop_closure_model_
+                                      // (multi_trajectory_optimizer.cc:68-81)
+};
+
+// One loop edge after the last solve: s_f and w_f of include/smhip.h, "Robust factors" (weight 1: taken at full weight)
+struct LoopEdgeWeight {
+  int target = 0, source = 0;
+  double norm = 0.0, weight = 1.0;
 };
 
 // view_graph.h's GraphItem without the picture: what GetWholeGraph returns
@@ -244,14 +309,18 @@ class IsamOptimizer {
   // TEST HOOK, not part of the reference's class: `solver` replaces the device solve (tests without a device); it optimises the
   // graph in place and returns false when it could not
   using Solver = std::function<bool(PoseGraph*)>;
+  // TEST HOOK beside it: `reporter` replaces PoseGraph::Report, for the graph at the poses the solver left
+  using Reporter = std::function<bool(const PoseGraph&, std::vector<double>* norm, std::vector<double>* weight)>;
 
   IsamOptimizer(const IsamOptimizerOptions& options, const LoopDetectorSettings& l_d_setting, smhip_handle handle)
       : loop_detector_(new LoopDetector(l_d_setting)), options_(options), handle_(handle) {
     SMHIP_CHECK(!options.enable_extrinsic_calib, "enable_extrinsic_calib is not restated: the GPS_CALIB_KEY point and the odometry calibration are out of scope");
+    SMHIP_CHECK(std::isfinite(options.loop_closure_huber) && options.loop_closure_huber >= 0.0, "loop_closure_huber is finite and not negative");
   }
   IsamOptimizer(const IsamOptimizer&) = delete;
   IsamOptimizer& operator=(const IsamOptimizer&) = delete;
   void SetSolver(Solver solver) { solver_ = std::move(solver); }
+  void SetReporter(Reporter reporter) { reporter_ = std::move(reporter); }
   // tf_tracking_gps_: only its translation is used (:247-248), the antenna in the tracking frame
   void SetTransformTrackingToGps(const Matrix4d& t) { for (int c = 0; c < 3; ++c) gps_lever_[c] = t(c, 3); }
 
@@ -273,7 +342,8 @@ class IsamOptimizer {
     bool ok = Update();                                                                         // IsamUpdate of :172
     if (result.close_succeed) {                                                                 // :227-236
       for (const LoopEdge& edge : result.edges) {
-        graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, LoopClosureSigmas());
+        loop_edge_at_.push_back(static_cast<int>(graph_.Edges().size()));
+        graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, LoopClosureSigmas(), options_.loop_closure_huber);
         ++loop_edges_;
       }
       ok = Update() && ok;
@@ -331,6 +401,22 @@ class IsamOptimizer {
   const PoseGraph& Graph() const { return graph_; }
   LoopDetector* GetLoopDetector() { return loop_detector_.get(); }
   int LoopEdgeCount() const { return loop_edges_; }
+  // Every loop edge, in the order added, with its norm and weight at the poses of the last solve of the main graph (one launch of
+  // the report; not SolveGpsCorrdAlone's own graph, so ask before a frame that runs it or after the next solve).  Empty when there
+  // is no loop edge, no solve has run yet or the report was refused.
+  std::vector<LoopEdgeWeight> LoopEdgeReport() const {
+    std::vector<LoopEdgeWeight> out;
+    if (loop_edge_at_.empty() || !main_solved_) return out;
+    std::vector<double> norm, weight;
+    if (!(reporter_ ? reporter_(graph_, &norm, &weight) : graph_.Report(handle_, &norm, &weight, nullptr))) return out;
+    for (int at : loop_edge_at_) {
+      const PoseGraph::Edge& e = graph_.Edges()[static_cast<size_t>(at)];
+      LoopEdgeWeight w;
+      w.target = e.i; w.source = e.j; w.norm = norm[static_cast<size_t>(at)]; w.weight = weight[static_cast<size_t>(at)];
+      out.push_back(w);
+    }
+    return out;
+  }
   int SolveCount() const { return solves_; }
   const smhip_pose_graph_stats& LastStats() const { return last_stats_; }
 
@@ -348,6 +434,7 @@ class IsamOptimizer {
       ok = graph_.Optimize(handle_, &last_stats_, &o);
     }
     if (ok) ++solves_;
+    main_solved_ = ok;                                                                          // (the handle's last launch is this graph's, or none that counts)
     return ok;
   }
   void AddEnuFactor(int index, const std::array<double, 3>& enu) {                              // add_enu_factor, :238-262
@@ -376,6 +463,7 @@ class IsamOptimizer {
       o.max_iterations = 100;                                                                   // :331
       ok = alone.Optimize(handle_, &alone_stats_, &o);
     }
+    main_solved_ = false;                                                                       // the handle's last launch is the alone graph's
     if (!ok) return false;
     ++solves_;
     gps_coord_transform_ = alone.FrameVertexPose();                                             // :334
@@ -390,6 +478,9 @@ class IsamOptimizer {
   IsamOptimizerOptions options_;
   smhip_handle handle_ = nullptr;
   Solver solver_;
+  Reporter reporter_;
+  std::vector<int> loop_edge_at_;                   // the loop edges' places in graph_.Edges()
+  bool main_solved_ = false;                        // the last solve was one of graph_, as it is now, and it succeeded
   PoseGraph graph_;
   std::vector<std::shared_ptr<LoopFrame>> frames_;
   smhip_pose_graph_stats last_stats_{}, alone_stats_{};

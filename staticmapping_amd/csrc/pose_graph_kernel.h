@@ -11,6 +11,8 @@
 // Poses and measurements are 12 doubles here: the rotation row-major, then the translation.  A factor is a BETWEEN, a PRIOR or a
 // POINT (include/smhip.h, "Factor kinds"; tests/pose_graph_gps_ref.py); whatever its kind it has an index pair, 12 doubles of
 // data, 6 inverse sigmas and 6 rows of whitened A, B and residual, so only edge_cost and linearize_edge look at the kind.
+// Any factor may carry a Huber threshold (include/smhip.h, "Robust factors"; tests/pose_graph_robust_ref.py): the same two
+// functions turn s_f^2 into the cost term and the rows into the weighted rows, and nothing else of the loop knows.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -35,6 +37,7 @@ struct Dev {
   int max_it = 0, pcg_cap = 0;
   int pcg_budget = 0;                     // conjugate-gradient iterations of the whole launch (SMHIP_POSE_GRAPH_MAX_PCG_TOTAL)
   int probe = 0;                          // 1: first linearisation, gradient and M^-1 v only (smhip_pose_graph_last)
+                                          // 2: the report at the poses in cur, left there by the last loop (smhip_pose_graph_last_robust)
   // per node
   const double* pose0 = nullptr;          // 12: the poses as given
   double *cur = nullptr, *cand = nullptr; // 12
@@ -49,6 +52,9 @@ struct Dev {
   const double* sinv = nullptr;           // 6: 1 / sigma (POINT reads the first three)
   double *A = nullptr, *B = nullptr;      // 36, row-major, whitened
   double *rw = nullptr, *u = nullptr;     // 6: whitened residual; A p_i + B p_j
+  const double* huber = nullptr;          // 1: the Huber threshold k_f, 0 = none; nullptr: no threshold anywhere ("Robust factors")
+  double* wgt = nullptr;                  // 1: the weight w_f of the last linearisation (1, or k_f / s_f); nullptr: not kept
+  double *rep_s = nullptr, *rep_c = nullptr;   // 1: the report's s_f and cost term (its weight goes to wgt)
   // probe
   const double* v = nullptr;
   double* minv = nullptr;
@@ -138,7 +144,7 @@ PG_HD void point_error(const double* Xi, const double* Xj, const double* lz, dou
 
 // A PRIOR on node i around P is the BETWEEN from a constant node at P measured as the identity: the same residual, and that
 // factor's B is the PRIOR's only Jacobian.
-PG_HD double edge_cost(const Dev& d, const double* X, int e) {
+PG_HD double edge_norm2(const Dev& d, const double* X, int e) {
   const int kind = d.kind ? d.kind[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
   const double* Xi = X + 12 * (size_t)d.ij[2 * e];
   const double* Xj = X + 12 * (size_t)d.ij[2 * e + 1];
@@ -159,7 +165,26 @@ PG_HD double edge_cost(const Dev& d, const double* X, int e) {
   return s;
 }
 
-PG_HD void linearize_edge(const Dev& d, const double* X, int e) {
+// s_f^2 -> the factor's cost term: s_f^2 itself within the threshold (or without one), else 2 k_f s_f - k_f^2, twice the Huber loss
+PG_HD double huber_term(const Dev& d, int e, double s2) {
+  if (d.huber) {
+    const double k = d.huber[e];
+    if (k > 0.0 && s2 > k * k) return 2.0 * k * sqrt(s2) - k * k;
+  }
+  return s2;
+}
+// ... and its weight
+PG_HD double huber_weight(const Dev& d, int e, double s2) {
+  if (d.huber) {
+    const double k = d.huber[e];
+    if (k > 0.0 && s2 > k * k) return k / sqrt(s2);
+  }
+  return 1.0;
+}
+
+PG_HD double edge_cost(const Dev& d, const double* X, int e) { return huber_term(d, e, edge_norm2(d, X, e)); }
+
+PG_HD void linearize_edge_plain(const Dev& d, const double* X, int e) {
   const int kind = d.kind ? d.kind[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
   const double* Xi = X + 12 * (size_t)d.ij[2 * e];
   const double* Xj = X + 12 * (size_t)d.ij[2 * e + 1];
@@ -209,6 +234,24 @@ PG_HD void linearize_edge(const Dev& d, const double* X, int e) {
     }
   if (prior) for (int k = 0; k < 36; ++k) A[k] = 0.0;
   for (int a = 0; a < 6; ++a) d.rw[6 * (size_t)e + a] = err[a] * sinv[a];
+}
+
+// The whitened rows exactly as without thresholds, then -- only where w_f < 1 -- times sqrt(w_f): J^T r becomes the gradient of half
+// the robust cost and H the sum of w J^T J (GTSAM's Robust::WhitenSystem).  The plain rows are written first and scaled from
+// memory, so that their expressions, and with them their bits, stay what they are without a threshold.
+PG_HD void linearize_edge(const Dev& d, const double* X, int e) {
+  linearize_edge_plain(d, X, e);
+  double* rw = d.rw + 6 * (size_t)e;
+  double s2 = 0.0;
+  for (int a = 0; a < 6; ++a) s2 += rw[a] * rw[a];                              // (rows 3..5 of a POINT are zero)
+  const double w = huber_weight(d, e, s2);
+  if (d.wgt) d.wgt[e] = w;
+  if (!(w < 1.0)) return;
+  const double q = sqrt(w);
+  double* A = d.A + 36 * (size_t)e;
+  double* B = d.B + 36 * (size_t)e;
+  for (int k = 0; k < 36; ++k) { A[k] *= q; B[k] *= q; }
+  for (int a = 0; a < 6; ++a) rw[a] *= q;
 }
 
 // ---- 6x6 blocks -------------------------------------------------------------------------------------------------------------
@@ -463,10 +506,15 @@ template <class Ctx>
 PG_HD void run(const Dev& d, Ctx& c) {
   double* cur = d.cur;
   double* cand = d.cand;
-  for (int k = c.tid(); k < 12 * d.n; k += c.nthreads()) cur[k] = d.pose0[k];
-  c.sync();
-  if (d.probe) {
-    linearize(d, c, cur);
+  if (d.probe == 2) {                                                        // one thread, one factor; cur is only read
+    for (int e = c.tid(); e < d.m; e += c.nthreads()) {
+      const double s2 = edge_norm2(d, cur, e);
+      d.rep_s[e] = sqrt(s2); d.wgt[e] = huber_weight(d, e, s2); d.rep_c[e] = huber_term(d, e, s2);
+    }
+    return;
+  }
+  if (d.probe) {                                                             // (at pose0 itself: cur keeps the last loop's result for the report)
+    linearize(d, c, d.pose0);
     assemble(d, c);
     factor(d, c, 0.0);
     for (int k = c.tid(); k < 6 * d.n; k += c.nthreads()) d.r[k] = d.fixed[k / 6] ? 0.0 : d.v[k];
@@ -474,6 +522,8 @@ PG_HD void run(const Dev& d, Ctx& c) {
     apply_minv(d, c, d.r, d.minv);
     return;
   }
+  for (int k = c.tid(); k < 12 * d.n; k += c.nthreads()) cur[k] = d.pose0[k];
+  c.sync();
   double c0 = total_cost(d, c, cur);
   const double initial = c0;
   double lambda = 0.0;

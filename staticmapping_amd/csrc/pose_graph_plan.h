@@ -118,6 +118,20 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
   return SMHIP_OK;
 }
 
+// check_and_plan_factors, then the Huber thresholds (one per factor, nullptr = none): each finite and not negative
+inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                          const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
+  Plan made;
+  if (const smhip_status s = check_and_plan_factors(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, &made, why)) return s;
+  for (int e = 0; huber && e < n_factors; ++e)
+    if (!std::isfinite(huber[e]) || huber[e] < 0.0) {
+      if (why) *why = "pose graph: edge " + std::to_string(e) + " has a Huber threshold that is negative or not finite";
+      return SMHIP_ERR_INVALID_ARGUMENT;
+    }
+  if (plan) *plan = made;
+  return SMHIP_OK;
+}
+
 inline smhip_status check_and_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
                                    const double* edge_sigmas, Plan* plan, std::string* why) {
   return check_and_plan_factors(n_nodes, poses, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, plan, why);

@@ -127,6 +127,14 @@ Args Parse(int argc, char** argv) {
     else if (k == "--loop-use-descriptor") a.loop.use_descriptor = std::atoi(val().c_str()) != 0;
     else if (k == "--loop-m2dp-score") a.loop.m2dp_match_score = static_cast<float>(std::atof(val().c_str()));
     else if (k == "--loop-accept-score") a.loop.accept_scan_match_score = static_cast<float>(std::atof(val().c_str()));
+    else if (k == "--loop-huber") {
+      const std::string text = val();
+      char* end = nullptr;
+      a.loop_huber = std::strtod(text.c_str(), &end);
+      if (text.empty() || *end != '\0') a.loop_huber = std::nan("");                  // (refused below)
+      a.loop_huber_given = true;
+    }
+    else if (k == "--loop-report") a.loop_report = val();
     else if (k == "--gps-enu") a.gps_enu = val();
     else if (k == "--gps-lever") { if (std::sscanf(val().c_str(), "%lf,%lf,%lf", &a.gps_lever[0], &a.gps_lever[1], &a.gps_lever[2]) != 3) Die("--gps-lever takes x,y,z"); }
     else if (k == "--gps-init-num") a.gps_init_num = std::atoi(val().c_str());
@@ -143,7 +151,8 @@ Args Parse(int argc, char** argv) {
              "[--package-border-offset 100] [--package-prefix part_] [--package-descript map_package.xml]\n"
              "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]\n"
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
-             "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75]\n"
+             "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75] "
+             "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)]\n"
              "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
              "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]");
   }
@@ -160,11 +169,14 @@ Args Parse(int argc, char** argv) {
   if (!a.submap_edges.empty() && !a.map_poses.empty()) Die("--submap-edges needs the alignment run (not --map-poses)");
   if (!a.close_loops.empty() && !a.map_poses.empty()) Die("--close-loops needs the alignment run (not --map-poses)");
   if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
+  if (a.loop_huber_given && a.close_loops.empty()) Die("--loop-huber needs --close-loops");
+  if (!a.loop_report.empty() && a.close_loops.empty()) Die("--loop-report needs --close-loops");
   if (a.gps_output_enu && a.gps_enu.empty()) Die("--gps-output-enu needs --gps-enu");
   if (!std::isfinite(a.gps_lever[0]) || !std::isfinite(a.gps_lever[1]) || !std::isfinite(a.gps_lever[2]) || !std::isfinite(a.gps_init_angle) || a.gps_init_num < 0)
     Die("bad GPS setting (--gps-lever finite, --gps-init-angle finite, --gps-init-num >= 0)");
   if (a.loop.nearest_history_pos_num < 1 || a.loop.loop_ignore_threshold < 0 || a.loop.trying_detect_loop_count < 1)
     Die("bad loop setting (--loop-history >= 1, --loop-ignore-threshold >= 0, --loop-detect-count >= 1)");
+  if (!std::isfinite(a.loop_huber) || a.loop_huber < 0.0) Die("bad loop setting (--loop-huber finite and >= 0)");
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
   if (a.world < 0 && std::getenv("WORLD_SIZE")) a.world = std::atoi(std::getenv("WORLD_SIZE"));
   if (a.local_rank < 0 && std::getenv("LOCAL_RANK")) a.local_rank = std::atoi(std::getenv("LOCAL_RANK"));

@@ -54,6 +54,11 @@ struct Args {
   // descriptor gate on as in the shipped KITTI config
   std::string close_loops;
   smhip::back_end::LoopDetectorSettings loop = [] { smhip::back_end::LoopDetectorSettings s; s.use_descriptor = true; return s; }();
+  // --loop-huber K: IsamOptimizerOptions::loop_closure_huber, the Huber threshold of every loop edge (0: none); --loop-report FILE: a
+  // line per loop edge after the last solve
+  double loop_huber = 0.0;
+  bool loop_huber_given = false;
+  std::string loop_report;
   // --gps-enu FILE: one line per scan in file order, three numbers already in ENU metres, nan = no fix (the geodetic conversion is
   // not restated); the factors' settings (isam_optimizer.h:61-66) and the antenna in the tracking frame
   std::string gps_enu;
@@ -391,7 +396,13 @@ inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files,
 // (--gps-lever x,y,z: the antenna in the tracking frame; --gps-init-num, --gps-sample-step, --gps-init-angle: isam_optimizer.h:61-66);
 // --gps-output-enu premultiplies every submap pose by GetGpsCoordTransform() before UpdateInnerFramePose (map_builder.cc:748-762),
 // so PATH is in the ENU frame.  --gps-enu without --close-loops, or a FILE whose line count is not the scan count, ends the run
-// with exit 2 before any device work.  Returns 0, or 3 when the device refused something (the file is then removed).
+// with exit 2 before any device work.
+// --loop-huber K gives every loop edge, and nothing else, the Huber threshold K (IsamOptimizerOptions::loop_closure_huber; DESIGN.md
+// section 6, "Robust factors"): a wrong match that settles metres off is then down-weighted instead of dragging the ring, and the JSON
+// line gains "loop_edges_downweighted", the loop edges that end with a weight below 1.  --loop-report FILE writes one line per loop
+// edge after the last solve, in the order added: target source norm weight (%.8g; weight 1 = taken at full weight, also without
+// --loop-huber, where the norm alone shows the strain).  Either without --close-loops, or a K that is negative or not finite, ends
+// the run with exit 2 before any device work.  Returns 0, or 3 when the device refused something (the file is then removed and no report written).
 inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
   namespace be = smhip::back_end;
   namespace bld = smhip::builder;
@@ -401,7 +412,9 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   struct {
     int loop_edges = 0, solves = 0, stop_reason = 0; double final_cost = 0.0, moved_m = 0.0;
     int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
+    int downweighted = 0;                                                                             // with --loop-huber
   } res;
+  std::vector<smhip::back_end::LoopEdgeWeight> loop_report;
   std::ofstream out(a.close_loops);
   if (!out) Die("cannot write " + a.close_loops);
   out.precision(8);
@@ -420,6 +433,7 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     be::IsamOptimizerOptions io;
     io.use_gps = !a.gps_enu.empty();
     io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
+    io.loop_closure_huber = a.loop_huber;
     be::IsamOptimizer optimizer(io, settings, h);
     {
       Matrix4d tracking_to_gps = Matrix4d::Identity();
@@ -475,6 +489,11 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
       if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
     }
     if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
+    if (rc == 0 && (a.loop_huber > 0.0 || !a.loop_report.empty())) {
+      loop_report = optimizer.LoopEdgeReport();
+      if (static_cast<int>(loop_report.size()) != optimizer.LoopEdgeCount()) { std::fprintf(stderr, "smhip_shard: the loop edges' report was refused\n"); rc = 3; }
+      for (const be::LoopEdgeWeight& w : loop_report) res.downweighted += w.weight < 1.0;
+    }
     if (rc == 0) {
       res.loop_edges = optimizer.LoopEdgeCount(); res.solves = optimizer.SolveCount();
       res.stop_reason = optimizer.LastStats().stop_reason; res.final_cost = optimizer.LastStats().final_cost;
@@ -507,9 +526,15 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   }
   out.close();
   if (rc != 0) { std::remove(a.close_loops.c_str()); return rc; }
+  if (!a.loop_report.empty()) {
+    std::ofstream rep(a.loop_report);
+    if (!rep) Die("cannot write " + a.loop_report);
+    for (const smhip::back_end::LoopEdgeWeight& w : loop_report) rep << Fmt("%d %d %.8g %.8g\n", w.target, w.source, w.norm, w.weight);
+  }
   *fields += Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
                  "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), S,
                  res.loop_edges, res.solves, res.stop_reason, res.final_cost, res.moved_m, Since(t0));
+  if (a.loop_huber > 0.0) *fields += Fmt(", \"loop_edges_downweighted\": %d", res.downweighted);
   if (!a.gps_enu.empty()) {
     *fields += Fmt(", \"gps_factors\": %d, \"gps_coord\": [", res.gps_factors);
     for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.gps_coord[q], q == 15 ? "]" : ", ");

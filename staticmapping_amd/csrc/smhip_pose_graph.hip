@@ -6,7 +6,7 @@
 // and nothing read back in between (pose_graph_kernel.h holds the loop; it also compiles for a CPU).  The work between two
 // barriers is a few thousand 6x6 block operations at most, so a grid-wide seam would cost more than what it separates.
 //   linearise     one thread per factor: e, the whitened A and B; the only place that knows a factor's kind (BETWEEN, PRIOR, POINT:
-//                 include/smhip.h, "Factor kinds")
+//                 include/smhip.h, "Factor kinds") and, with the cost, its Huber threshold ("Robust factors")
 //   assemble      one thread per node, its edges in index order (the host's CSR list): Hkk, g, the chain block -- no atomics
 //   factor        block cyclic reduction of M = the block-tridiagonal part of H + lambda blockdiag(H): two barriers per level
 //   pcg           H p matrix-free (per edge, then per node), M^-1 by one sweep up and one down the levels, dot products as
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_solve(const pg::Dev d) 
 }
 
 // doubles and words of the device state per node / per edge, and of the staging the host fills
-constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6;
+constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6 + 4;      // (+ huber, wgt, rep_s, rep_c)
 constexpr int kNodeI = 2, kEdgeI = 5;           // fixed, csr_off (+1); ij, csr_edge, kind
 
 }  // namespace
@@ -72,6 +72,7 @@ struct smhip_pose_graph_state {
   std::vector<int32_t> host_i;
   pg::Plan plan;
   int last_n = -1, last_m = 0;     // what smhip_pose_graph_last can run again (-1: nothing)
+  bool last_huber = false;         // that call uploaded thresholds
 };
 
 namespace {
@@ -87,13 +88,14 @@ smhip_status pg_ensure(smhip_context* h) {
   double* p = st->dbl;
   auto take = [&p](size_t count) { double* r = p; p += count; return r; };
   pg::Dev& d = st->dev;
-  // (what the host uploads: pose0, Z, sinv; v for the probe)
-  d.pose0 = take(12 * N); d.Z = take(12 * M); d.sinv = take(6 * M);
+  // (what the host uploads: pose0, Z, sinv, huber; v for the probe)
+  d.pose0 = take(12 * N); d.Z = take(12 * M); d.sinv = take(6 * M); d.huber = take(M);
   d.v = take(6 * N); d.minv = take(6 * N);
   d.cur = take(12 * N); d.cand = take(12 * N);
   d.Hkk = take(36 * N); d.C = take(36 * N); d.D = take(36 * N); d.U = take(36 * N); d.Dinv = take(36 * N); d.Wm = take(36 * N); d.Wp = take(36 * N);
   d.g = take(6 * N); d.x = take(6 * N); d.r = take(6 * N); d.z = take(6 * N); d.p = take(6 * N); d.q = take(6 * N); d.b = take(6 * N);
   d.A = take(36 * M); d.B = take(36 * M); d.rw = take(6 * M); d.u = take(6 * M);
+  d.wgt = take(M); d.rep_s = take(M); d.rep_c = take(M);
   d.out_d = take(pg::kOutDoubles);
   int32_t* q = st->ints;
   auto takei = [&q](size_t count) { int32_t* r = q; q += count; return r; };
@@ -131,9 +133,15 @@ void smhip_pose_graph_default_options(smhip_pose_graph_options* o) {
 
 smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
                                            const double* data, const double* sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  return smhip_pose_graph_plan_robust(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, nullptr, csr_offsets, csr_edges, why, why_len);
+}
+
+smhip_status smhip_pose_graph_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                          const double* data, const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why,
+                                          int why_len) {
   pg::Plan plan;
   std::string text;
-  const smhip_status s = pg::check_and_plan_factors(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, &plan, &text);
+  const smhip_status s = pg::check_and_plan_robust(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &plan, &text);
   if (why && why_len > 0) { std::strncpy(why, text.c_str(), (size_t)why_len - 1); why[why_len - 1] = '\0'; }
   if (s) return s;
   if (csr_offsets) std::memcpy(csr_offsets, plan.csr_offsets.data(), sizeof(int32_t) * plan.csr_offsets.size());
@@ -155,13 +163,19 @@ smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* pose
 smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
                                                const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas,
                                                const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+  return smhip_pose_graph_optimize_robust(h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, nullptr, opts, stats);
+}
+
+smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                              const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
+                                              const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   smhip_pose_graph_options o;
   smhip_pose_graph_default_options(&o);
   if (opts) o = *opts;
   if (o.max_iterations < 1) { h->err = "pose graph: max_iterations must be at least 1"; return SMHIP_ERR_INVALID_ARGUMENT; }
   pg::Plan plan;
-  if (const smhip_status s = pg::check_and_plan_factors(n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, &plan, &h->err)) return s;
+  if (const smhip_status s = pg::check_and_plan_robust(n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, &plan, &h->err)) return s;
   HIPCHK(h, hipSetDevice(h->device));
   if (const smhip_status s = pg_ensure(h)) return s;
   smhip_pose_graph_state* st = h->pose_graph;
@@ -194,6 +208,9 @@ smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, doub
   hipStream_t s = h->stream;
   pg::Dev d = st->dev;
   d.n = n_nodes; d.m = n_edges; d.max_it = o.max_iterations; d.pcg_cap = plan.pcg_cap; d.pcg_budget = SMHIP_POSE_GRAPH_MAX_PCG_TOTAL; d.probe = 0;
+  const bool robust = huber != nullptr && n_edges > 0;
+  if (robust) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.huber), huber, sizeof(double) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+  else d.huber = nullptr;
   HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.pose0), hd, sizeof(double) * 12 * (size_t)n_nodes, hipMemcpyHostToDevice, s));
   if (n_edges > 0) {
     HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.Z), hd + 12 * N, sizeof(double) * 12 * (size_t)n_edges, hipMemcpyHostToDevice, s));
@@ -212,7 +229,7 @@ smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, doub
   HIPCHK(h, hipMemcpyAsync(out_d, d.out_d, sizeof(out_d), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(out_i, d.out_i, sizeof(out_i), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  st->last_n = n_nodes; st->last_m = n_edges;
+  st->last_n = n_nodes; st->last_m = n_edges; st->last_huber = robust;
   if (stats) {
     stats->initial_cost = out_d[pg::kOutInitial]; stats->final_cost = out_d[pg::kOutFinal]; stats->damping = out_d[pg::kOutLambda];
     stats->stop_reason = out_i[pg::kOutStop]; stats->iterations = out_i[pg::kOutIterations];
@@ -252,6 +269,7 @@ smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, dou
   hipStream_t s = h->stream;
   pg::Dev d = st->dev;
   d.n = n; d.m = m; d.max_it = 0; d.pcg_cap = 0; d.probe = 1;
+  if (!st->last_huber) d.huber = nullptr;
   if (v) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.v), v, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, s));
   else HIPCHK(h, hipMemsetAsync(const_cast<double*>(d.v), 0, sizeof(double) * 6 * (size_t)n, s));
   hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
@@ -261,6 +279,30 @@ smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, dou
   if (B && m > 0) HIPCHK(h, hipMemcpyAsync(B, d.B, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
   if (gradient) HIPCHK(h, hipMemcpyAsync(gradient, d.g, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
   if (minv_v) HIPCHK(h, hipMemcpyAsync(minv_v, d.minv, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return SMHIP_OK;
+}
+
+smhip_status smhip_pose_graph_last_robust(smhip_handle h, int n_factors, double* norm, double* weight, double* cost) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  smhip_pose_graph_state* st = h->pose_graph;
+  if (!st || st->last_n < 0) { h->err = "pose graph: no optimisation has been launched on this handle"; return SMHIP_ERR_NOT_READY; }
+  if (n_factors != st->last_m) {
+    h->err = "pose graph: the last optimisation had " + std::to_string(st->last_m) + " factors, not the count given";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  const int m = st->last_m;
+  if (m == 0) return SMHIP_OK;
+  hipStream_t s = h->stream;
+  pg::Dev d = st->dev;
+  d.n = st->last_n; d.m = m; d.max_it = 0; d.pcg_cap = 0; d.probe = 2;
+  if (!st->last_huber) d.huber = nullptr;
+  hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
+  HIPCHK(h, hipGetLastError());
+  if (norm) HIPCHK(h, hipMemcpyAsync(norm, d.rep_s, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (weight) HIPCHK(h, hipMemcpyAsync(weight, d.wgt, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (cost) HIPCHK(h, hipMemcpyAsync(cost, d.rep_c, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   return SMHIP_OK;
 }

@@ -1,6 +1,6 @@
 """ctypes view of the device pose-graph optimiser (include/smhip.h, `smhip_pose_graph_*`): what back_end::IsamOptimizer asks of GTSAM
 in the reference (back_end/isam_optimizer.{h,cc}) -- rigid poses, between-factors, fixed nodes, and the PRIOR and POINT factors behind its GPS / ENU factors
-(*_factors below) -- as one kernel launch per optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
+(*_factors below), any of them with a Huber threshold (*_robust) -- as one kernel launch per optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
 from __future__ import annotations
 
 import ctypes
@@ -142,9 +142,60 @@ def optimize_factors(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, m
     return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
 
 
+def _huber(huber, n_factors):
+    if huber is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(huber, np.float64), (n_factors,)))
+
+
+def plan_robust(poses, kinds, ij, data, fixed=None, sigmas=None, huber=None):
+    """plan_factors() plus huber: one Huber threshold per factor ([F] or a scalar; 0 = none) or None for none at all (include/smhip.h,
+    "Robust factors").  A threshold that is negative or not finite raises PoseGraphRefused."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    off = np.zeros(len(P) + 1, np.int32)
+    inc = np.zeros(max(2 * len(E), 1), np.int32)
+    why = ctypes.create_string_buffer(256)
+    s = _capi.load_library().smhip_pose_graph_plan_robust(len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                          _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                          _ptr(H, _capi.c_double_p), off.ctypes.data_as(_capi.c_int32_p),
+                                                          inc.ctypes.data_as(_capi.c_int32_p), why, len(why))
+    if s != 0:
+        raise PoseGraphRefused(s, why.value.decode())
+    return off, inc[:off[-1]]
+
+
+def optimize_robust(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, huber=None, max_iterations: int | None = None):
+    """optimize_factors() with Huber thresholds; the arguments of plan_robust().  Returns (poses [N, 4, 4], stats dict); last() then
+    gives the weighted rows and last_robust() every factor's norm, weight and cost term."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    lib = matcher._lib
+    o = _capi.PoseGraphOptions()
+    lib.smhip_pose_graph_default_options(ctypes.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = max_iterations
+    st = _capi.PoseGraphStats()
+    matcher._check(lib.smhip_pose_graph_optimize_robust(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                        _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                        _ptr(H, _capi.c_double_p), ctypes.byref(o), ctypes.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
+    stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
+
+
+def last_robust(matcher, n_factors: int):
+    """The report of the last optimise call on the handle, whichever it was, which had n_factors factors (another count is refused): dict(norm [F]
+    = s_f, weight [F] = w_f, cost [F] = the cost term) at the poses that call ended at.  After a call without thresholds every weight is 1."""
+    norm, weight, cost = np.zeros(n_factors), np.zeros(n_factors), np.zeros(n_factors)
+    matcher._check(matcher._lib.smhip_pose_graph_last_robust(matcher._h, n_factors, _ptr(norm, _capi.c_double_p), _ptr(weight, _capi.c_double_p),
+                                                             _ptr(cost, _capi.c_double_p)))
+    return dict(norm=norm, weight=weight, cost=cost)
+
+
 def last(matcher, n_nodes: int, n_edges: int, v=None):
     """Parity hook: the first linearisation of the last optimize() on the handle, which had n_nodes and n_edges (other sizes are refused).  Returns dict(r [E, 6]
-    whitened residuals, A, B [E, 6, 6] whitened, g [N, 6], minv_v [N, 6] = M^-1 v or None without v)."""
+    whitened residuals, A, B [E, 6, 6] whitened, g [N, 6], minv_v [N, 6] = M^-1 v or None without v).  After optimize_robust() the rows are the weighted ones."""
     r = np.zeros((n_edges, 6))
     A = np.zeros((n_edges, 6, 6))
     B = np.zeros((n_edges, 6, 6))

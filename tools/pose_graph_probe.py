@@ -4,6 +4,9 @@ chained odometry.  Median of --repeats calls after --warmup calls, a host clock 
 the graph, launches, and copies the poses back).  Beside it, as the yardstick on the same box, the restatement with scipy's sparse
 direct solve: its whole time (the linearisation there is a Python loop) and the time inside the sparse solves alone.
 --gps: instead, the same size as four laps with no loop edge and a GPS (ENU) factor on every submap (profiles/pose_graph_gps_probe.json).
+--huber K: the two loop cases through smhip_pose_graph_optimize_robust with the Huber threshold K on every loop edge (DESIGN.md section 6,
+"Robust factors"); --bad-loops M: M wrong loop edges beside the good ones, alternately 3 m ahead and 3 m behind (as many as the overlap has
+room for: one with 3 loop edges, four with 60), with or without --huber.  Without either flag the run is what it was.
 One JSON line on stdout (and in --out when given)."""
 import argparse
 import json
@@ -51,12 +54,41 @@ def gps_case(m, a):
     return case
 
 
+def robust_case(m, a, drive, n_loops, overlap):
+    """the loop case `drive` as factors, plus --bad-loops wrong loop edges, solved with the threshold --huber on the loop edges"""
+    import pose_graph_robust_cases as cases
+    from staticmapping_amd import pose_graph
+    period = N_NODES - overlap
+    bad = [(n_loops + q, n_loops + q + period, (3.0 if q % 2 == 0 else -3.0, 0.0, 0.0), 0.0) for q in range(min(a.bad_loops, overlap - n_loops))]
+    g = cases.as_factors(drive, n_loops, bad, k=a.huber)
+    hub = g["huber"] if a.huber > 0.0 else None
+
+    def call():
+        return pose_graph.optimize_robust(m, g["poses"], g["kinds"], g["ij"], g["data"], fixed=g["fixed"], sigmas=g["sigmas"], huber=hub)
+    for _ in range(a.warmup):
+        call()
+    t = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        poses, stats = call()
+        t.append(time.perf_counter() - t0)
+    rep = pose_graph.last_robust(m, len(g["kinds"]))
+    return {"loop_edges": n_loops, "bad_loop_edges": len(bad), "huber": a.huber, "edges": int(len(g["kinds"])), "device_median_ms": round(float(np.median(t)) * 1e3, 4),
+            "device_min_ms": round(float(np.min(t)) * 1e3, 4), "outer_steps": stats["iterations"], "rejected_steps": stats["rejected_steps"],
+            "pcg_iterations": stats["pcg_iterations"], "pcg_longest_solve": stats["pcg_max_iterations"], "pcg_cap": stats["pcg_cap"],
+            "levels": stats["levels"], "stop": stats["stop"], "initial_cost": stats["initial_cost"], "final_cost": stats["final_cost"],
+            "loop_edges_downweighted": int((rep["weight"] < 1.0).sum()), "bad_loop_weights": [float(w) for w in rep["weight"][g["bad"]]],
+            "truth_error_m": cases.truth_error(g, poses)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-restatement", action="store_true")
     ap.add_argument("--gps", action="store_true", help="the 909-submap drive that never closes a loop, with a GPS factor on every submap, instead of the two loop cases")
+    ap.add_argument("--huber", type=float, default=0.0, help="the Huber threshold of every loop edge (0: none), through smhip_pose_graph_optimize_robust")
+    ap.add_argument("--bad-loops", type=int, default=0, help="wrong loop edges added beside the good ones")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -73,6 +105,9 @@ def main():
     for n_loops in (() if a.gps else (3, 60)):
         # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
         g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
+        if a.huber > 0.0 or a.bad_loops > 0:
+            res["cases"].append(robust_case(m, a, g, n_loops, 4 if n_loops <= 4 else 64))
+            continue
 
         def call():
             return pose_graph.optimize(m, g["poses"], g["edges"], g["Z"], fixed=g["fixed"])
