@@ -607,8 +607,9 @@ double smhip_m2dp_match(const float* P, const float* Q, int n);
  * (isam_optimizer.cc:238-349): a PRIOR on one node, and a POINT between a frame node and an observed node.
  * smhip_pose_graph_*_robust give any factor a Huber threshold ("Robust factors" below): the reference's Robust(Huber(1), ...) of
  * isam_optimizer.cc:90-93 and of the multi-trajectory optimiser's between-factors (multi_trajectory_optimizer.cc:68-81).
- * Not restated: the odometry calibration factor (and with it the place the reference's IsamOptimizer puts its Huber model, :84-93),
- * IMU, ViewGraph's picture output, the multi-trajectory optimiser itself, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
+ * smhip_pose_graph_*_calib take a fourth kind, HANDEYE ("Odometry calibration factor" below): the reference's odometry calibration
+ * factor through ODOM_CALIB_KEY (:84-93, 153-162, 209-224, 361-367), the place its IsamOptimizer puts its Huber model.
+ * Not restated: IMU, ViewGraph's picture output, the multi-trajectory optimiser itself, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
  * conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300). */
 #define SMHIP_POSE_GRAPH_MAX_NODES 8192
 #define SMHIP_POSE_GRAPH_MAX_EDGES 32768
@@ -681,6 +682,7 @@ smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, dou
 #define SMHIP_POSE_GRAPH_FACTOR_BETWEEN 0
 #define SMHIP_POSE_GRAPH_FACTOR_PRIOR 1
 #define SMHIP_POSE_GRAPH_FACTOR_POINT 2
+#define SMHIP_POSE_GRAPH_FACTOR_HANDEYE 3   /* the *_calib entries only: "Odometry calibration factor" below */
 /* smhip_pose_graph_plan for factors of any kind.  kinds: one byte per factor, NULL = all BETWEEN; sigmas: NULL = the defaults of a
  * BETWEEN, refused when any other kind is present.  csr_edges: room for 2 n_factors indices; a PRIOR is listed once, so
  * csr_offsets[n_nodes] of them are written.  The refusals of smhip_pose_graph_optimize, and SMHIP_ERR_INVALID_ARGUMENT for: a kind
@@ -720,6 +722,27 @@ smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, doubl
  * After a call without thresholds every weight is 1.  SMHIP_ERR_INVALID_ARGUMENT when n_factors is not that call's count,
  * SMHIP_ERR_NOT_READY when no call got as far as the launch. */
 smhip_status smhip_pose_graph_last_robust(smhip_handle h, int n_factors, double* norm, double* weight, double* cost);
+/* Odometry calibration factor ("Odometry calibration factor"; tests/pose_graph_calib_ref.py).
+ *   HANDEYE  between a frame node i (pose X) and a calibration node j != i (pose T): data = Z, a rigid pose, column-major 4x4 -- the
+ *            odometer's pose relative to its first reading.  h = T^-1 X T, E = Z^-1 h, e = [Log_SO3(R_E); t_E], whitened by six
+ *            sigmas.  With B_h = [Jr^-1(e_w), 0; 0, R_E] and Ad(G) = [R_G, 0; hat(t_G) R_G, R_G]:  A = B_h Ad(T^-1),
+ *            B = B_h (I - Ad(h^-1)).  The reference's compose(between(calib_tf, pose), calib_tf) measured as
+ *            Pose3(GetRelatedOdom()) (isam_optimizer.cc:215-223), to first order in the residual.  The model assumes the frame
+ *            node of the first reading is at the identity.
+ * The *_calib entries take the argument lists of the *_robust ones and accept kinds 0..3; every other entry keeps refusing kind 3.
+ * Without a HANDEYE in the call every output has the bits of the *_robust call.  B vanishes where h is the identity and is
+ * rank-deficient for planar motion (the z of t_T and a rotation of T about the common axis are not seen), so beside the refusals of
+ * the *_robust forms, before anything is touched, SMHIP_ERR_INVALID_ARGUMENT for: a kind outside 0..3; a HANDEYE with i == j, a Z that
+ * is no rigid transform or a sigma that is not finite and positive; a free node that is the j of a HANDEYE and carries no PRIOR.  For
+ * its node i a HANDEYE counts like a BETWEEN (Ad is invertible); it connects components, and with |i - j| != 1 it is a non-chain edge
+ * of pcg_cap.  Huber thresholds act on it as on the other kinds, s_f^2 over six rows.  smhip_pose_graph_last and
+ * smhip_pose_graph_last_robust serve these calls too. */
+smhip_status smhip_pose_graph_plan_calib(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds,
+                                         const int32_t* ij, const double* data, const double* sigmas, const double* huber,
+                                         int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len);
+smhip_status smhip_pose_graph_optimize_calib(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
+                                             const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
+                                             const double* huber, const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

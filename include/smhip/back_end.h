@@ -136,6 +136,8 @@ struct LoopFrame {
   descriptor::M2dp::Descriptor descriptor;      // read when use_descriptor is set
   bool has_enu = false;                         // FrameBase::related_enu_ (builder/frame_base.h:93-95): the GPS fix of the frame,
   double enu[3] = {0.0, 0.0, 0.0};              // already in ENU metres; read by IsamOptimizer when use_gps is set
+  bool has_odom = false;                        // FrameBase::related_odom_ (HasOdom / GetRelatedOdom): the odometer's pose relative to
+  Matrix4d odom = Matrix4d::Identity();         // its first reading; read by IsamOptimizer when use_odom is set
 };
 
 struct LoopCandidates {

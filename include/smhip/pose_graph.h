@@ -23,6 +23,10 @@
 //                                                                 Gauss-Newton at a relative error of 1e-6 (:330); here the stop
 //                                                                 rules of smhip_pose_graph_optimize apply, with max_iterations 100
 //   IsamOptimizer::GetGpsCoordTransform :370-383
+//   the odometry calibration factor  :84-93, 153-162, 209-224,    use_odom: vertex 0 brings the calibration vertex (ODOM_CALIB_KEY) at tf_odom_lidar^-1,
+//                                    361-367                      and every frame with an odometer reading a HANDEYE factor (include/smhip.h,
+//                                                                 "Odometry calibration factor") of sigmas (0.2, 0.2, 0.2, 1.5, 1.5, 2) under
+//                                                                 Huber(odom_huber = 1); RunFinalOptimazation writes tf_odom_lidar back
 //
 // What differs from the reference, on purpose:
 //   * GTSAM's iSAM2 (incremental, dogleg, :70-76) is replaced by a batch solve from the current estimate on every update; the
@@ -32,12 +36,17 @@
 //     in the residual: the POINT factor of include/smhip.h.  AnalyseAllFramePoseForMaxRotation clamps the dot product to [-1, 1]
 //     before acos (the reference's can be NaN for two equal rotations, which compares as "not below the angle").  A
 //     SolveGpsCorrdAlone that fails leaves nothing behind: the next frame with a fix tries again.
-//   * The reference's IsamOptimizer puts its Robust(Huber(1), ...) on the odometry calibration factor alone (:84-93), which is not
-//     restated; its loop edges are plain.  The multi-trajectory optimiser puts Huber(1) on every between-factor, its
+//   * The reference's IsamOptimizer puts its Robust(Huber(1), ...) on the odometry calibration factor alone (:84-93):
+//     IsamOptimizerOptions::odom_huber; its loop edges are plain.  The multi-trajectory optimiser puts Huber(1) on every between-factor, its
 //     loop_closure_model_ among them (multi_trajectory_optimizer.cc:68-81).  IsamOptimizerOptions::loop_closure_huber offers that
 //     model for the loop edges here: 0 (the default) is the reference's IsamOptimizer, 1.0 the multi-trajectory optimiser's loop
 //     model.  The chain edges have no option: thresholds there make the loop converge slowly (include/smhip.h, "Robust factors").
-//   * Not restated, and without an option here: the odometry calibration factor (ODOM_CALIB_KEY), IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
+//   * Whether the calibration is estimated is an option of its own, odom_extrinsic_calib, in place of enable_extrinsic_calib (which
+//     also creates the GPS tf_error point and stays refused).  Held (the default), the calibration vertex is a fixed node where the
+//     reference has a prior of sigma 1e-6 (:87-88), for the reason DESIGN.md section 6 gives for node 0; free, it carries the
+//     reference's prior of (0.5, 0.5, 1.5, 0.1, 0.1, 0.1) (:85-86).  The vertex starts at tf_odom_lidar^-1 itself: the reference's
+//     detour through Euler angles (:154-157) is the same matrix up to rounding.
+//   * Not restated, and without an option here: IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
 //     geodetic conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300).  The tf_error
 //     calibration point (GPS_CALIB_KEY) is not created: enable_extrinsic_calib = true is refused.
 #ifndef SMHIP_POSE_GRAPH_H_
@@ -66,14 +75,18 @@ inline std::array<double, 3> GpsSigmas() { return {0.15, 0.15, 0.15}; }         
 inline Sigmas GpsCoordPriorSigmas() { return {0.1, 0.1, 0.2, 1.0, 1.0, 1.0}; }     // :340-343
 inline Sigmas AloneGpsCoordPriorSigmas() { return {0.2, 0.2, 1.57, 20.0, 20.0, 20.0}; }   // :306-309
 inline Sigmas AlonePosePriorSigmas() { return {1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2, 1.0e-2}; }   // :310
+inline Sigmas OdomSigmas() { return {0.2, 0.2, 0.2, 1.5, 1.5, 2.0}; }                // odom_noise_model_, :92-93
+inline Sigmas OdomCalibPriorSigmas() { return {0.5, 0.5, 1.5, 0.1, 0.1, 0.1}; }      // odom_tf_noise_model_ when the calibration is estimated, :85-86
 
 // The vertices and factors, in the arrays smhip_pose_graph_optimize / smhip_pose_graph_optimize_factors take.  The frame vertex (the
 // map origin in the GPS frame) is kept apart from the chain and emitted as the LAST node at every solve, so that chain vertices stay
-// index-adjacent and the preconditioner keeps solving the chain exactly.
+// index-adjacent and the preconditioner keeps solving the chain exactly.  The calibration vertex (the lidar-odometer extrinsic,
+// ODOM_CALIB_KEY) is kept apart likewise and emitted after the chain vertices and before the frame vertex, only when it is set.
 class PoseGraph {
  public:
   struct Edge { int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };   // huber: the factor's Huber threshold, 0 = none
-  // a PRIOR on vertex `index` around `pose`, or a POINT between the frame vertex and vertex `index`
+  // a PRIOR on vertex `index` around `pose`, a POINT between the frame vertex and vertex `index`, or a HANDEYE between vertex `index`
+  // and the calibration vertex measured as `pose`
   struct Factor { int kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; int index = 0; Matrix4d pose = Matrix4d::Identity(); double lever[3] = {0, 0, 0}, point[3] = {0, 0, 0}; Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };
 
   // :140-173.  Vertices come in index order; vertex 0 is constant.
@@ -118,34 +131,74 @@ class PoseGraph {
     f.sigmas = {sigmas3[0], sigmas3[1], sigmas3[2], 1.0, 1.0, 1.0};            // (the last three are not read)
     factors_.push_back(f);
   }
-  bool HasFactors() const { return has_frame_ || !factors_.empty(); }
+  // The calibration vertex at `pose`, held there (the reference's prior of sigma 1e-6 as a fixed node) ...
+  void SetCalibVertex(const Matrix4d& pose) { has_calib_ = true; calib_held_ = true; calib_pose_ = pose; calib_prior_ = pose; }
+  // ... or free under a prior around `pose`; set again, it moves and its prior with it.
+  void SetCalibVertex(const Matrix4d& pose, const Sigmas& prior_sigmas) {
+    has_calib_ = true; calib_held_ = false; calib_pose_ = pose; calib_prior_ = pose; calib_prior_sigmas_ = prior_sigmas;
+  }
+  bool HasCalibVertex() const { return has_calib_; }
+  bool CalibVertexHeld() const { return calib_held_; }
+  const Matrix4d& CalibVertexPose() const { return calib_pose_; }
+  // :209-224: calib^-1 * pose_index * calib = odom, six sigmas
+  void AddHandEyeFactor(int index, const Matrix4d& odom, const Sigmas& sigmas = OdomSigmas(), double huber = 0.0) {
+    SMHIP_CHECK(has_calib_, "a hand-eye factor needs the calibration vertex");
+    SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a hand-eye factor observes a vertex that exists");
+    SMHIP_CHECK(std::isfinite(huber) && huber >= 0.0, "a Huber threshold is finite and not negative");
+    Factor f;
+    f.kind = SMHIP_POSE_GRAPH_FACTOR_HANDEYE; f.index = index; f.pose = odom; f.sigmas = sigmas; f.huber = huber;
+    factors_.push_back(f);
+  }
+  int HandEyeFactorCount() const {
+    int n = 0;
+    for (const Factor& f : factors_) n += f.kind == SMHIP_POSE_GRAPH_FACTOR_HANDEYE;
+    return n;
+  }
+  bool HasFactors() const { return has_frame_ || has_calib_ || !factors_.empty(); }
   const std::vector<Factor>& Factors() const { return factors_; }
   int PointFactorCount() const {
     int n = 0;
     for (const Factor& f : factors_) n += f.kind == SMHIP_POSE_GRAPH_FACTOR_POINT;
     return n;
   }
-  int NodeCount() const { return static_cast<int>(poses_.size()) + (has_frame_ ? 1 : 0); }
-  // the factors of one solve: the between-factors, the frame vertex's prior, Factors()
-  int FactorCount() const { return static_cast<int>(edges_.size() + factors_.size()) + (has_frame_ ? 1 : 0); }
+  int NodeCount() const { return static_cast<int>(poses_.size()) + (has_calib_ ? 1 : 0) + (has_frame_ ? 1 : 0); }
+  // the factors of one solve: the between-factors, the free calibration vertex's prior, the frame vertex's prior, Factors()
+  int FactorCount() const { return static_cast<int>(edges_.size() + factors_.size()) + (has_calib_ && !calib_held_ ? 1 : 0) + (has_frame_ ? 1 : 0); }
   // some factor has a Huber threshold
   bool HasHuber() const {
     for (const Edge& e : edges_) if (e.huber != 0.0) return true;
     for (const Factor& f : factors_) if (f.huber != 0.0) return true;
     return false;
   }
-  // the thresholds in the order of FlattenFactors' factors (the frame vertex's prior has none)
+  // the thresholds in the order of FlattenFactors' factors (the calibration and frame vertices' priors have none)
   void FlattenHuber(std::vector<double>* huber) const {
     huber->clear();
     for (const Edge& e : edges_) huber->push_back(e.huber);
+    if (has_calib_ && !calib_held_) huber->push_back(0.0);
     if (has_frame_) huber->push_back(0.0);
     for (const Factor& f : factors_) huber->push_back(f.huber);
   }
   // One device solve from the current poses, which it replaces.  false (poses unchanged, the reason on stderr) when refused.  The
   // robust entry is called only when some threshold is not zero: without one the calls are those made before thresholds existed.
+  // Likewise the calib entry only when a HANDEYE factor exists.
   bool Optimize(smhip_handle handle, smhip_pose_graph_stats* stats = nullptr, const smhip_pose_graph_options* options = nullptr) {
     SMHIP_CHECK(handle != nullptr, "PoseGraph::Optimize needs a device handle");
     if (poses_.empty()) return true;
+    if (HandEyeFactorCount() > 0) {
+      std::vector<double> poses, data, sigmas, huber;
+      std::vector<int32_t> ij;
+      std::vector<uint8_t> fixed, kinds;
+      FlattenFactors(&poses, &fixed, &kinds, &ij, &data, &sigmas);
+      if (HasHuber()) FlattenHuber(&huber);
+      const smhip_status s = smhip_pose_graph_optimize_calib(handle, NodeCount(), poses.data(), fixed.data(), static_cast<int>(kinds.size()), kinds.data(),
+                                                             ij.data(), data.data(), sigmas.data(), huber.empty() ? nullptr : huber.data(), options, stats);
+      if (s != SMHIP_OK) {
+        std::fprintf(stderr, "[ERROR] smhip_pose_graph_optimize_calib: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+        return false;
+      }
+      SetFlatNodePoses(poses);
+      return true;
+    }
     if (HasHuber()) {
       std::vector<double> poses, data, sigmas, huber;
       std::vector<int32_t> ij;
@@ -214,20 +267,26 @@ class PoseGraph {
       sigmas->insert(sigmas->end(), e.sigmas.begin(), e.sigmas.end());
     }
   }
-  // The arrays of smhip_pose_graph_optimize_factors: the vertices and then the frame vertex (when set) as the last node; the
-  // between-factors in the order of Edges(), the frame vertex's prior, then Factors() in their order.
+  // The arrays of smhip_pose_graph_optimize_factors: the vertices, then the calibration vertex (when set), then the frame vertex (when
+  // set) as the last node; the between-factors in the order of Edges(), the calibration vertex's prior (when it is free), the frame
+  // vertex's prior, then Factors() in their order.
   void FlattenFactors(std::vector<double>* poses, std::vector<uint8_t>* fixed, std::vector<uint8_t>* kinds, std::vector<int32_t>* ij, std::vector<double>* data,
                       std::vector<double>* sigmas) const {
     Flatten(poses, ij, data, sigmas);
     *fixed = fixed_;
     kinds->assign(edges_.size(), SMHIP_POSE_GRAPH_FACTOR_BETWEEN);
-    const int frame = static_cast<int>(poses_.size());
+    const int calib = static_cast<int>(poses_.size()), frame = calib + (has_calib_ ? 1 : 0);
     auto put = [&](int kind, int i, int j, const double* d16, const Sigmas& s) {
       kinds->push_back(static_cast<uint8_t>(kind));
       ij->push_back(i); ij->push_back(j);
       data->insert(data->end(), d16, d16 + 16);
       sigmas->insert(sigmas->end(), s.begin(), s.end());
     };
+    if (has_calib_) {
+      poses->insert(poses->end(), calib_pose_.data(), calib_pose_.data() + 16);
+      fixed->push_back(calib_held_ ? 1 : 0);
+      if (!calib_held_) put(SMHIP_POSE_GRAPH_FACTOR_PRIOR, calib, calib, calib_prior_.data(), calib_prior_sigmas_);
+    }
     if (has_frame_) {
       poses->insert(poses->end(), frame_pose_.data(), frame_pose_.data() + 16);
       fixed->push_back(0);
@@ -236,6 +295,8 @@ class PoseGraph {
     for (const Factor& f : factors_) {
       if (f.kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) {
         put(f.kind, f.index, f.index, f.pose.data(), f.sigmas);
+      } else if (f.kind == SMHIP_POSE_GRAPH_FACTOR_HANDEYE) {
+        put(f.kind, f.index, calib, f.pose.data(), f.sigmas);
       } else {
         double d16[16] = {f.lever[0], f.lever[1], f.lever[2], f.point[0], f.point[1], f.point[2]};
         put(f.kind, frame, f.index, d16, f.sigmas);
@@ -247,8 +308,10 @@ class PoseGraph {
     SMHIP_CHECK(poses.size() == 16 * static_cast<size_t>(NodeCount()), "16 doubles per node");
     for (size_t k = 0; k < poses_.size(); ++k)
       for (int q = 0; q < 16; ++q) poses_[k].data()[q] = poses[16 * k + static_cast<size_t>(q)];
+    if (has_calib_)
+      for (int q = 0; q < 16; ++q) calib_pose_.data()[q] = poses[16 * poses_.size() + static_cast<size_t>(q)];
     if (has_frame_)
-      for (int q = 0; q < 16; ++q) frame_pose_.data()[q] = poses[16 * poses_.size() + static_cast<size_t>(q)];
+      for (int q = 0; q < 16; ++q) frame_pose_.data()[q] = poses[16 * (poses_.size() + (has_calib_ ? 1 : 0)) + static_cast<size_t>(q)];
   }
   void SetFlatPoses(const std::vector<double>& poses) {
     SMHIP_CHECK(poses.size() == 16 * poses_.size(), "16 doubles per vertex");
@@ -277,6 +340,9 @@ class PoseGraph {
   bool has_frame_ = false;
   Matrix4d frame_pose_ = Matrix4d::Identity(), frame_prior_ = Matrix4d::Identity();
   Sigmas frame_prior_sigmas_ = GpsCoordPriorSigmas();
+  bool has_calib_ = false, calib_held_ = true;
+  Matrix4d calib_pose_ = Matrix4d::Identity(), calib_prior_ = Matrix4d::Identity();
+  Sigmas calib_prior_sigmas_ = OdomCalibPriorSigmas();
 };
 
 struct IsamOptimizerOptions {
@@ -286,6 +352,9 @@ struct IsamOptimizerOptions {
   int gps_factor_sample_step = 1;
   double gps_factor_init_angle_rad = 1.6;
   bool enable_extrinsic_calib = false;   // true is refused: the tf_error point (GPS_CALIB_KEY) is not restated
+  bool use_odom = false;              // isam_optimizer.h: a HANDEYE factor for every frame with an odometer reading
+  bool odom_extrinsic_calib = false;  // false: the calibration vertex is held at tf_odom_lidar^-1; true: free under the prior of :85-86
+  double odom_huber = 1.0;            // the Huber threshold of the odometry factors (:90-91); 0: none
   double loop_closure_huber = 0.0;    // the Huber threshold of every loop edge, and of nothing else.  0: none, the reference's
                                       // IsamOptimizer (:82-83); 1.0: the multi-trajectory optimiser's loop_closure_model_
                                       // (multi_trajectory_optimizer.cc:68-81)
@@ -316,6 +385,7 @@ class IsamOptimizer {
       : loop_detector_(new LoopDetector(l_d_setting)), options_(options), handle_(handle) {
     SMHIP_CHECK(!options.enable_extrinsic_calib, "enable_extrinsic_calib is not restated: the GPS_CALIB_KEY point and the odometry calibration are out of scope");
     SMHIP_CHECK(std::isfinite(options.loop_closure_huber) && options.loop_closure_huber >= 0.0, "loop_closure_huber is finite and not negative");
+    SMHIP_CHECK(std::isfinite(options.odom_huber) && options.odom_huber >= 0.0, "odom_huber is finite and not negative");
   }
   IsamOptimizer(const IsamOptimizer&) = delete;
   IsamOptimizer& operator=(const IsamOptimizer&) = delete;
@@ -323,6 +393,11 @@ class IsamOptimizer {
   void SetReporter(Reporter reporter) { reporter_ = std::move(reporter); }
   // tf_tracking_gps_: only its translation is used (:247-248), the antenna in the tracking frame
   void SetTransformTrackingToGps(const Matrix4d& t) { for (int c = 0; c < 3; ++c) gps_lever_[c] = t(c, 3); }
+  // tf_odom_lidar_ (odom -> lidar): where the calibration vertex starts (its inverse, :153-157), so set it before the first frame;
+  // RunFinalOptimazation writes the estimate back (:361-367)
+  void SetTransformOdomToLidar(const Matrix4d& t) { tf_odom_lidar_ = t; }
+  const Matrix4d& GetTransformOdomToLidar() const { return tf_odom_lidar_; }
+  int OdomFactorCount() const { return graph_.HandEyeFactorCount(); }
 
   // :196-293.  `frame`: the submap as the detector sees it; `transform_from_last`: Submap::TransformFromLast(), the matched
   // transform from the previous submap (ignored for the first).  Every frame's global_pose is written back, which is what the
@@ -339,7 +414,16 @@ class IsamOptimizer {
     SMHIP_CHECK(frame_index == result.current_frame_index, "CHECK_EQ(frame_index, result.current_frame_index)");   // :202
     frames_.push_back(frame);
     graph_.AddVertex(frame_index, frame->global_pose, transform_from_last, FrameMatchSigmas());  // :206-207
+    if (frame_index == 0 && options_.use_odom) {                                                // :153-162
+      const Matrix4d calib = RigidInverse(tf_odom_lidar_);
+      if (options_.odom_extrinsic_calib) graph_.SetCalibVertex(calib, OdomCalibPriorSigmas());
+      else graph_.SetCalibVertex(calib);
+    }
     bool ok = Update();                                                                         // IsamUpdate of :172
+    if (options_.use_odom && frame->has_odom) {                                                 // :209-224
+      graph_.AddHandEyeFactor(frame_index, frame->odom, OdomSigmas(), options_.odom_huber);
+      ok = Update() && ok;
+    }
     if (result.close_succeed) {                                                                 // :227-236
       for (const LoopEdge& edge : result.edges) {
         loop_edge_at_.push_back(static_cast<int>(graph_.Edges().size()));
@@ -387,9 +471,10 @@ class IsamOptimizer {
   int GpsFactorCount() const { return graph_.PointFactorCount(); }
   int CachedEnuCount() const { return static_cast<int>(cached_enu_.size()); }
   const smhip_pose_graph_stats& AloneStats() const { return alone_stats_; }
-  bool RunFinalOptimazation() {                                                                 // :351-353
+  bool RunFinalOptimazation() {                                                                 // :351-353, 361-367
     const bool ok = Update();
     if (ok) UpdateAllPose();
+    if (ok && options_.use_odom && graph_.HasCalibVertex()) tf_odom_lidar_ = RigidInverse(graph_.CalibVertexPose());
     return ok;
   }
   std::vector<GraphItem> GetWholeGraph() const {                                                // :385-387
@@ -489,6 +574,7 @@ class IsamOptimizer {
   bool calculated_first_gps_coord_ = false;
   Matrix4d gps_coord_transform_ = Matrix4d::Identity();
   double gps_lever_[3] = {0.0, 0.0, 0.0};
+  Matrix4d tf_odom_lidar_ = Matrix4d::Identity();
 };
 
 }  // namespace back_end

@@ -218,6 +218,11 @@ SIGNATURES = {
                                                         ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_double_p, c_double_p, c_double_p,
                                                         ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
     "smhip_pose_graph_last_robust": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    "smhip_pose_graph_plan_calib": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
+                                                   c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, ctypes.c_char_p, ctypes.c_int]),
+    "smhip_pose_graph_optimize_calib": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_double_p, c_double_p, c_double_p,
+                                                       ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

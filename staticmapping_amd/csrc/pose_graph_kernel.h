@@ -8,8 +8,9 @@
 // bits in every thread, so all threads take the same branches and meet at the same barriers.  Every loop has a bound from the
 // sizes or the options; nothing waits on memory.
 //
-// Poses and measurements are 12 doubles here: the rotation row-major, then the translation.  A factor is a BETWEEN, a PRIOR or a
-// POINT (include/smhip.h, "Factor kinds"; tests/pose_graph_gps_ref.py); whatever its kind it has an index pair, 12 doubles of
+// Poses and measurements are 12 doubles here: the rotation row-major, then the translation.  A factor is a BETWEEN, a PRIOR, a
+// POINT (include/smhip.h, "Factor kinds"; tests/pose_graph_gps_ref.py) or a HANDEYE ("Odometry calibration factor";
+// tests/pose_graph_calib_ref.py); whatever its kind it has an index pair, 12 doubles of
 // data, 6 inverse sigmas and 6 rows of whitened A, B and residual, so only edge_cost and linearize_edge look at the kind.
 // Any factor may carry a Huber threshold (include/smhip.h, "Robust factors"; tests/pose_graph_robust_ref.py): the same two
 // functions turn s_f^2 into the cost term and the rows into the weighted rows, and nothing else of the loop knows.
@@ -48,7 +49,7 @@ struct Dev {
   // per edge
   const int32_t* ij = nullptr;            // 2
   const int32_t* kind = nullptr;          // SMHIP_POSE_GRAPH_FACTOR_*; nullptr: every factor is a BETWEEN
-  const double* Z = nullptr;              // 12: BETWEEN the measurement, PRIOR the pose P, POINT the lever (0..2) and the point (3..5)
+  const double* Z = nullptr;              // 12: BETWEEN the measurement, PRIOR the pose P, POINT the lever (0..2) and the point (3..5), HANDEYE the odometer's pose
   const double* sinv = nullptr;           // 6: 1 / sigma (POINT reads the first three)
   double *A = nullptr, *B = nullptr;      // 36, row-major, whitened
   double *rw = nullptr, *u = nullptr;     // 6: whitened residual; A p_i + B p_j
@@ -142,6 +143,26 @@ PG_HD void point_error(const double* Xi, const double* Xj, const double* lz, dou
   for (int a = 0; a < 3; ++a) r[a] = Xi[3 * a] * p[0] + Xi[3 * a + 1] * p[1] + Xi[3 * a + 2] * p[2] + Xi[9 + a] - lz[3 + a];
 }
 
+// HANDEYE: h = T^-1 X T and E = Z^-1 h for the frame node's pose X and the calibration node's pose T; e = [Log(R_E); t_E], with
+// R_h, t_h and R_E handed back
+PG_HD void handeye_error(const double* X, const double* T, const double* Z, double* e, double* Rh, double* th, double* RE) {
+  double M[9], u[3];                                                               // R_X R_T;  R_X t_T + t_X - t_T
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) M[3 * a + b] = X[3 * a] * T[b] + X[3 * a + 1] * T[3 + b] + X[3 * a + 2] * T[6 + b];
+    u[a] = X[3 * a] * T[9] + X[3 * a + 1] * T[10] + X[3 * a + 2] * T[11] + X[9 + a] - T[9 + a];
+  }
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) Rh[3 * a + b] = T[a] * M[b] + T[3 + a] * M[3 + b] + T[6 + a] * M[6 + b];
+    th[a] = T[a] * u[0] + T[3 + a] * u[1] + T[6 + a] * u[2];
+  }
+  const double dz[3] = {th[0] - Z[9], th[1] - Z[10], th[2] - Z[11]};
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) RE[3 * a + b] = Z[a] * Rh[b] + Z[3 + a] * Rh[3 + b] + Z[6 + a] * Rh[6 + b];
+    e[3 + a] = Z[a] * dz[0] + Z[3 + a] * dz[1] + Z[6 + a] * dz[2];
+  }
+  log_so3(RE, e);
+}
+
 // A PRIOR on node i around P is the BETWEEN from a constant node at P measured as the identity: the same residual, and that
 // factor's B is the PRIOR's only Jacobian.
 PG_HD double edge_norm2(const Dev& d, const double* X, int e) {
@@ -155,6 +176,12 @@ PG_HD double edge_norm2(const Dev& d, const double* X, int e) {
     double r[3], p[3];
     point_error(Xi, Xj, Z, r, p);
     for (int a = 0; a < 3; ++a) { const double w = r[a] * sinv[a]; s += w * w; }
+    return s;
+  }
+  if (kind == SMHIP_POSE_GRAPH_FACTOR_HANDEYE) {
+    double err[6], Rh[9], th[3], RE[9];
+    handeye_error(Xi, Xj, Z, err, Rh, th, RE);
+    for (int a = 0; a < 6; ++a) { const double w = err[a] * sinv[a]; s += w * w; }
     return s;
   }
   const double eye[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
@@ -211,6 +238,35 @@ PG_HD void linearize_edge_plain(const Dev& d, const double* X, int e) {
       d.rw[6 * (size_t)e + 3 + a] = 0.0;
     }
     for (int k = 18; k < 36; ++k) { A[k] = 0.0; B[k] = 0.0; }
+    return;
+  }
+  if (kind == SMHIP_POSE_GRAPH_FACTOR_HANDEYE) {
+    // A = B_h Ad(T^-1), B = B_h (I - Ad(h^-1)) with B_h = [Jr^-1, 0; 0, R_E], Ad(G) = [R_G, 0; hat(t_G) R_G, R_G], written out block
+    // by block and row by row into memory: Ad(T^-1) = [R_T^T, 0; -R_T^T hat(t_T), R_T^T], Ad(h^-1) = [R_h^T, 0; -R_h^T hat(t_h), R_h^T],
+    // R_E R_h^T = R_Z^T, and a row p times hat(t) is the cross product p x t.  Both upper right blocks are zero.
+    double err[6], Rh[9], th[3], RE[9], J[9];
+    handeye_error(Xi, Xj, Z, err, Rh, th, RE);
+    jr_inv(err, J);
+    const double* tT = Xj + 9;
+    for (int a = 0; a < 3; ++a) {
+      const double w = sinv[a], v = sinv[3 + a];
+      double p[3];                                                                                                       // row a of R_E R_T^T
+      for (int b = 0; b < 3; ++b) p[b] = RE[3 * a] * Xj[3 * b] + RE[3 * a + 1] * Xj[3 * b + 1] + RE[3 * a + 2] * Xj[3 * b + 2];
+      const double q[3] = {Z[a], Z[3 + a], Z[6 + a]};                                                                    // row a of R_Z^T
+      const double pt[3] = {p[1] * tT[2] - p[2] * tT[1], p[2] * tT[0] - p[0] * tT[2], p[0] * tT[1] - p[1] * tT[0]};
+      const double qt[3] = {q[1] * th[2] - q[2] * th[1], q[2] * th[0] - q[0] * th[2], q[0] * th[1] - q[1] * th[0]};
+      for (int b = 0; b < 3; ++b) {
+        A[6 * a + b] = w * (J[3 * a] * Xj[3 * b] + J[3 * a + 1] * Xj[3 * b + 1] + J[3 * a + 2] * Xj[3 * b + 2]);         // Jr^-1 R_T^T
+        A[6 * a + 3 + b] = 0.0;
+        A[6 * (3 + a) + b] = -v * pt[b];                                                                                 // -R_E R_T^T hat(t_T)
+        A[6 * (3 + a) + 3 + b] = v * p[b];
+        B[6 * a + b] = w * (J[3 * a + b] - (J[3 * a] * Rh[3 * b] + J[3 * a + 1] * Rh[3 * b + 1] + J[3 * a + 2] * Rh[3 * b + 2]));   // Jr^-1 (I - R_h^T)
+        B[6 * a + 3 + b] = 0.0;
+        B[6 * (3 + a) + b] = v * qt[b];                                                                                  // R_Z^T hat(t_h)
+        B[6 * (3 + a) + 3 + b] = v * (RE[3 * a + b] - q[b]);                                                             // R_E - R_Z^T
+      }
+    }
+    for (int a = 0; a < 6; ++a) d.rw[6 * (size_t)e + a] = err[a] * sinv[a];
     return;
   }
   const double eye[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};

@@ -20,7 +20,7 @@ constexpr double kOrthonormalTolerance = 1.0e-6;
 struct Plan {
   std::vector<int32_t> csr_offsets;      // n_nodes + 1
   std::vector<int32_t> csr_edges;        // 2 n_edges less the PRIORs: the factors of node k, ascending, at [csr_offsets[k], csr_offsets[k + 1])
-  int non_chain_edges = 0;               // BETWEEN and POINT factors with |i - j| != 1
+  int non_chain_edges = 0;               // BETWEEN, POINT and HANDEYE factors with |i - j| != 1
   int pcg_cap = 0;                       // 12 non_chain_edges + 64
   int levels = 0;                        // of the cyclic reduction: the smallest L with 2^L >= n_nodes
 };
@@ -42,8 +42,10 @@ inline const char* transform_problem(const double* m) {
 // SMHIP_OK and the plan, or the refusal with its reason in *why.  Reads nothing beyond the sizes it has accepted.  kinds: one
 // SMHIP_POSE_GRAPH_FACTOR_* per factor, nullptr = every factor a BETWEEN.  data: 16 doubles per factor -- BETWEEN the measurement and
 // PRIOR the pose, column-major 4x4; POINT the lever arm (0..2) and the measured point (3..5).
-inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
-                                           const double* data, const double* sigmas, Plan* plan, std::string* why) {
+// calib: HANDEYE factors (data: the odometer's pose, column-major 4x4) are accepted too -- the *_calib entries; without it kind 3 is
+// refused in the words it always was.
+inline smhip_status check_and_plan_kinds(bool calib, int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                         const double* data, const double* sigmas, Plan* plan, std::string* why) {
   auto refuse = [&](smhip_status s, const std::string& text) { if (why) *why = "pose graph: " + text; return s; };
   if (!poses || !fixed || (n_factors > 0 && (!ij || !data))) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "null pointer");
   if (n_nodes < 1 || n_factors < 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "at least one node and no negative edge count");
@@ -53,6 +55,7 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
     if (const char* p = transform_problem(poses + 16 * (size_t)k)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "pose " + std::to_string(k) + " " + p);
   std::vector<int32_t> parent((size_t)n_nodes), degree((size_t)n_nodes, 0);
   std::vector<uint8_t> held((size_t)n_nodes, 0), prior((size_t)n_nodes, 0);      // by a BETWEEN or a PRIOR: all six directions; by a PRIOR
+  std::vector<uint8_t> calibrated((size_t)n_nodes, 0);                           // the j of a HANDEYE
   std::iota(parent.begin(), parent.end(), 0);
   auto root = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
   int non_chain = 0;
@@ -61,8 +64,9 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
     const int kind = kinds ? kinds[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN;
     const double* dat = data + 16 * (size_t)e;
     const std::string name = "edge " + std::to_string(e);
-    if (kind != SMHIP_POSE_GRAPH_FACTOR_BETWEEN && kind != SMHIP_POSE_GRAPH_FACTOR_PRIOR && kind != SMHIP_POSE_GRAPH_FACTOR_POINT)
-      return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " has a kind that is none of BETWEEN, PRIOR and POINT");
+    const bool handeye = calib && kind == SMHIP_POSE_GRAPH_FACTOR_HANDEYE;
+    if (kind != SMHIP_POSE_GRAPH_FACTOR_BETWEEN && kind != SMHIP_POSE_GRAPH_FACTOR_PRIOR && kind != SMHIP_POSE_GRAPH_FACTOR_POINT && !handeye)
+      return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + (calib ? " has a kind that is none of BETWEEN, PRIOR, POINT and HANDEYE" : " has a kind that is none of BETWEEN, PRIOR and POINT"));
     if (i < 0 || j < 0 || i >= n_nodes || j >= n_nodes) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " names a node out of range");
     int read = 6;
     if (kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) {
@@ -73,6 +77,9 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
       for (int c = 0; c < 6; ++c)
         if (!std::isfinite(dat[c])) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " has a lever arm or a point that is not finite");
       read = 3;
+    } else if (handeye) {
+      if (i == j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " is a hand-eye factor that joins a node to itself");
+      if (const char* p = transform_problem(dat)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + "'s odometer pose " + p);
     } else {
       if (i == j) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + " joins a node to itself");
       if (const char* p = transform_problem(dat)) return refuse(SMHIP_ERR_INVALID_ARGUMENT, name + "'s measurement " + p);
@@ -89,12 +96,15 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
     if (kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR) { held[i] = 1; prior[i] = 1; continue; }       // listed once, diagonal: never a chain or non-chain edge
     ++degree[j];
     if (kind == SMHIP_POSE_GRAPH_FACTOR_BETWEEN) { held[i] = 1; held[j] = 1; }
+    if (handeye) { held[i] = 1; calibrated[j] = 1; }                             // Ad(T^-1) is invertible: node i's block has full rank; B can vanish
     parent[root(i)] = root(j);
     if (i - j != 1 && j - i != 1) ++non_chain;
   }
   std::vector<uint8_t> anchored((size_t)n_nodes, 0);
   for (int k = 0; k < n_nodes; ++k) {
     if (!fixed[k] && degree[k] == 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "free node " + std::to_string(k) + " has no edge");
+    if (!fixed[k] && calibrated[k] && !prior[k])
+      return refuse(SMHIP_ERR_INVALID_ARGUMENT, "free node " + std::to_string(k) + " is the calibration node of a hand-eye factor and has no prior: the factor's B vanishes at h = I and is rank-deficient for planar motion");
     if (!fixed[k] && !held[k])
       return refuse(SMHIP_ERR_INVALID_ARGUMENT, "free node " + std::to_string(k) + " has point factors only, which leave its block at rank 3");
     if (fixed[k] || prior[k]) anchored[root(k)] = 1;
@@ -118,11 +128,16 @@ inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, con
   return SMHIP_OK;
 }
 
-// check_and_plan_factors, then the Huber thresholds (one per factor, nullptr = none): each finite and not negative
-inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
-                                          const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
+inline smhip_status check_and_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                           const double* data, const double* sigmas, Plan* plan, std::string* why) {
+  return check_and_plan_kinds(false, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, plan, why);
+}
+
+// check_and_plan_kinds, then the Huber thresholds (one per factor, nullptr = none): each finite and not negative
+inline smhip_status check_and_plan_calib(bool calib, int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                         const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
   Plan made;
-  if (const smhip_status s = check_and_plan_factors(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, &made, why)) return s;
+  if (const smhip_status s = check_and_plan_kinds(calib, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, &made, why)) return s;
   for (int e = 0; huber && e < n_factors; ++e)
     if (!std::isfinite(huber[e]) || huber[e] < 0.0) {
       if (why) *why = "pose graph: edge " + std::to_string(e) + " has a Huber threshold that is negative or not finite";
@@ -130,6 +145,11 @@ inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, cons
     }
   if (plan) *plan = made;
   return SMHIP_OK;
+}
+
+inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                          const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
+  return check_and_plan_calib(false, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, plan, why);
 }
 
 inline smhip_status check_and_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,

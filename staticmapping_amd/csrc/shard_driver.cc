@@ -73,6 +73,43 @@ void ReadGpsEnu(Args* a) {
     Die(a->gps_enu + " holds " + std::to_string(a->enu.size()) + " lines for " + std::to_string(scans) + " scans in " + a->scans_dir);
 }
 
+// --odom FILE into a->odom, before any device work: a line per scan of the listing with 12 numbers each, or the run ends here.  A line
+// with a nan is "no reading"; the others are taken relative to the first of them.
+void ReadOdom(Args* a) {
+  const size_t scans = ListScans(a->scans_dir).size();
+  std::ifstream in(a->odom_file);
+  if (!in) Die("cannot read " + a->odom_file);
+  std::string text;
+  bool have_first = false;
+  double fR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, ft[3] = {0, 0, 0};       // the first reading: rotation row-major, translation
+  while (std::getline(in, text)) {
+    if (text.find_first_not_of(" \t\r") == std::string::npos) continue;
+    double m[12];
+    const char* p = text.c_str();
+    bool finite = true;
+    for (int c = 0; c < 12; ++c) {
+      char* end = nullptr;
+      m[c] = std::strtod(p, &end);
+      if (end == p) Die(a->odom_file + ": line " + std::to_string(a->odom.size() + 1) + " does not hold 12 numbers");
+      finite = finite && std::isfinite(m[c]);
+      p = end;
+    }
+    if (std::string(p).find_first_not_of(" \t\r") != std::string::npos) Die(a->odom_file + ": line " + std::to_string(a->odom.size() + 1) + " does not hold 12 numbers");
+    std::array<double, 16> z{};                     // ([15] = 0: no reading)
+    if (finite) {
+      if (!have_first) { for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) fR[3 * r + c] = m[4 * r + c]; ft[r] = m[4 * r + 3]; } have_first = true; }
+      for (int r = 0; r < 3; ++r) {                 // first^-1 * reading, column-major
+        for (int c = 0; c < 3; ++c) z[4 * c + r] = fR[r] * m[c] + fR[3 + r] * m[4 + c] + fR[6 + r] * m[8 + c];
+        z[12 + r] = fR[r] * (m[3] - ft[0]) + fR[3 + r] * (m[7] - ft[1]) + fR[6 + r] * (m[11] - ft[2]);
+      }
+      z[15] = 1.0;
+    }
+    a->odom.push_back(z);
+  }
+  if (a->odom.size() != scans)
+    Die(a->odom_file + " holds " + std::to_string(a->odom.size()) + " lines for " + std::to_string(scans) + " scans in " + a->scans_dir);
+}
+
 Args Parse(int argc, char** argv) {
   Args a;
   for (int i = 1; i < argc; ++i) {
@@ -141,6 +178,22 @@ Args Parse(int argc, char** argv) {
     else if (k == "--gps-sample-step") a.gps_sample_step = std::atoi(val().c_str());
     else if (k == "--gps-init-angle") a.gps_init_angle = std::atof(val().c_str());
     else if (k == "--gps-output-enu") a.gps_output_enu = true;
+    else if (k == "--odom") a.odom_file = val();
+    else if (k == "--odom-tf") {
+      const std::string text = val();
+      char tail = '\0';
+      if (std::sscanf(text.c_str(), "%lf,%lf,%lf,%lf,%lf,%lf%c", &a.odom_tf[0], &a.odom_tf[1], &a.odom_tf[2], &a.odom_tf[3], &a.odom_tf[4], &a.odom_tf[5], &tail) != 6)
+        a.odom_tf[0] = std::nan("");                                                     // (refused below)
+      a.odom_tf_given = true;
+    }
+    else if (k == "--odom-calib") a.odom_calib = true;
+    else if (k == "--odom-huber") {
+      const std::string text = val();
+      char* end = nullptr;
+      a.odom_huber = std::strtod(text.c_str(), &end);
+      if (text.empty() || *end != '\0') a.odom_huber = std::nan("");                  // (refused below)
+      a.odom_huber_given = true;
+    }
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
              "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
@@ -154,7 +207,9 @@ Args Parse(int argc, char** argv) {
              "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75] "
              "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)]\n"
              "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
-             "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]");
+             "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]\n"
+             "  odometry (with --close-loops): [--odom odom.txt (a line per scan: 12 numbers, the odometer's pose as a row-major 3x4, nan = no reading)] "
+             "[--odom-tf 0,0,0,0,0,0 (odom -> lidar: tx,ty,tz,rx,ry,rz)] [--odom-calib (estimate it)] [--odom-huber 1]");
   }
   if (a.scans_dir.empty()) Die("--scans DIR is required");
   if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
@@ -172,6 +227,10 @@ Args Parse(int argc, char** argv) {
   if (a.loop_huber_given && a.close_loops.empty()) Die("--loop-huber needs --close-loops");
   if (!a.loop_report.empty() && a.close_loops.empty()) Die("--loop-report needs --close-loops");
   if (a.gps_output_enu && a.gps_enu.empty()) Die("--gps-output-enu needs --gps-enu");
+  if (!a.odom_file.empty() && a.close_loops.empty()) Die("--odom needs --close-loops");
+  if ((a.odom_tf_given || a.odom_calib || a.odom_huber_given) && a.odom_file.empty()) Die("--odom-tf, --odom-calib and --odom-huber need --odom");
+  for (int c = 0; c < 6; ++c) if (!std::isfinite(a.odom_tf[c])) Die("bad odometry setting (--odom-tf takes tx,ty,tz,rx,ry,rz, all finite)");
+  if (!std::isfinite(a.odom_huber) || a.odom_huber < 0.0) Die("bad odometry setting (--odom-huber finite and >= 0)");
   if (!std::isfinite(a.gps_lever[0]) || !std::isfinite(a.gps_lever[1]) || !std::isfinite(a.gps_lever[2]) || !std::isfinite(a.gps_init_angle) || a.gps_init_num < 0)
     Die("bad GPS setting (--gps-lever finite, --gps-init-angle finite, --gps-init-num >= 0)");
   if (a.loop.nearest_history_pos_num < 1 || a.loop.loop_ignore_threshold < 0 || a.loop.trying_detect_loop_count < 1)
@@ -516,6 +575,7 @@ int main(int argc, char** argv) {
   setenv("GPU_MAX_HW_QUEUES", "8", 0);
   Args a = Parse(argc, argv);
   if (!a.gps_enu.empty()) ReadGpsEnu(&a);
+  if (!a.odom_file.empty()) ReadOdom(&a);
   if (a.id_file.empty()) a.id_file = "/tmp/smhip_shard_id_" + std::to_string(a.rank >= 0 ? static_cast<long>(getppid()) : static_cast<long>(getpid()));
   if (!a.map_poses.empty()) return RunMapOnly(a);                       // the map alone: one process, no RCCL
   if (a.rank >= 0) {                                                     // one rank of a launched group

@@ -67,6 +67,14 @@ struct Args {
   int gps_init_num = 25, gps_sample_step = 1;
   double gps_init_angle = 1.6;
   bool gps_output_enu = false;
+  // --odom FILE: one line per scan in file order, 12 numbers: the odometer's pose as a row-major 3 x 4, any nan = no reading; the
+  // readings are taken relative to the first finite line (data_collector.cc:179-184).  --odom-tf tx,ty,tz,rx,ry,rz: the initial
+  // odom -> lidar transform (common::Vector6ToTransform: R = Rz Ry Rx); --odom-calib: estimate it; --odom-huber K: the factors' threshold
+  std::string odom_file;
+  std::vector<std::array<double, 16>> odom;       // column-major 4 x 4, relative to the first reading; [15] = 0 marks "no reading"
+  double odom_tf[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool odom_tf_given = false, odom_calib = false, odom_huber_given = false;
+  double odom_huber = 1.0;
 };
 
 [[noreturn]] inline void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -402,7 +410,16 @@ inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files,
 // line gains "loop_edges_downweighted", the loop edges that end with a weight below 1.  --loop-report FILE writes one line per loop
 // edge after the last solve, in the order added: target source norm weight (%.8g; weight 1 = taken at full weight, also without
 // --loop-huber, where the norm alone shows the strain).  Either without --close-loops, or a K that is negative or not finite, ends
-// the run with exit 2 before any device work.  Returns 0, or 3 when the device refused something (the file is then removed and no report written).
+// the run with exit 2 before any device work.
+// With --odom FILE (one line per scan in file order: 12 numbers, the odometer's pose as a row-major 3 x 4, any nan = no reading, taken
+// relative to the first finite line) a submap carries the reading of its first frame and IsamOptimizer adds the odometry calibration
+// factors of isam_optimizer.cc:209-224 ("Odometry calibration factor"; the model assumes that the first submap
+// stands at the identity, as the pose writer's first pose does): --odom-tf tx,ty,tz,rx,ry,rz is the initial odom -> lidar transform in
+// common::Vector6ToTransform's convention (default: the identity), --odom-calib frees the calibration under the reference's prior,
+// --odom-huber K is the factors' threshold (default 1).  The JSON line gains "odom_factors" and "odom_tf" (the transform after the
+// final solve, row-major).  --odom without --close-loops, a FILE whose line count is not the scan count or with a line that does not
+// hold 12 numbers, a bad --odom-tf or K: exit 2 before any device work.
+// Returns 0, or 3 when the device refused something (the file is then removed and no report written).
 inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
   namespace be = smhip::back_end;
   namespace bld = smhip::builder;
@@ -413,6 +430,7 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     int loop_edges = 0, solves = 0, stop_reason = 0; double final_cost = 0.0, moved_m = 0.0;
     int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
     int downweighted = 0;                                                                             // with --loop-huber
+    int odom_factors = 0; double odom_tf[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // with --odom; row-major
   } res;
   std::vector<smhip::back_end::LoopEdgeWeight> loop_report;
   std::ofstream out(a.close_loops);
@@ -434,7 +452,18 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     io.use_gps = !a.gps_enu.empty();
     io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
     io.loop_closure_huber = a.loop_huber;
+    io.use_odom = !a.odom_file.empty(); io.odom_extrinsic_calib = a.odom_calib; io.odom_huber = a.odom_huber;
     be::IsamOptimizer optimizer(io, settings, h);
+    if (io.use_odom) {   // common::Vector6ToTransform: the translation, then R = Rz(rz) Ry(ry) Rx(rx)
+      const double* v = a.odom_tf;
+      const double cx = std::cos(v[3]), sx = std::sin(v[3]), cy = std::cos(v[4]), sy = std::sin(v[4]), cz = std::cos(v[5]), sz = std::sin(v[5]);
+      Matrix4d tf = Matrix4d::Identity();
+      tf(0, 0) = cz * cy; tf(0, 1) = cz * sy * sx - sz * cx; tf(0, 2) = cz * sy * cx + sz * sx;
+      tf(1, 0) = sz * cy; tf(1, 1) = sz * sy * sx + cz * cx; tf(1, 2) = sz * sy * cx - cz * sx;
+      tf(2, 0) = -sy;     tf(2, 1) = cy * sx;                tf(2, 2) = cy * cx;
+      for (int c = 0; c < 3; ++c) tf(c, 3) = v[c];
+      optimizer.SetTransformOdomToLidar(tf);
+    }
     {
       Matrix4d tracking_to_gps = Matrix4d::Identity();
       for (int c = 0; c < 3; ++c) tracking_to_gps(c, 3) = a.gps_lever[c];
@@ -485,6 +514,10 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
           for (int c = 0; c < 3; ++c) frame->enu[c] = maps.back()->GetRelatedGpsInENU()[c];
         }
       }
+      if (io.use_odom) {  // the reading of the submap's first frame
+        const std::array<double, 16>& z = a.odom[static_cast<size_t>(k) * N];
+        if (z[15] != 0.0) { frame->has_odom = true; std::memcpy(frame->odom.data(), z.data(), sizeof(double) * 16); }
+      }
       frames.push_back(frame);
       if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
     }
@@ -501,6 +534,8 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
       // by the map origin's pose in the GPS frame before UpdateInnerFramePose, and the file is in the ENU frame
       const Matrix4d to_enu = optimizer.GetGpsCoordTransform();
       res.gps_factors = optimizer.GpsFactorCount();
+      res.odom_factors = optimizer.OdomFactorCount();
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) res.odom_tf[4 * r + c] = optimizer.GetTransformOdomToLidar()(r, c);
       for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) res.gps_coord[4 * r + c] = to_enu(r, c);
       for (int k = 0; k < S; ++k) {
         maps[k]->SetGlobalPose(frames[k]->global_pose);
@@ -538,6 +573,10 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   if (!a.gps_enu.empty()) {
     *fields += Fmt(", \"gps_factors\": %d, \"gps_coord\": [", res.gps_factors);
     for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.gps_coord[q], q == 15 ? "]" : ", ");
+  }
+  if (!a.odom_file.empty()) {
+    *fields += Fmt(", \"odom_factors\": %d, \"odom_tf\": [", res.odom_factors);
+    for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.odom_tf[q], q == 15 ? "]" : ", ");
   }
   return 0;
 }

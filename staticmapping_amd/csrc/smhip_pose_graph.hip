@@ -5,8 +5,9 @@
 // conjugate-gradient iteration and every level of the preconditioner's cyclic reduction, with __syncthreads as the only barrier
 // and nothing read back in between (pose_graph_kernel.h holds the loop; it also compiles for a CPU).  The work between two
 // barriers is a few thousand 6x6 block operations at most, so a grid-wide seam would cost more than what it separates.
-//   linearise     one thread per factor: e, the whitened A and B; the only place that knows a factor's kind (BETWEEN, PRIOR, POINT:
-//                 include/smhip.h, "Factor kinds") and, with the cost, its Huber threshold ("Robust factors")
+//   linearise     one thread per factor: e, the whitened A and B; the only place that knows a factor's kind (BETWEEN, PRIOR, POINT,
+//                 HANDEYE: include/smhip.h, "Factor kinds", "Odometry calibration factor") and, with the cost, its Huber threshold
+//                 ("Robust factors")
 //   assemble      one thread per node, its edges in index order (the host's CSR list): Hkk, g, the chain block -- no atomics
 //   factor        block cyclic reduction of M = the block-tridiagonal part of H + lambda blockdiag(H): two barriers per level
 //   pcg           H p matrix-free (per edge, then per node), M^-1 by one sweep up and one down the levels, dot products as
@@ -116,32 +117,11 @@ void pack12(const double* m, double* o) {
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-void smhip_internal_free_pose_graph(smhip_context* h) {
-  delete h->pose_graph;            // (the device arrays are among the handle's allocations)
-  h->pose_graph = nullptr;
-}
-
-void smhip_pose_graph_default_options(smhip_pose_graph_options* o) {
-  if (!o) return;
-  std::memset(o, 0, sizeof(*o));
-  o->max_iterations = 50;
-}
-
-smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
-                                           const double* data, const double* sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
-  return smhip_pose_graph_plan_robust(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, nullptr, csr_offsets, csr_edges, why, why_len);
-}
-
-smhip_status smhip_pose_graph_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
-                                          const double* data, const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why,
-                                          int why_len) {
+smhip_status pg_plan(bool calib, int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij, const double* data,
+                     const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
   pg::Plan plan;
   std::string text;
-  const smhip_status s = pg::check_and_plan_robust(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &plan, &text);
+  const smhip_status s = pg::check_and_plan_calib(calib, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &plan, &text);
   if (why && why_len > 0) { std::strncpy(why, text.c_str(), (size_t)why_len - 1); why[why_len - 1] = '\0'; }
   if (s) return s;
   if (csr_offsets) std::memcpy(csr_offsets, plan.csr_offsets.data(), sizeof(int32_t) * plan.csr_offsets.size());
@@ -149,33 +129,17 @@ smhip_status smhip_pose_graph_plan_robust(int n_nodes, const double* poses, cons
   return SMHIP_OK;
 }
 
-smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
-                                   const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
-  return smhip_pose_graph_plan_factors(n_nodes, poses, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, csr_offsets, csr_edges, why, why_len);
-}
-
-smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const int32_t* edge_ij,
-                                       const double* edge_Z, const double* edge_sigmas, const smhip_pose_graph_options* opts,
-                                       smhip_pose_graph_stats* stats) {
-  return smhip_pose_graph_optimize_factors(h, n_nodes, poses_inout, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, opts, stats);
-}
-
-smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
-                                               const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas,
-                                               const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
-  return smhip_pose_graph_optimize_robust(h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, nullptr, opts, stats);
-}
-
-smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
-                                              const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
-                                              const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+// every optimise entry; calib: HANDEYE factors are accepted (smhip_pose_graph_optimize_calib)
+smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                         const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
+                         const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   smhip_pose_graph_options o;
   smhip_pose_graph_default_options(&o);
   if (opts) o = *opts;
   if (o.max_iterations < 1) { h->err = "pose graph: max_iterations must be at least 1"; return SMHIP_ERR_INVALID_ARGUMENT; }
   pg::Plan plan;
-  if (const smhip_status s = pg::check_and_plan_robust(n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, &plan, &h->err)) return s;
+  if (const smhip_status s = pg::check_and_plan_calib(calib, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, &plan, &h->err)) return s;
   HIPCHK(h, hipSetDevice(h->device));
   if (const smhip_status s = pg_ensure(h)) return s;
   smhip_pose_graph_state* st = h->pose_graph;
@@ -253,6 +217,67 @@ smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, doubl
     m[15] = 1.0;
   }
   return SMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void smhip_internal_free_pose_graph(smhip_context* h) {
+  delete h->pose_graph;            // (the device arrays are among the handle's allocations)
+  h->pose_graph = nullptr;
+}
+
+void smhip_pose_graph_default_options(smhip_pose_graph_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->max_iterations = 50;
+}
+
+smhip_status smhip_pose_graph_plan_factors(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                           const double* data, const double* sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  return smhip_pose_graph_plan_robust(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, nullptr, csr_offsets, csr_edges, why, why_len);
+}
+
+smhip_status smhip_pose_graph_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                          const double* data, const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why,
+                                          int why_len) {
+  return pg_plan(false, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, csr_offsets, csr_edges, why, why_len);
+}
+
+smhip_status smhip_pose_graph_plan_calib(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                         const double* data, const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why,
+                                         int why_len) {
+  return pg_plan(true, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, csr_offsets, csr_edges, why, why_len);
+}
+
+smhip_status smhip_pose_graph_plan(int n_nodes, const double* poses, const uint8_t* fixed, int n_edges, const int32_t* edge_ij, const double* edge_Z,
+                                   const double* edge_sigmas, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  return smhip_pose_graph_plan_factors(n_nodes, poses, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, csr_offsets, csr_edges, why, why_len);
+}
+
+smhip_status smhip_pose_graph_optimize(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const int32_t* edge_ij,
+                                       const double* edge_Z, const double* edge_sigmas, const smhip_pose_graph_options* opts,
+                                       smhip_pose_graph_stats* stats) {
+  return smhip_pose_graph_optimize_factors(h, n_nodes, poses_inout, fixed, n_edges, nullptr, edge_ij, edge_Z, edge_sigmas, opts, stats);
+}
+
+smhip_status smhip_pose_graph_optimize_factors(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                               const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas,
+                                               const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+  return smhip_pose_graph_optimize_robust(h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, nullptr, opts, stats);
+}
+
+smhip_status smhip_pose_graph_optimize_robust(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                              const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
+                                              const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+  return pg_optimize(false, h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, opts, stats);
+}
+
+smhip_status smhip_pose_graph_optimize_calib(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                             const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
+                                             const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+  return pg_optimize(true, h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, opts, stats);
 }
 
 smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, double* residuals, double* A, double* B, double* gradient, const double* v, double* minv_v) {

@@ -1,6 +1,6 @@
 """ctypes view of the device pose-graph optimiser (include/smhip.h, `smhip_pose_graph_*`): what back_end::IsamOptimizer asks of GTSAM
 in the reference (back_end/isam_optimizer.{h,cc}) -- rigid poses, between-factors, fixed nodes, and the PRIOR and POINT factors behind its GPS / ENU factors
-(*_factors below), any of them with a Huber threshold (*_robust) -- as one kernel launch per optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
+(*_factors below), any of them with a Huber threshold (*_robust), and the HANDEYE factor behind its odometry calibration (*_calib) -- as one kernel launch per optimisation.  The definition is DESIGN.md section 6 ("Pose graph").  No compute happens in Python."""
 from __future__ import annotations
 
 import ctypes
@@ -10,7 +10,7 @@ import numpy as np
 from . import _capi
 
 MAX_NODES, MAX_EDGES = 8192, 32768
-BETWEEN, PRIOR, POINT = 0, 1, 2
+BETWEEN, PRIOR, POINT, HANDEYE = 0, 1, 2, 3
 STOP_REASONS = {1: "step", 2: "cost", 3: "max_iterations", 4: "damping", 5: "numeric"}
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -80,7 +80,7 @@ def optimize(matcher, poses, edges, Z, fixed=None, sigmas=None, max_iterations: 
 
 
 def factor_data(kind, *parts):
-    """The 16 doubles of one factor: (BETWEEN, Z [4, 4]), (PRIOR, P [4, 4]) -- column-major -- or (POINT, lever [3], point [3])"""
+    """The 16 doubles of one factor: (BETWEEN, Z [4, 4]), (PRIOR, P [4, 4]), (HANDEYE, Z [4, 4]) -- column-major -- or (POINT, lever [3], point [3])"""
     out = np.zeros(16)
     if kind == POINT:
         out[:3], out[3:6] = parts
@@ -179,6 +179,42 @@ def optimize_robust(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, hu
     matcher._check(lib.smhip_pose_graph_optimize_robust(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
                                                         _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
                                                         _ptr(H, _capi.c_double_p), ctypes.byref(o), ctypes.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
+    stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
+
+
+def plan_calib(poses, kinds, ij, data, fixed=None, sigmas=None, huber=None):
+    """plan_robust() that also accepts HANDEYE factors (include/smhip.h, "Odometry calibration factor"): ij = (frame node, calibration
+    node), data = factor_data(HANDEYE, Z) with Z the odometer's pose.  A free calibration node without a PRIOR raises PoseGraphRefused."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    off = np.zeros(len(P) + 1, np.int32)
+    inc = np.zeros(max(2 * len(E), 1), np.int32)
+    why = ctypes.create_string_buffer(256)
+    s = _capi.load_library().smhip_pose_graph_plan_calib(len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                         _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                         _ptr(H, _capi.c_double_p), off.ctypes.data_as(_capi.c_int32_p),
+                                                         inc.ctypes.data_as(_capi.c_int32_p), why, len(why))
+    if s != 0:
+        raise PoseGraphRefused(s, why.value.decode())
+    return off, inc[:off[-1]]
+
+
+def optimize_calib(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, huber=None, max_iterations: int | None = None):
+    """optimize_robust() that also accepts HANDEYE factors; the arguments of plan_calib().  Returns (poses [N, 4, 4], stats dict); last()
+    and last_robust() serve this call too."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    lib = matcher._lib
+    o = _capi.PoseGraphOptions()
+    lib.smhip_pose_graph_default_options(ctypes.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = max_iterations
+    st = _capi.PoseGraphStats()
+    matcher._check(lib.smhip_pose_graph_optimize_calib(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                       _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                       _ptr(H, _capi.c_double_p), ctypes.byref(o), ctypes.byref(st)))
     stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
     stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
     return np.ascontiguousarray(P.transpose(0, 2, 1)), stats

@@ -7,6 +7,9 @@ direct solve: its whole time (the linearisation there is a Python loop) and the 
 --huber K: the two loop cases through smhip_pose_graph_optimize_robust with the Huber threshold K on every loop edge (DESIGN.md section 6,
 "Robust factors"); --bad-loops M: M wrong loop edges beside the good ones, alternately 3 m ahead and 3 m behind (as many as the overlap has
 room for: one with 3 loop edges, four with 60), with or without --huber.  Without either flag the run is what it was.
+--odom: instead, the drive with 3 loop edges re-based to start at the identity, with an odometry calibration (HANDEYE) factor of threshold
+1 on every submap through smhip_pose_graph_optimize_calib ("Odometry calibration factor"): the calibration node is a
+chord to every submap.  The calibration is held at the truth; with --odom-calib it is free from a start 0.1 rad off.
 One JSON line on stdout (and in --out when given)."""
 import argparse
 import json
@@ -54,6 +57,32 @@ def gps_case(m, a):
     return case
 
 
+def odom_case(m, a):
+    """909 submaps with 3 loop edges and a HANDEYE factor on every submap (tests/pose_graph_calib_cases.py): the calibration node last"""
+    import pose_graph_calib_cases as cases
+    import pose_graph_calib_ref as calib
+    from staticmapping_amd import pose_graph
+    g = cases.ring_odom(N_NODES, 1, a.odom_calib)
+
+    def call():
+        return pose_graph.optimize_calib(m, g["poses"], g["kinds"], g["ij"], g["data"], fixed=g["fixed"], sigmas=g["sigmas"], huber=g["huber"])
+    for _ in range(a.warmup):
+        call()
+    t = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        poses, stats = call()
+        t.append(time.perf_counter() - t0)
+    r0, t0m = cases.calib_errors(g["poses"][g["calib_node"]])
+    r1, t1m = cases.calib_errors(poses[g["calib_node"]])
+    return {"odom_factors": int((g["kinds"] == calib.HANDEYE).sum()), "calibration": "free" if a.odom_calib else "held", "factors": int(len(g["kinds"])),
+            "device_median_ms": round(float(np.median(t)) * 1e3, 4), "device_min_ms": round(float(np.min(t)) * 1e3, 4), "outer_steps": stats["iterations"],
+            "rejected_steps": stats["rejected_steps"], "pcg_iterations": stats["pcg_iterations"], "pcg_longest_solve": stats["pcg_max_iterations"],
+            "pcg_cap": stats["pcg_cap"], "levels": stats["levels"], "stop": stats["stop"], "initial_cost": stats["initial_cost"], "final_cost": stats["final_cost"],
+            "truth_error_before_m": cases.truth_error(g, g["poses"]), "truth_error_after_m": cases.truth_error(g, poses),
+            "calib_rotation_error_rad": [r0, r1], "calib_translation_error_m": [t0m, t1m]}
+
+
 def robust_case(m, a, drive, n_loops, overlap):
     """the loop case `drive` as factors, plus --bad-loops wrong loop edges, solved with the threshold --huber on the loop edges"""
     import pose_graph_robust_cases as cases
@@ -89,6 +118,8 @@ def main():
     ap.add_argument("--gps", action="store_true", help="the 909-submap drive that never closes a loop, with a GPS factor on every submap, instead of the two loop cases")
     ap.add_argument("--huber", type=float, default=0.0, help="the Huber threshold of every loop edge (0: none), through smhip_pose_graph_optimize_robust")
     ap.add_argument("--bad-loops", type=int, default=0, help="wrong loop edges added beside the good ones")
+    ap.add_argument("--odom", action="store_true", help="an odometry calibration factor on every submap of the drive with 3 loop edges, instead of the two loop cases")
+    ap.add_argument("--odom-calib", action="store_true", help="with --odom: the calibration free, from a start 0.1 rad off")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -102,7 +133,9 @@ def main():
     res = {"nodes": N_NODES, "repeats": a.repeats, "warmup": a.warmup, "cases": []}
     if a.gps:
         res["cases"].append(gps_case(m, a))
-    for n_loops in (() if a.gps else (3, 60)):
+    if a.odom:
+        res["cases"].append(odom_case(m, a))
+    for n_loops in (() if a.gps or a.odom else (3, 60)):
         # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
         g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
         if a.huber > 0.0 or a.bad_loops > 0:
