@@ -194,6 +194,21 @@ class PoseExtrapolatorCTRV {
   double linear_[3] = {0, 0, 0}, angular_[3] = {0, 0, 0};
 };
 
+// The guess for the next pair when T is the last pair's result, every scan is the next pair's target (a motion filter of 0) and the
+// scans are equally spaced in time: [R_T, R_T^T t_T], normalised.  It is what PoseExtrapolatorCTRV + ProcessCloud form there: with
+// poses P_k = P_{k-1} T the extrapolated pose is [R_k E(euler(R_T)), t_k + R_{k-1} t_T] (the linear velocity stays in the map
+// frame, :170-177; E(euler(R)) = R below 90 degrees of pitch), and P_k^-1 times that is [R_T, R_k^T R_{k-1} t_T] (:261-262).
+// smhip_shard --guess ctrv starts every pair from it (csrc/shard_driver.cc).
+inline Matrix4d CtrvGuessFromLast(const Matrix4d& T) {
+  Matrix4d g = Matrix4d::Identity();
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) g(i, j) = T(i, j);
+    g(i, 3) = T(0, i) * T(0, 3) + T(1, i) * T(1, 3) + T(2, i) * T(2, 3);
+  }
+  NormalizeRotation(g);
+  return g;
+}
+
 struct MotionFilter {                      // builder/map_builder.h:79-82
   float translation_range = 0.35f;
   float angle_range = 1.5f;                // degrees, sum of |Euler angles|

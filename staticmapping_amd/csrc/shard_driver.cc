@@ -28,6 +28,7 @@
 #include <unistd.h>
 
 #include "shard_passes.h"     // (and the standard headers)
+#include "../../include/smhip/front_end.h"   // CtrvGuessFromLast
 
 namespace {
 
@@ -132,6 +133,7 @@ Args Parse(int argc, char** argv) {
     else if (k == "--warmup") a.warmup = std::atoi(val().c_str());
     else if (k == "--parts") a.parts = std::atoi(val().c_str());
     else if (k == "--guess-tx") a.guess_tx = std::atof(val().c_str());
+    else if (k == "--guess") a.guess = val();
     else if (k == "--quiet") a.quiet = true;
     else if (k == "--map") a.map_path = val();
     else if (k == "--map-poses") a.map_poses = val();
@@ -195,7 +197,7 @@ Args Parse(int argc, char** argv) {
       a.odom_huber_given = true;
     }
     else Die("unknown argument " + k + "\nusage: smhip_shard --scans DIR [--gpus G] [--out kitti_pose.txt] [--batch 256] "
-             "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
+             "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--guess constant|ctrv (ctrv: pair k + 1 starts from pair k's motion; one GPU, one matcher)] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
              "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
              "[--map-max-table-log2 28]\n"
@@ -211,6 +213,7 @@ Args Parse(int argc, char** argv) {
              "  odometry (with --close-loops): [--odom odom.txt (a line per scan: 12 numbers, the odometer's pose as a row-major 3x4, nan = no reading)] "
              "[--odom-tf 0,0,0,0,0,0 (odom -> lidar: tx,ty,tz,rx,ry,rz)] [--odom-calib (estimate it)] [--odom-huber 1]");
   }
+  if (a.guess != "constant" && a.guess != "ctrv") Die("--guess takes constant or ctrv (got " + a.guess + ")");
   if (a.scans_dir.empty()) Die("--scans DIR is required");
   if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
   if (!a.map_package.empty() && (!std::isfinite(a.package.piece_width) || !(a.package.piece_width > 0.0) || !std::isfinite(a.package.border_offset) ||
@@ -239,6 +242,10 @@ Args Parse(int argc, char** argv) {
   if (a.rank < 0 && std::getenv("RANK")) a.rank = std::atoi(std::getenv("RANK"));
   if (a.world < 0 && std::getenv("WORLD_SIZE")) a.world = std::atoi(std::getenv("WORLD_SIZE"));
   if (a.local_rank < 0 && std::getenv("LOCAL_RANK")) a.local_rank = std::atoi(std::getenv("LOCAL_RANK"));
+  // a pair's guess comes from its predecessor's result: round-robin pairs have none on their rank, and a second matcher would run beside it
+  // (after the launcher's variables are read: WORLD_SIZE counts as --world)
+  if (a.guess == "ctrv" && (a.gpus > 1 || a.world > 1)) Die("--guess ctrv runs on one GPU (not with --gpus " + std::to_string(std::max(a.gpus, a.world)) + ")");
+  if (a.guess == "ctrv" && a.matchers >= 2) Die("--guess ctrv runs one matcher (not with --matchers " + std::to_string(a.matchers) + ")");
   return a;
 }
 
@@ -327,6 +334,12 @@ int RunRank(const Args& a, int rank, int world, int device) {
   // --matchers 2: two matchers, each with its own stream, take the batches in turn -- while one runs the alignments of batch k
   // (enqueued, not waited for), the host reads, uploads and prepares the targets of batch k + 1 on the other.
   const int NH = (a.matchers >= 2 && per > B) ? 2 : 1;
+  // --guess ctrv (one rank, one matcher): reading, the batched upload and the forest pass as they are; the pairs of a batch are then
+  // aligned one after the other, each a single-pair Align (the cooperative launch), pair k + 1 from front_end::CtrvGuessFromLast of
+  // pair k's result on the host -- across batches too.  (Parse refuses more than one rank.)
+  const bool ctrv = a.guess == "ctrv";
+  smhip::registrator::Matrix4d ctrv_guess = smhip::registrator::Matrix4d::Identity();
+  ctrv_guess(0, 3) = a.guess_tx;
   hipStream_t streams[2] = {nullptr, nullptr};
   smhip_handle hs[2] = {nullptr, nullptr};
   for (int k = 0; k < NH; ++k) HIPOK(hipStreamCreateWithFlags(&streams[k], hipStreamNonBlocking));
@@ -504,7 +517,16 @@ int RunRank(const Args& a, int rank, int world, int device) {
     }
     scans.ReleaseHeld();            // prepare_targets blocked on the stream: the uploads have left the host buffers
     upload_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - u0).count();
-    if (smhip_icp_enqueue_batch(h, nb, guesses.data()) != SMHIP_OK) Die(std::string("enqueue: ") + smhip_last_error(h));
+    if (ctrv) {
+      for (int k = 0; k < nb; ++k) {
+        smhip::registrator::Matrix4d result = ctrv_guess;                // (a pair without a correspondence keeps its guess)
+        double score = 0.0;
+        const smhip_status st = smhip_icp_align_range(h, k, 1, ctrv_guess.data(), result.data(), &score, nullptr);
+        // a pair that failed as a pair is counted below from its exported row (0 iterations); anything else ends the run
+        if (st != SMHIP_OK && st != SMHIP_ERR_NO_MATCH && st != SMHIP_ERR_INVALID_ARGUMENT) Die(std::string("align pair ") + std::to_string(base + k) + ": " + smhip_last_error(h));
+        ctrv_guess = smhip::front_end::CtrvGuessFromLast(result);
+      }
+    } else if (smhip_icp_enqueue_batch(h, nb, guesses.data()) != SMHIP_OK) Die(std::string("enqueue: ") + smhip_last_error(h));
     if (smhip_icp_export_results_device(h, nb, local_dev + static_cast<size_t>(kPoseDoubles) * base) != SMHIP_OK) Die(smhip_last_error(h));
     mark("alignments enqueued", base);
     if (turn == 0) { first_enq_s = since(t0); first_enq_pairs = nb; }
@@ -547,6 +569,7 @@ int RunRank(const Args& a, int rank, int world, int device) {
                   "\"unfinished_pairs\": %d, \"batch\": %d, \"readers\": %d, \"pinned_read_buffers\": %s, \"warmup_batch_before_the_clock_s\": %.4f, \"steady_state_pairs_per_s_rank0\": %.2f, \"poses_file\": \"%s\"",
                   world, n_pairs, my_pairs, elapsed, n_pairs / elapsed, upload_s, wait_s, set_s, prep_s, score_sum / n_pairs, iter_sum / n_pairs, bad, B, a.readers, pinned ? "true" : "false", warmup_s,
                   last_enq_s > first_enq_s ? (enq_pairs - first_enq_pairs) / (last_enq_s - first_enq_s) : 0.0, a.out_path.c_str());
+      if (ctrv) line += ", \"guess\": \"ctrv\"";
       if (!AnyPass(a)) { std::printf("%s}\n", line.c_str()); line.clear(); }
     }
     if (bad) rc = 3;

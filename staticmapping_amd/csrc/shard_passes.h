@@ -37,6 +37,7 @@ struct Args {
   int gpus = 1, rank = -1, world = -1, local_rank = -1;
   int batch = 256, iterations = 20, early_exit = 0, max_pairs = -1, readers = 8, matchers = 1, warmup = 1, parts = 0;
   double guess_tx = 0.0;
+  std::string guess = "constant";          // --guess constant|ctrv: every pair from the --guess-tx step, or pair k + 1 from pair k's result (one rank, one matcher)
   bool quiet = false;
   // the static map (--map); the MRVM settings are MrvmSettings' (multi_resolution_voxel_map.h:54-65), whose defaults these are
   std::string map_path, map_poses;
