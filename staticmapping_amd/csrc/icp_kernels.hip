@@ -2187,6 +2187,86 @@ __device__ __forceinline__ void block_reduce29(double* acc, double (*s_red)[29],
   __syncthreads();
 }
 
+// The same 27 sums held by PAIRS of lanes (the fused certificate pass: 28 accumulator registers per lane instead of 54).
+// With v = (J[0..5], r) the 27 columns are the products v[a] v[e], a <= e, a < 6.  Lanes 2k and 2k+1 each hold 14 of them and add
+// them for BOTH lanes' points; the partner's seven values arrive by a DPP quad_perm swap (register moves).  Which column a slot
+// holds must not cost an operand select per product, so the odd lane computes the even lane's 14 slots on a ROTATED vector,
+// w[a] = v[(a + 1) % 6], w[6] = r: under the rotation the products fall into orbits of six (three slots cover one: the squares,
+// the J r terms, the index distances 1 and 2) and one of three (index distance 3: two slots, so v[1] v[4] is held by both lanes
+// and taken from the even one).  Six selects per lane for its own vector, six for the one it sends.
+__host__ __device__ constexpr int pair_slot_a(int k) { return (int)((0x10020420420420ull >> (4 * k)) & 15); }   // slot k = w[a] w[e]:
+__host__ __device__ constexpr int pair_slot_e(int k) { return (int)((0x43442531666420ull >> (4 * k)) & 15); }   // (0,0) (2,2) (4,4) (0,r) (2,r) (4,r) (0,1) (2,3) (4,5) (0,2) (2,4) (0,4) (0,3) (1,4)
+// the column of accumulate_terms_p's row that slot k of a lane of parity `odd` holds
+__host__ __device__ constexpr int pair_slot_col(int k, int odd) {
+  const int a = (pair_slot_a(k) + odd) % 6, e6 = pair_slot_e(k);
+  if (e6 == 6) return 21 + a;
+  const int e = (e6 + odd) % 6, lo = a < e ? a : e, hi = a < e ? e : a;
+  return lo * 6 - lo * (lo - 1) / 2 + (hi - lo);
+}
+constexpr int kPairSlots = 14;
+// is column c held by the even lanes?  (v[1] v[4] is held by both parities: the even lanes' sum is the one taken)
+__host__ __device__ constexpr bool pair_col_is_even(int c) {
+  for (int k = 0; k < kPairSlots; ++k) if (pair_slot_col(k, 0) == c) return true;
+  return false;
+}
+constexpr bool pair_slots_cover_each_column_once() {
+  int n[27] = {};
+  for (int k = 0; k < kPairSlots; ++k) {
+    n[pair_slot_col(k, 0)] += 1;
+    if (!pair_col_is_even(pair_slot_col(k, 1))) n[pair_slot_col(k, 1)] += 1;
+  }
+  for (int c = 0; c < 27; ++c) if (n[c] != 1) return false;
+  return true;
+}
+static_assert(pair_slots_cover_each_column_once(), "every column of the row from exactly one slot of one parity (block_reduce_pair_sums)");
+// keep = false: exact zeros, by select (a NaN of this lane's point reaches neither lane's sums).  Called by all 64 lanes.
+__device__ __forceinline__ void accumulate_terms_pair(double px, double py, double pz, const float4 q4, const float4 n4, bool keep, bool odd, double* acc) {
+  const double nx = n4.x, ny = n4.y, nz = n4.z;
+  const auto z = [keep](double x) { return keep ? x : 0.0; };
+  const auto sw = [](double x) {                                          // quad_perm [1, 0, 3, 2]: the partner lane's x (every lane has one: in place)
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0xb1, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0xb1, 0xf, 0xf, false));
+  };
+  // (plain values, no array: a select between two elements of a local array becomes a select of the index)
+  const double j0 = z(py * nz - pz * ny), j1 = z(pz * nx - px * nz), j2 = z(px * ny - py * nx), j3 = z(nx), j4 = z(ny), j5 = z(nz);
+  const double r = z((px - (double)q4.x) * nx + (py - (double)q4.y) * ny + (pz - (double)q4.z) * nz);
+  // this lane's vector in its rotation first, then the partner's in THIS lane's rotation (each lane sends the other parity's): the two
+  // are never both in registers
+  {
+    const double own[7] = {odd ? j1 : j0, odd ? j2 : j1, odd ? j3 : j2, odd ? j4 : j3, odd ? j5 : j4, odd ? j0 : j5, r};
+#pragma unroll
+    for (int k = 0; k < kPairSlots; ++k) acc[k] += own[pair_slot_a(k)] * own[pair_slot_e(k)];
+  }
+  {
+    const double par[7] = {sw(odd ? j0 : j1), sw(odd ? j1 : j2), sw(odd ? j2 : j3), sw(odd ? j3 : j4), sw(odd ? j4 : j5), sw(odd ? j5 : j0), sw(r)};
+#pragma unroll
+    for (int k = 0; k < kPairSlots; ++k) acc[k] += par[pair_slot_a(k)] * par[pair_slot_e(k)];
+  }
+  // the sums are formed HERE: nothing reads them before the next round, and left to itself the compiler moves the additions of a
+  // trip's rounds down to the loop's end, with every round's seven values (and their partners') kept until then -- in scratch
+#pragma unroll
+  for (int k = 0; k < kPairSlots; ++k) asm volatile("" : "+v"(acc[k]));
+}
+// block_reduce29 for the lanes' 14 slots: per slot the even lanes' sum and the odd lanes' (the other parity enters as zeros), slot by
+// slot in the order of the slots, each to its column; column 27 zero, column 28 the waves' kept counts.  s_out[c] = the totals.
+__device__ __forceinline__ void block_reduce_pair_sums(const double* acc, bool odd, int nkept, double (*s_red)[29], double* s_out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kPairSlots; ++k) {
+    const int ce = pair_slot_col(k, 0), co = pair_slot_col(k, 1);
+    const double e = wave_sum_to_last(odd ? 0.0 : acc[k]);
+    if (lane == 63) s_red[wave][ce] = e;
+    if (!pair_col_is_even(co)) {
+      const double o = wave_sum_to_last(odd ? acc[k] : 0.0);
+      if (lane == 63) s_red[wave][co] = o;
+    }
+  }
+  if (lane == 63) { s_red[wave][27] = 0.0; s_red[wave][28] = (double)nkept; }
+  __syncthreads();
+  if (threadIdx.x < 29) s_out[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+  __syncthreads();
+}
+
 // One block (kAccThreads * ITEMS source points) of a pair's ErrorElements / ComputePointToPlane sums with the quantile's bin known:
 // row `blk` of partials, the bin's members as records in the block's four wave segments.
 template <int ITEMS>
@@ -2293,12 +2373,13 @@ __global__ __launch_bounds__(kAccThreads) void accumulate(IcpDev b, int nblk) {
 // whose certificate fails go to the wave's own segment of dlist; the listed search (nn_ball_listed_items) finds their matches
 // and records those inside the band, iteration_sums adds those below it.  nn_validate then checks the prediction against the
 // completed histogram (PairState::spec_ok); a miss costs one plain `accumulate` for that pair.  No atomics with a return value
-// inside the loop (the lists are per-wave segments, counted in SGPRs), so the two-deep load pipeline never drains.
+// inside the loop (the lists are per-wave segments, counted in SGPRs), so the load pipeline (below) never drains.
 // NABO = true, the reference-search form: the traversal certificates of the libnabo walk instead of the distance bounds, the
 // failing queries to the walk's four class lists (once per wave, after the loop), and after the walk nabo_validate +
 // accumulate_listed in the roles of nn_validate and of iteration_sums' listed matches.
 // Exactness: the same matches, the same distances, the same kept set as the separate passes; only the order in which the
-// 29 sums are added differs (1e-16 relative), and it is a fixed order -- the result is reproducible bit for bit.
+// 29 sums are added differs (1e-16 relative; here: by lane pairs, accumulate_terms_pair), and it is a fixed order -- the result is
+// reproducible bit for bit.
 // number of set bits of `mask` below this lane (v_mbcnt_lo / _hi: two instructions, no lane mask to build and AND)
 __device__ __forceinline__ uint32_t rank_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -2320,7 +2401,7 @@ __device__ __forceinline__ void emit_record(const IcpDev& b, size_t segbase, int
 // (launches whose targets all have fewer than 32 767 points).  The shadow's bound is never larger than the recorded one, so a few
 // more certificates fail and are searched -- the matches, distances and kept set are the same.
 template <int ITEMS, bool NABO = false, bool SHADOW = false>
-__global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDev b, int nblk) {   // (NABO: 129 registers without the hint, one wave per SIMD less)
+__global__ __launch_bounds__(kNnThreads, 4) void nn_certify_acc(IcpDev b, int nblk) {   // (128 registers, no scratch in all three forms: 4 waves per SIMD)
   int pair, blk;
   if (!xcd_block(nblk, b.npairs, b.pair_base, pair, blk)) return;
   PairState* st = &b.state[pair];
@@ -2366,54 +2447,63 @@ __global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDe
   char* __restrict__ dsegb = reinterpret_cast<char*>(b.dlist + (size_t)pair * b.dl_stride + (size_t)seg * (64 * ITEMS));
   int nrec = 0, ndef = 0, nkept = 0;
   uint32_t nabo_failed = 0;
-  double acc[29];
+  // the 27 sums in 14 slots per lane, shared by lanes 2k and 2k+1 (accumulate_terms_pair)
+  const bool odd = (lane & 1) != 0;
+  double acc[kPairSlots];
 #pragma unroll
-  for (int c = 0; c < 29; ++c) acc[c] = 0.0;
-  // two-deep software pipeline: a round's streamed values (point, bound, previous match id) are loaded two rounds ahead, the
-  // gathers of the previous match and its normal one round ahead (for every lane: seven in ten use both)
-  int ic = min(base + (int)threadIdx.x, ns - 1);
-  float4 s_1 = ld_s(ic);
-  float l_1, l_2;
-  int j_1, j_2;
-  uint32_t m_2 = 0;                                  // SHADOW: a round's packed (bound, match), unpacked when it becomes round 1
-  if (SHADOW) { const uint32_t m = ld_m(ic); l_1 = shadow_bound(m); j_1 = shadow_match(m); }
-  else { l_1 = ld_l(ic); j_1 = ld_j(ic); }
-  ic = min(base + kNnThreads + (int)threadIdx.x, ns - 1);
-  float4 s_2 = ld_s(ic);
-  if (SHADOW) { m_2 = ld_m(ic); l_2 = 0.f; j_2 = 0; }
-  else { l_2 = ld_l(ic); j_2 = ld_j(ic); }
-  float4 t_1 = ld_t(tqb, j_1);
-  float4 n_1 = ld_t(tnb, j_1);
-  // One round of 256 points.  GATHER / STREAM: whether the round still issues the gathers of the next round and the stream loads of
-  // the round after it -- compile-time flags (the last two rounds are written out after the loop), so that inside the loop the
+  for (int c = 0; c < kPairSlots; ++c) acc[c] = 0.0;
+  // The load pipeline.  Round r issues, in this order: the gather of round r+1's normal (what a round needs last), the gather of round
+  // r+2's matched point, round r+2's source row, and round r+4's bound and previous match id (SHADOW: their packed word).  The gathers'
+  // addresses come from the match ids, so the id a gather uses has to be an OLD load: with the ids two rounds ahead and both gathers one
+  // (the earlier form) the id was the last load issued a round before, and a round began by waiting for every load in flight.  Now a
+  // round begins by waiting for the loads of the round before last; the four of the last round stay in flight.
+  // The pipeline's registers are rings of four, indexed by the round's phase at compile time -- four rounds per trip of the loop -- so
+  // that nothing is copied from a register a load is still writing.
+  float4 s_r[4], t_r[4], n_r[2];
+  float l_r[4];
+  int j_r[4];
+  uint32_t m_r[4];
+  auto ld_w = [&](int slot, int k) {                 // a round's bound + match id into ring slot `slot`
+    if (SHADOW) m_r[slot] = ld_m(k);
+    else { l_r[slot] = ld_l(k); j_r[slot] = ld_j(k); }
+  };
+  auto id_of = [&](int slot) { return SHADOW ? shadow_match(m_r[slot]) : j_r[slot]; };
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ld_w(k, min(base + k * kNnThreads + (int)threadIdx.x, ns - 1));
+  s_r[0] = ld_s(min(base + (int)threadIdx.x, ns - 1));
+  s_r[1] = ld_s(min(base + kNnThreads + (int)threadIdx.x, ns - 1));
+  t_r[0] = ld_t(tqb, id_of(0));
+  n_r[0] = ld_t(tnb, id_of(0));
+  t_r[1] = ld_t(tqb, id_of(1));
+  // One round of 256 points, round r0 + PH (PH = its phase, r0 a multiple of 4).  NORMAL / POINT / WORD: whether the round still issues
+  // the loads named above -- compile-time flags (the last four rounds are written out after the loop), so that inside the loop the
   // pipeline registers are plainly overwritten: as run-time conditions every guarded load kept its old value alive and cost a
   // register copy per round.
-  auto round = [&](const int it, auto GATHER, auto STREAM) {
-    const int i = base + it * kNnThreads + threadIdx.x;
+  // i0: this lane's point of round r0, the ONE induction variable of the loop (kept opaque there: left to itself the compiler carries
+  // one per address expression and round of the trip, in registers the pipeline needs)
+  auto round = [&](const int i0, const int r0, auto PH, auto NORMAL, auto POINT, auto WORD) {
+    constexpr int ph = decltype(PH)::value;
+    const int it = r0 + ph;
+    const int i = i0 + ph * kNnThreads;
     bool hard = false, fail = false, band = false;
-    const float4 s = s_1;
-    const float l = l_1;
-    const int j = j_1;
-    const float4 t = t_1, n = n_1;
-    s_1 = s_2;
-    if (SHADOW) { l_1 = shadow_bound(m_2); j_1 = shadow_match(m_2); }
-    else { l_1 = l_2; j_1 = j_2; }
+    const float l = SHADOW ? shadow_bound(m_r[ph]) : l_r[ph];
+    const int j = id_of(ph);
     // (the normals are gathered in the one iteration without a prediction too: a branch around the load costs its register copies
     // in every other)
-    if (GATHER.value) { t_1 = ld_t(tqb, j_1); n_1 = ld_t(tnb, j_1); }
-    if (STREAM.value) {
-      ic = min(i + 2 * kNnThreads, ns - 1);
-      s_2 = ld_s(ic);
-      if (SHADOW) m_2 = ld_m(ic);
-      else { l_2 = ld_l(ic); j_2 = ld_j(ic); }
+    if (NORMAL.value) n_r[(ph + 1) & 1] = ld_t(tnb, id_of((ph + 1) & 3));
+    if (POINT.value) {
+      t_r[(ph + 2) & 3] = ld_t(tqb, id_of((ph + 2) & 3));
+      s_r[(ph + 2) & 3] = ld_s(min(i + 2 * kNnThreads, ns - 1));
     }
+    if (WORD.value) ld_w(ph, min(i + 4 * kNnThreads, ns - 1));
+    const float4 s = s_r[ph], t = t_r[ph], n = n_r[ph & 1];
     float d1 = 0.f;
     unsigned long long m_fail = 0, m_band = 0, m_hard = 0;    // the wave's ballots of fail / band / hard
     if (NABO) {
       bool keep = false;
+      double px, py, pz;
+      transform_point(Mc, s, px, py, pz);
       if (i < ns) {
-        double px, py, pz;
-        transform_point(Mc, s, px, py, pz);
         const float qx = (float)px, qy = (float)py, qz = (float)pz;
         fail = true;
         // the traversal certificate of the libnabo walk (nn_certify<., true>, with its expression and its |s|): the query keeps
@@ -2426,11 +2516,12 @@ __global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDe
           const int bin = (int)(__float_as_uint(d1) >> kHistShift);
           atomicAdd(&s_hist[bin], 1u);
           fail = false;
-          if (bin < band_lo) { accumulate_terms_p<false>(px, py, pz, t, n, acc); keep = true; }
-          else band = bin <= band_hi;
+          keep = bin < band_lo;
+          band = !keep && bin <= band_hi;
         }
       }
-      nkept += (int)__popcll(__ballot(keep));        // (counted where the whole wave is: an update inside the branches would be per lane)
+      accumulate_terms_pair(px, py, pz, t, n, keep, odd, acc);     // (where the whole wave is: the lanes of a pair exchange their terms)
+      nkept += (int)__popcll(__ballot(keep));        // (counted there too: an update inside the branches would be per lane)
     } else {
       // Every predicate of the round as a WAVE MASK: the ballots of the single compares (a compare's own scalar result) combined
       // by scalar ANDs, over values all lanes have (the loads are clamped to the pair's last point); a lane's own predicate is
@@ -2464,7 +2555,7 @@ __global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDe
         st_d(i, d1);
         atomicAdd(&s_hist[bin], 1u);
       }
-      if (P(m_keep)) accumulate_terms_p<false>(px, py, pz, t, n, acc);
+      accumulate_terms_pair(px, py, pz, t, n, P(m_keep), odd, acc);
       if (hard) {
         const float lb2 = Lp * Lp;
         st_d(i, lb2);
@@ -2485,14 +2576,26 @@ __global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDe
       uint32_t basepos = 0;
       if (lane == 0) basepos = atomicAdd(&st->hard_count, (uint32_t)__popcll(hm));
       basepos = (uint32_t)__builtin_amdgcn_readlane((int)basepos, 0);   // lane 0 did the atomic
-      if (hard) b.hlist[so + basepos + __popcll(hm & ((1ull << lane) - 1ull))] = i;
+      if (hard) b.hlist[so + basepos + rank_below(hm)] = i;
     }
   };
-  static_assert(ITEMS >= 2, "the pipeline's last two rounds are written out");
-#pragma unroll 2
-  for (int it = 0; it < ITEMS - 2; ++it) round(it, std::true_type{}, std::true_type{});
-  round(ITEMS - 2, std::true_type{}, std::false_type{});
-  round(ITEMS - 1, std::false_type{}, std::false_type{});
+  static_assert(ITEMS % 4 == 0 && ITEMS >= 8, "four rounds per trip; the pipeline's last four rounds are written out");
+  using Y = std::true_type; using N = std::false_type;
+  using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>; using P2 = std::integral_constant<int, 2>; using P3 = std::integral_constant<int, 3>;
+  int i0 = base + (int)threadIdx.x;
+#pragma unroll 1
+  for (int r0 = 0; r0 < ITEMS - 4; r0 += 4) {
+    asm volatile("" : "+v"(i0));
+    round(i0, r0, P0{}, Y{}, Y{}, Y{});
+    round(i0, r0, P1{}, Y{}, Y{}, Y{});
+    round(i0, r0, P2{}, Y{}, Y{}, Y{});
+    round(i0, r0, P3{}, Y{}, Y{}, Y{});
+    i0 += 4 * kNnThreads;
+  }
+  round(i0, ITEMS - 4, P0{}, Y{}, Y{}, N{});
+  round(i0, ITEMS - 4, P1{}, Y{}, Y{}, N{});
+  round(i0, ITEMS - 4, P2{}, Y{}, N{}, N{});
+  round(i0, ITEMS - 4, P3{}, N{}, N{}, N{});
   if (lane == 0) {
     b.gcount[(size_t)pair * b.seg_stride + seg] = (uint32_t)nrec;
     b.dcount[(size_t)pair * b.seg_stride + seg] = ndef;
@@ -2500,10 +2603,9 @@ __global__ __launch_bounds__(kNnThreads, NABO ? 4 : 1) void nn_certify_acc(IcpDe
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) min_lb = min(min_lb, (uint32_t)__shfl_xor((int)min_lb, off, 64));
   if (lane == 0 && min_lb != 0xffffffffu) atomicMin(&st->min_lb_key, min_lb);
-  if (lane == 0) acc[28] = (double)nkept;           // the wave's kept matches (counted in an SGPR)
-  block_reduce29(acc, s_red, s_out);                // (its barriers also order the histogram updates before the flush)
+  block_reduce_pair_sums(acc, odd, nkept, s_red, s_out);   // nkept: the wave's kept matches, counted in an SGPR  (its barriers also order the histogram updates before the flush)
   if (threadIdx.x < 29) b.partials[((size_t)pair * b.part_stride + blk) * kAccCols + threadIdx.x] = s_out[threadIdx.x];
-  if (NABO) nabo_list_append<ITEMS>(b, st, so, base, ns, nabo_failed, lane);      // (after the sums: their 58 registers are free again)
+  if (NABO) nabo_list_append<ITEMS>(b, st, so, base, ns, nabo_failed, lane);      // (after the sums: their registers are free again)
   uint32_t* gh = b.hist + (size_t)pair * kHistBins;
   for (int k = threadIdx.x; k < kHistBins; k += kNnThreads) {
     const uint32_t v = s_hist[k];
@@ -2983,8 +3085,8 @@ __global__ __launch_bounds__(kAccThreads) void iteration_sums(IcpDev b) {
 // Reference-search mode, fused path: the queries the list walk (nn_nabo<., true>) has just matched again, by the fused pass's
 // rule -- a match below the predicted band is summed, a match inside it becomes a record -- once the histogram is complete and
 // nabo_validate has checked the prediction (the quantile's bin inside the band: this mode's nn_validate; spec_ok also tells
-// `accumulate` to return at once, and finalize which form the iteration's sums have).  kNaboAccBlocks workgroups per pair take
-// equal shares of the four class lists laid end to end; every wave leaves its records in its own segment of region 1 (a wave
+// `accumulate` to return at once, and finalize which form the iteration's sums have).  The waves of kNaboAccBlocks workgroups per pair take
+// equal ranges of the pair's query indices and each the listed queries of its range, in ascending index (below); every wave leaves its records in its own segment of region 1 (a wave
 // meets at most ceil(ns / 32) entries and a segment holds bl_stride / 32), the workgroup its sums in row nblk + blk of partials.
 // (the check of the prediction: one workgroup per pair looks at the completed histogram -- a look costs as much as a small
 // workgroup's whole share of the lists, so the kNaboAccBlocks workgroups of accumulate_listed read its verdict instead)
@@ -3016,10 +3118,19 @@ __global__ __launch_bounds__(kAccThreads) void accumulate_listed(IcpDev b) {
   const int total = cls_first[4];
   constexpr int kWaves = kNaboAccBlocks * (kAccThreads / 64);
   const int lane = threadIdx.x & 63, wave = blk * (kAccThreads / 64) + (int)(threadIdx.x >> 6);
-  const int share = (total + kWaves - 1) / kWaves;
-  const int e0 = wave * share, e1 = min(total, e0 + share);
-  if (blk != 0 && blk * (kAccThreads / 64) * share >= total) {
-    // nothing of the lists falls to this workgroup (the usual case once the pose has settled): empty segments, a zero row --
+  // The lists are filled by atomics (nabo_list_append): which query stands where follows the waves' timing.  The sums must not: a wave
+  // takes the queries of ITS share of the query indices, wherever they stand, in ascending index -- the lists are read once per
+  // workgroup, every query marked in its wave's bitmap in LDS, and a wave walks its set bits in order -- so the additions have one
+  // fixed order, and so have the records.  (Equal shares of the list positions, as before: the last bit of a pose differed from run to
+  // run.)  A wave's share: one of kWaves equal ranges of the indices (shares interleaved in groups of 8 indices, to even out the
+  // clusters failing queries come in, measured 0.3 % slower in the reference-search figure: scattered loads).
+  constexpr int kRange = 4096, kWords = kRange / 32;        // query indices per wave and pass
+  __shared__ uint32_t s_bits[kAccThreads / 64][kWords];
+  __shared__ uint32_t s_pre[kAccThreads / 64][kWords];      // set bits in front of a word
+  static_assert(kAccThreads / 64 == 4, "four bitmaps per workgroup");
+  const int range = (ns + kWaves - 1) / kWaves;             // indices of a wave's share: at most what its record segment holds
+  if (total == 0) {
+    // nothing was walked again (the usual case once the pose has settled): empty segments, a zero row --
     // harmless if the prediction missed
     if (lane == 0) b.gcount[(size_t)pair * b.seg_stride + nseg0 + wave] = 0u;
     if (threadIdx.x < 29) b.partials[((size_t)pair * b.part_stride + nblk0 + blk) * kAccCols + threadIdx.x] = 0.0;
@@ -3043,35 +3154,81 @@ __global__ __launch_bounds__(kAccThreads) void accumulate_listed(IcpDev b) {
     return *nabo_list_slot(b, so, c, (uint32_t)(e - f));
   };
   constexpr int kU = 2;                                     // entries per lane and round: their dependent loads level by level
-  for (int eb = e0; eb < e1; eb += 64 * kU) {               // wave-uniform
-    int i[kU], jm[kU];
-    float d[kU];
-    float4 s4[kU], q4[kU], n4[kU];
-    bool live[kU], below[kU], rec[kU];
+  const int wv = (int)(threadIdx.x >> 6);
+  for (int p0 = 0; p0 < range; p0 += kRange) {              // (uniform over the workgroup: the barriers below)
+    for (int k = threadIdx.x; k < (kAccThreads / 64) * kWords; k += kAccThreads) (&s_bits[0][0])[k] = 0u;
+    __syncthreads();
+    // (the workgroup reads the lists once for its four waves, kS independent loads per thread and trip: the loop is all latency)
+    constexpr int kS = 32;
+    for (int eb = 0; eb < total; eb += kAccThreads * kS) {
+      int iq[kS];
 #pragma unroll
-    for (int u = 0; u < kU; ++u) { live[u] = eb + 64 * u + lane < e1; i[u] = live[u] ? entry(eb + 64 * u + lane) : 0; }
+      for (int s = 0; s < kS; ++s) { const int e = eb + s * kAccThreads + (int)threadIdx.x; iq[s] = e < total ? entry(e) : -1; }
 #pragma unroll
-    for (int u = 0; u < kU; ++u) { d[u] = b.d2[so + i[u]]; jm[u] = b.idx[so + i[u]]; s4[u] = ld_src(b, so + i[u]); }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const uint32_t key = __float_as_uint(d[u]);
-      const int bin = (int)(key >> kHistShift);
-      const bool valid = live[u] && key < 0x7f800000u && jm[u] >= 0;
-      below[u] = valid && bin < band_lo;
-      rec[u] = valid && bin >= band_lo && bin <= band_hi;
-      if (below[u]) { q4[u] = b.tq[to + jm[u]]; n4[u] = b.tn[to + jm[u]]; }
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      if (below[u]) accumulate_terms(Mc, s4[u], q4[u], n4[u], acc);
-      const unsigned long long bm = __ballot(rec[u]);
-      if (rec[u]) {
-        const size_t at = segbase + wcount + __popcll(bm & ((1ull << lane) - 1ull));
-        b.rec_a[at] = make_float4(s4[u].x, s4[u].y, s4[u].z, d[u]);
-        b.rec_j[at] = jm[u];
+      for (int s = 0; s < kS; ++s) {
+        const int rel = iq[s] - blk * (kAccThreads / 64) * range;      // from the first index of this workgroup's four shares
+        if (iq[s] >= 0 && rel >= 0 && rel < (kAccThreads / 64) * range) {
+          int wq = rel >= 2 * range ? 2 : 0;
+          wq += rel - wq * range >= range ? 1 : 0;
+          const int off = rel - wq * range - p0;
+          if (off >= 0 && off < kRange) atomicOr(&s_bits[wq][off >> 5], 1u << (off & 31));
+        }
       }
-      wcount += (int)__popcll(bm);
     }
+    __syncthreads();
+    // set bits in front of every word: lane l counts words 2l and 2l+1, an exclusive scan over the wave
+    static_assert(kWords == 128, "two words per lane");
+    const int ca = __popc(s_bits[wv][2 * lane]), cb = __popc(s_bits[wv][2 * lane + 1]);
+    int incl = ca + cb;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off, 64); if (lane >= off) incl += v; }
+    s_pre[wv][2 * lane] = (uint32_t)(incl - ca - cb);
+    s_pre[wv][2 * lane + 1] = (uint32_t)(incl - cb);
+    const int e1 = __shfl(incl, 63, 64);                    // this wave's queries of this pass
+    __syncthreads();
+    for (int eb = 0; eb < e1; eb += 64 * kU) {               // wave-uniform
+      int i[kU], jm[kU];
+      float d[kU];
+      float4 s4[kU], q4[kU], n4[kU];
+      bool live[kU], below[kU], rec[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int r = eb + 64 * u + lane;
+        live[u] = r < e1;
+        i[u] = 0;
+        if (live[u]) {                                        // the r-th set bit: its word by bisection of the counts, then inside the word
+          int wd = 0;
+#pragma unroll
+          for (int step = kWords / 2; step > 0; step >>= 1) if ((int)s_pre[wv][wd + step] <= r) wd += step;
+          uint32_t w = s_bits[wv][wd];
+          for (int t = r - (int)s_pre[wv][wd]; t > 0; --t) w &= w - 1u;
+          i[u] = wave * range + p0 + wd * 32 + (__ffs(w) - 1);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) { d[u] = b.d2[so + i[u]]; jm[u] = b.idx[so + i[u]]; s4[u] = ld_src(b, so + i[u]); }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const uint32_t key = __float_as_uint(d[u]);
+        const int bin = (int)(key >> kHistShift);
+        const bool valid = live[u] && key < 0x7f800000u && jm[u] >= 0;
+        below[u] = valid && bin < band_lo;
+        rec[u] = valid && bin >= band_lo && bin <= band_hi;
+        if (below[u]) { q4[u] = b.tq[to + jm[u]]; n4[u] = b.tn[to + jm[u]]; }
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        if (below[u]) accumulate_terms(Mc, s4[u], q4[u], n4[u], acc);
+        const unsigned long long bm = __ballot(rec[u]);
+        if (rec[u]) {
+          const size_t at = segbase + wcount + __popcll(bm & ((1ull << lane) - 1ull));
+          b.rec_a[at] = make_float4(s4[u].x, s4[u].y, s4[u].z, d[u]);
+          b.rec_j[at] = jm[u];
+        }
+        wcount += (int)__popcll(bm);
+      }
+    }
+    __syncthreads();                                        // (the next pass clears every wave's bitmap)
   }
   if (lane == 0) b.gcount[(size_t)pair * b.seg_stride + nseg0 + wave] = (uint32_t)wcount;
   block_reduce29(acc, s_red, s_out);
