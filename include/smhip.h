@@ -313,7 +313,22 @@ smhip_status smhip_icp_find_closests(smhip_handle h, int slot, const double T[16
  * Uses slot 0's clouds (upload them with smhip_set_source_f32 / smhip_set_target_f32: the reference's
  * Ndt converts the InnerPointType AoS to pcl::PointXYZ, ndt.cc:44-51; the target needs no normals).
  * Defaults are the wrapper's: resolution 1.0 (ndt.cc:31), KDTREE neighbourhood (ndt.cc:33), step 0.1,
- * outlier ratio 0.55, transformation epsilon 0.1, 35 iterations (pclomp/ndt_omp_impl.hpp:47-76). */
+ * outlier ratio 0.55, transformation epsilon 0.1, 35 iterations (pclomp/ndt_omp_impl.hpp:47-76).
+ *
+ * search_method is pclomp's setNeighborhoodSearchMethod with the enum's own values (pclomp/ndt_omp.h:52-57): which voxels a
+ * transformed point is paired with in computeDerivatives (ndt_omp_impl.hpp:233-247).  KDTREE: the voxels whose centroid lies
+ * within `resolution` of the point.  The direct rules (voxel_grid_covariance_omp_impl.hpp:373-442) start from the cell
+ * floor(x / resolution) -- a float division -- and keep each cell of their stencil that lies inside the target's voxel box, is
+ * occupied and holds min_points_per_voxel points, whatever the distance: DIRECT1 the cell itself, DIRECT7 the cell and its
+ * six face neighbours (pclomp's own default, ndt_omp_impl.hpp:74), DIRECT26 the 26 cells around it WITHOUT the cell itself.
+ * That last stencil is pcl::getAllNeighborCellIndices() of PCL 1.8.1, which the reference does not vendor: like the rest of
+ * the registrator restatements it is unpinned.  The rule applies to smhip_ndt_align, smhip_ndt_align_batch,
+ * smhip_ndt_compute_derivatives[_ex] and smhip_ndt_time_derivatives; the voxel table does not depend on it (a kept table is
+ * reused when only the rule changes), and NdtWithGicp's NDT stage (stock PCL, which has no such switch) never uses it. */
+#define SMHIP_NDT_SEARCH_KDTREE 0
+#define SMHIP_NDT_SEARCH_DIRECT26 1
+#define SMHIP_NDT_SEARCH_DIRECT7 2
+#define SMHIP_NDT_SEARCH_DIRECT1 3
 typedef struct smhip_ndt_options {
   float resolution;
   float step_size;
@@ -322,7 +337,8 @@ typedef struct smhip_ndt_options {
   int32_t max_iterations;
   int32_t min_points_per_voxel;      /* voxel_grid_covariance_omp.h:204 */
   float min_covar_eigvalue_mult;     /* voxel_grid_covariance_omp.h:205 */
-  int32_t reserved[5];
+  int32_t search_method;             /* SMHIP_NDT_SEARCH_*; 0 = KDTREE; anything else is refused by smhip_ndt_set_options */
+  int32_t reserved[4];
 } smhip_ndt_options;
 
 typedef struct smhip_ndt_stats {

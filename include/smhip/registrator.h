@@ -573,8 +573,11 @@ class IcpFastHip : public Interface {
   smhip_icp_stats stats_{};
 };
 
-// GPU replacement of registrator::Ndt (ndt.h / ndt.cc:29-64): pclomp NDT with resolution 1.0 and the
-// KDTREE neighbourhood; score = pcl getFitnessScore() (mean squared 1-NN distance, lower is better).
+// GPU replacement of registrator::Ndt (ndt.h / ndt.cc:29-64): pclomp NDT with resolution 1.0 and, by default, the
+// KDTREE neighbourhood the reference's wrapper picks (ndt.cc:33); score = pcl getFitnessScore() (mean squared 1-NN distance,
+// lower is better).  The inner option "search_method" is pclomp's setNeighborhoodSearchMethod with the enum's values
+// (SMHIP_NDT_SEARCH_KDTREE 0, _DIRECT26 1, _DIRECT7 2 -- pclomp's own default --, _DIRECT1 3; see smhip.h): Align and AlignBatch
+// run under it, LastStats().pairs_last counts its pairs, and a value outside 0..3 fails the next Align's option check.
 class NdtHip : public Interface {
  public:
   explicit NdtHip(int device = 0, int max_source = 1 << 18, int max_target = 1 << 21)
@@ -585,6 +588,7 @@ class NdtHip : public Interface {
     SMHIP_REG_REGISTRATOR_INNER_OPTION("resolution", OptionItemDataType::kFloat32, opt_.resolution);
     SMHIP_REG_REGISTRATOR_INNER_OPTION("step_size", OptionItemDataType::kFloat32, opt_.step_size);
     SMHIP_REG_REGISTRATOR_INNER_OPTION("max_iterations", OptionItemDataType::kInt32, opt_.max_iterations);
+    SMHIP_REG_REGISTRATOR_INNER_OPTION("search_method", OptionItemDataType::kInt32, opt_.search_method);
   }
   void InitWithOptions() override { EnsureHandle(0, 0); }
 

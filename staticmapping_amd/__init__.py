@@ -9,7 +9,7 @@ scan-pair sharding helper built on torch.distributed (RCCL).
 """
 from . import synth  # noqa: F401
 from .matcher import (IcpFastHip, IcpPointMatcherHip, NdtGicpHip, NdtHip, SmhipError, se3_error, calculate_normals,  # noqa: F401
-                      NN_BRUTE, NN_GRID, NN_NABO)
+                      NN_BRUTE, NN_GRID, NN_NABO, NDT_SEARCH_KDTREE, NDT_SEARCH_DIRECT26, NDT_SEARCH_DIRECT7, NDT_SEARCH_DIRECT1)
 from .mrvm import MultiResolutionVoxelMapHip  # noqa: F401
 from .submap import SubmapBuilder, build_submap, output_to_target  # noqa: F401
 from . import m2dp  # noqa: F401

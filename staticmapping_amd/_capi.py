@@ -44,7 +44,11 @@ class NdtOptions(ctypes.Structure):
     _fields_ = [("resolution", ctypes.c_float), ("step_size", ctypes.c_float), ("outlier_ratio", ctypes.c_float),
                 ("transformation_epsilon", ctypes.c_float), ("max_iterations", ctypes.c_int32),
                 ("min_points_per_voxel", ctypes.c_int32), ("min_covar_eigvalue_mult", ctypes.c_float),
-                ("reserved", ctypes.c_int32 * 5)]
+                ("search_method", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+
+
+# smhip_ndt_options.search_method: pclomp's NeighborSearchMethod values (SMHIP_NDT_SEARCH_* in smhip.h)
+NDT_SEARCH_KDTREE, NDT_SEARCH_DIRECT26, NDT_SEARCH_DIRECT7, NDT_SEARCH_DIRECT1 = 0, 1, 2, 3
 
 
 class NdtStats(ctypes.Structure):

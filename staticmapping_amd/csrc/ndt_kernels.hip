@@ -2,7 +2,8 @@
 //
 // Reference lines are in /root/reference/registrators:
 //   ndt_voxel_*      VoxelGridCovariance::applyFilter   pclomp/voxel_grid_covariance_omp_impl.hpp:49-370
-//   ndt_derivatives  computeDerivatives + computePointDerivatives + updateDerivatives
+//   ndt_derivatives  computeDerivatives + computePointDerivatives + updateDerivatives, under each of the four neighbourhoods of
+//                    setNeighborhoodSearchMethod (ndt_omp.h:52-57; voxel_grid_covariance_omp_impl.hpp:373-442 for the direct ones)
 //                                                       pclomp/ndt_omp_impl.hpp:180-284, 397-438, 483-535
 //   ndt_ctl_step     the fold of the partial sums (:272-281) + the Newton / More-Thuente driver
 //                                                       pclomp/ndt_omp_impl.hpp:81-171, 757-916
@@ -509,7 +510,8 @@ __device__ __forceinline__ void ndt_voxel_finish(const NdtDev& d, int v, const d
 // pcl::NormalDistributionsTransform (PCL 1.8.1 ndt.hpp: the same formulas on Vector3d / Matrix3d), which
 // registrators/ndt_gicp.cc:38-41,84-89 uses.
 //
-// Shape of the kernel.  A wave owns 64 source points (four granules of 16 Morton-consecutive points taken a quarter of the cloud
+// Shape of the kernel under the KDTREE neighbourhood, the reference wrapper's (ndt.cc:33); what the direct neighbourhoods change
+// is said at ndt_stencil_has below.  A wave owns 64 source points (four granules of 16 Morton-consecutive points taken a quarter of the cloud
 // apart, so every wave gets the cloud's average neighbour count); its four phases meet no other wave until the final fold.
 //   A  (a lane per POINT): transform, the occupancy words of the nine (z, y) rows around its voxel (a row's three cells lie in
 //      at most two words: 18 loads in flight), one (point, voxel slot) entry per OCCUPIED neighbour voxel appended to the wave's
@@ -606,9 +608,25 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
   return v;
 }
 
+// The neighbourhood rules of pclomp's setNeighborhoodSearchMethod (ndt_omp.h:52-57; the values are the enum's).  KDTREE is the
+// shape described above.  The three direct rules (getNeighborhoodAtPoint*, voxel_grid_covariance_omp_impl.hpp:373-442) take
+// the cell of the transformed point by a float DIVISION, floor(x / leaf) (:379-381 -- the table build multiplies by the
+// inverse, :218-220, and the two disagree at some floats when the leaf is no power of two), and keep every cell of a fixed
+// stencil that lies inside the box, is occupied and has min_points (:392-395): the cell itself (DIRECT1), it and its six face
+// neighbours (DIRECT7), or the 26 around it WITHOUT it (DIRECT26: pcl::getAllNeighborCellIndices() of PCL 1.8.1, which the
+// reference does not vendor).  No centroid, no distance: phase A reads only the occupancy rows the stencil touches (1, 5, 9), a
+// point's entries already follow one another in the list, phase B1 is gone and phase B2 takes the min_points rule from the
+// record's own count (the last word of the 64-byte line it gathers anyway).  DIRECT1 has no list: its one slot stays in a register.
+constexpr int kNdtSearchKdtree = 0, kNdtSearchDirect26 = 1, kNdtSearchDirect7 = 2, kNdtSearchDirect1 = 3;
+template <int NB>
+__device__ __forceinline__ constexpr bool ndt_stencil_has(int dz, int dy, int dx) {
+  const int n1 = (dz < 0 ? -dz : dz) + (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
+  return NB == kNdtSearchDirect26 ? n1 != 0 : NB == kNdtSearchDirect7 ? n1 <= 1 : n1 == 0;
+}
+
 // The granule assignment depends on the slot's own point count only (never on the batch a launch carries), so an evaluation's
 // sums have one order.
-template <typename R, bool HESS>
+template <typename R, bool HESS, int NB = kNdtSearchKdtree>
 __device__ __forceinline__ void ndt_derivatives_body(const NdtDev& d, const NdtPose& P, double* __restrict__ row_out, NdtDerivShared& sh) {
   constexpr bool kDouble = sizeof(R) == 8;
   constexpr int kCap = kNdtPairCap;
@@ -651,7 +669,12 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtDev& d, const NdtP
     const float tz = P.T[8] * s.x + P.T[9] * s.y + P.T[10] * s.z + P.T[11];
     int c0 = 0, c1 = 0, c2 = 0;
     if (live) {
-      c0 = (int)(floorf(tx * inv) - mb0); c1 = (int)(floorf(ty * inv) - mb1); c2 = (int)(floorf(tz * inv) - mb2);
+      if constexpr (NB == kNdtSearchKdtree) {
+        c0 = (int)(floorf(tx * inv) - mb0); c1 = (int)(floorf(ty * inv) - mb1); c2 = (int)(floorf(tz * inv) - mb2);
+      } else {                                             // :379-381: the correctly rounded quotient, not tx * inv
+        const float leaf = g->res;
+        c0 = (int)(floorf(__fdiv_rn(tx, leaf)) - mb0); c1 = (int)(floorf(__fdiv_rn(ty, leaf)) - mb1); c2 = (int)(floorf(__fdiv_rn(tz, leaf)) - mb2);
+      }
       // (far outside the box every row test below fails; keep the row arithmetic inside int range)
       live = !g->status && c0 >= -1 && c0 <= div0 && c1 >= -1 && c1 <= div1 && c2 >= -1 && c2 <= div2;
     }
@@ -664,118 +687,224 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtDev& d, const NdtP
     uint32_t npairs_lane = 0;
     const double tdx = (double)tx, tdy = (double)ty, tdz = (double)tz;
     NDT_STAMP(1);
-    for (uint32_t wbase = 0; wbase == 0 || wbase < total; wbase += kCap) {
-      // the occupancy words of the nine rows (re-read for every further window of a crowded wave: L2 hits)
-      uint2 wa[9], wb[9];
-      uint32_t rowok = 0;
-      int c1w = c1, c2w = c2;
-      asm volatile("" : "+v"(c1w), "+v"(c2w));            // (keeps the 18 row addresses out of registers across phase B)
+    if constexpr (NB == kNdtSearchKdtree) {
+      for (uint32_t wbase = 0; wbase == 0 || wbase < total; wbase += kCap) {
+        // the occupancy words of the nine rows (re-read for every further window of a crowded wave: L2 hits)
+        uint2 wa[9], wb[9];
+        uint32_t rowok = 0;
+        int c1w = c1, c2w = c2;
+        asm volatile("" : "+v"(c1w), "+v"(c2w));            // (keeps the 18 row addresses out of registers across phase B)
 #pragma unroll
-      for (int r = 0; r < 9; ++r) {
-        const int z = c2w + r / 3 - 1, y = c1w + r % 3 - 1;
-        const bool ok = live && z >= 0 && z < div2 && y >= 0 && y < div1;
-        rowok |= ok ? 1u << r : 0u;
-        const int rowbase = ok ? (z * div1 + y) * wx : 0;
-        { const u32x2 v = words[rowbase + (xa >> 5)]; wa[r] = make_uint2(v.x, v.y); }
-        { const u32x2 v = words[rowbase + (xb >> 5)]; wb[r] = make_uint2(v.x, v.y); }
-      }
-      if (wbase == 0) {
-        uint32_t nnb = 0;
+        for (int r = 0; r < 9; ++r) {
+          const int z = c2w + r / 3 - 1, y = c1w + r % 3 - 1;
+          const bool ok = live && z >= 0 && z < div2 && y >= 0 && y < div1;
+          rowok |= ok ? 1u << r : 0u;
+          const int rowbase = ok ? (z * div1 + y) * wx : 0;
+          { const u32x2 v = words[rowbase + (xa >> 5)]; wa[r] = make_uint2(v.x, v.y); }
+          { const u32x2 v = words[rowbase + (xb >> 5)]; wb[r] = make_uint2(v.x, v.y); }
+        }
+        if (wbase == 0) {
+          uint32_t nnb = 0;
+#pragma unroll
+          for (int r = 0; r < 9; ++r)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+              const int x = c0 + dx;
+              const uint2 wd = (x >> 5) == (xa >> 5) ? wa[r] : wb[r];
+              nnb += (((rowok >> r) & 1u) && x >= 0 && x < div0 && ((wd.x >> (x & 31)) & 1u)) ? 1u : 0u;
+            }
+          NDT_STAMP(2);
+          const uint32_t incl = wave_incl_scan_u32(nnb);
+          off = incl - nnb;
+          total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // (the wave's earlier reads of its window are done)
+        uint32_t k = off - wbase;                            // position in this window (wraps below it: the unsigned compare drops those)
 #pragma unroll
         for (int r = 0; r < 9; ++r)
 #pragma unroll
           for (int dx = -1; dx <= 1; ++dx) {
             const int x = c0 + dx;
             const uint2 wd = (x >> 5) == (xa >> 5) ? wa[r] : wb[r];
-            nnb += (((rowok >> r) & 1u) && x >= 0 && x < div0 && ((wd.x >> (x & 31)) & 1u)) ? 1u : 0u;
+            if (((rowok >> r) & 1u) && x >= 0 && x < div0 && ((wd.x >> (x & 31)) & 1u)) {
+              if (k < (uint32_t)kCap) s_pair[k] = ((uint32_t)lane << 24) | (wd.y + __popc(wd.x & ((1u << (x & 31)) - 1u)));
+              ++k;
+            }
           }
-        NDT_STAMP(2);
-        const uint32_t incl = wave_incl_scan_u32(nnb);
-        off = incl - nnb;
-        total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // (the wave's earlier reads of its window are done)
-      uint32_t k = off - wbase;                            // position in this window (wraps below it: the unsigned compare drops those)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // the window is written: LDS is in order inside a wave
+        NDT_STAMP(3);
+        // ---- phase B1: a lane per entry; keep what radiusSearch returns, compacting the window in place and counting per point
+        const uint32_t nwin = min((uint32_t)kCap, total - wbase);
+        uint32_t kept = 0;                                   // wave-uniform
+        for (uint32_t q0 = 0; q0 < nwin; q0 += 256) {
+          uint32_t prs[4];
+          u32x4 cen[4];
 #pragma unroll
-      for (int r = 0; r < 9; ++r)
+          for (int u = 0; u < 4; ++u) {
+            const uint32_t q = q0 + 64 * u + lane;
+            prs[u] = 0; cen[u] = u32x4{0, 0, 0, 0};
+            if (q < nwin) { prs[u] = s_pair[q]; cen[u] = ((gptr<u32x4>)(d.vox + (prs[u] & 0xffffffu)))[3]; }
+          }
 #pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-          const int x = c0 + dx;
-          const uint2 wd = (x >> 5) == (xa >> 5) ? wa[r] : wb[r];
-          if (((rowok >> r) & 1u) && x >= 0 && x < div0 && ((wd.x >> (x & 31)) & 1u)) {
-            if (k < (uint32_t)kCap) s_pair[k] = ((uint32_t)lane << 24) | (wd.y + __popc(wd.x & ((1u << (x & 31)) - 1u)));
-            ++k;
+          for (int u = 0; u < 4; ++u) {
+            const uint32_t q = q0 + 64 * u + lane;
+            const float4 tp = s_t[prs[u] >> 24];
+            const int vn_pts = (int)cen[u].w;
+            const float ex = tp.x - __uint_as_float(cen[u].x), ey = tp.y - __uint_as_float(cen[u].y), ez = tp.z - __uint_as_float(cen[u].z);
+            const bool pass = q < nwin && !(vn_pts >= 0 && vn_pts < d.min_points) && !(ex * ex + ey * ey + ez * ez > P.res2);
+            const unsigned long long mask = __ballot(pass);
+            const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            if (pass) { s_pair[pos] = prs[u]; atomicAdd(&s_cnt[prs[u] >> 24], 1u); }
+            kept += (uint32_t)__popcll(mask);
           }
         }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // the window is written: LDS is in order inside a wave
-      NDT_STAMP(3);
-      // ---- phase B1: a lane per entry; keep what radiusSearch returns, compacting the window in place and counting per point
-      const uint32_t nwin = min((uint32_t)kCap, total - wbase);
-      uint32_t kept = 0;                                   // wave-uniform
-      for (uint32_t q0 = 0; q0 < nwin; q0 += 256) {
-        uint32_t prs[4];
-        u32x4 cen[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const uint32_t q = q0 + 64 * u + lane;
-          prs[u] = 0; cen[u] = u32x4{0, 0, 0, 0};
-          if (q < nwin) { prs[u] = s_pair[q]; cen[u] = ((gptr<u32x4>)(d.vox + (prs[u] & 0xffffffu)))[3]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const uint32_t q = q0 + 64 * u + lane;
-          const float4 tp = s_t[prs[u] >> 24];
-          const int vn_pts = (int)cen[u].w;
-          const float ex = tp.x - __uint_as_float(cen[u].x), ey = tp.y - __uint_as_float(cen[u].y), ez = tp.z - __uint_as_float(cen[u].z);
-          const bool pass = q < nwin && !(vn_pts >= 0 && vn_pts < d.min_points) && !(ex * ex + ey * ey + ez * ez > P.res2);
-          const unsigned long long mask = __ballot(pass);
-          const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-          if (pass) { s_pair[pos] = prs[u]; atomicAdd(&s_cnt[prs[u] >> 24], 1u); }
-          kept += (uint32_t)__popcll(mask);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        // ---- phase B2: a lane per point over its kept voxels (they follow one another in the compacted window); the next record is
+        // on its way while this one is worked on
+        const uint32_t mine = s_cnt[lane];
+        s_cnt[lane] = 0u;
+        const uint32_t first = wave_incl_scan_u32(mine) - mine;
+        npairs_lane += mine;
+        VoxRaw vn;
+        vn.a = vn.b = vn.c = u32x4{0, 0, 0, 0};
+        uint32_t slot_next = 0;
+        if (mine) { slot_next = s_pair[first] & 0xffffffu; vn = load_voxel_raw(d.vox, slot_next); }
+        for (uint32_t jn = 0; jn < mine; ++jn) {
+          const VoxRaw vr = vn;
+          const uint32_t slot = slot_next;
+          if (jn + 1 < mine) { slot_next = s_pair[first + jn + 1] & 0xffffffu; vn = load_voxel_raw(d.vox, slot_next); }
+          // x_trans - mean in double, then R (:253, :490)
+          const R u0 = (R)(tdx - __hiloint2double((int)vr.a.y, (int)vr.a.x));
+          const R u1 = (R)(tdy - __hiloint2double((int)vr.a.w, (int)vr.a.z));
+          const R u2 = (R)(tdz - __hiloint2double((int)vr.b.y, (int)vr.b.x));
+          R cxx, cxy, cxz, cyy, cyz, czz;
+          if (kDouble) {
+            const gptr<double> ic = icovd + (size_t)slot * 6;
+            cxx = (R)ic[0]; cxy = (R)ic[1]; cxz = (R)ic[2]; cyy = (R)ic[3]; cyz = (R)ic[4]; czz = (R)ic[5];
+          } else {
+            cxx = __uint_as_float(vr.b.z); cxy = __uint_as_float(vr.b.w); cxz = __uint_as_float(vr.c.x);
+            cyy = __uint_as_float(vr.c.y); cyz = __uint_as_float(vr.c.z); czz = __uint_as_float(vr.c.w);
+          }
+          // x_trans4 * c_inv4
+          const R v0 = u0 * cxx + u1 * cxy + u2 * cxz;
+          const R v1 = u0 * cxy + u1 * cyy + u2 * cyz;
+          const R v2 = u0 * cxz + u1 * cyz + u2 * czz;
+          const R qq = u0 * v0 + u1 * v1 + u2 * v2;
+          const R e0 = kDouble ? (R)exp(-(double)gd2 * (double)qq / 2) : (R)expf(-(float)gd2 * (float)qq * 0.5f);   // :497
+          const R e1 = gd2 * e0;                                     // :501
+          // :504-505: a term whose e_x_cov_x is out of range (or NaN) adds nothing, not even its score -- here by a factor of zero
+          const bool good = !(e1 > (R)1 || e1 < (R)0 || e1 != e1);
+          S0 += good ? (R)(-P.d1d * (double)e0) : (R)0;                              // :499
+          const R e = good ? (R)(P.d1d * (double)e1) : (R)0;                          // :508
+          const R ev0 = e * v0, ev1 = e * v1, ev2 = e * v2;
+          sv0 += ev0; sv1 += ev1; sv2 += ev2;
+          SCxx += e * cxx; SCxy += e * cxy; SCxz += e * cxz; SCyy += e * cyy; SCyz += e * cyz; SCzz += e * czz;
+          if (HESS) { Wxx += ev0 * v0; Wxy += ev0 * v1; Wxz += ev0 * v2; Wyy += ev1 * v1; Wyz += ev1 * v2; Wzz += ev2 * v2; }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      // ---- phase B2: a lane per point over its kept voxels (they follow one another in the compacted window); the next record is
-      // on its way while this one is worked on
-      const uint32_t mine = s_cnt[lane];
-      s_cnt[lane] = 0u;
-      const uint32_t first = wave_incl_scan_u32(mine) - mine;
-      npairs_lane += mine;
-      VoxRaw vn;
-      vn.a = vn.b = vn.c = u32x4{0, 0, 0, 0};
-      uint32_t slot_next = 0;
-      if (mine) { slot_next = s_pair[first] & 0xffffffu; vn = load_voxel_raw(d.vox, slot_next); }
-      for (uint32_t jn = 0; jn < mine; ++jn) {
-        const VoxRaw vr = vn;
-        const uint32_t slot = slot_next;
-        if (jn + 1 < mine) { slot_next = s_pair[first + jn + 1] & 0xffffffu; vn = load_voxel_raw(d.vox, slot_next); }
-        // x_trans - mean in double, then R (:253, :490)
-        const R u0 = (R)(tdx - __hiloint2double((int)vr.a.y, (int)vr.a.x));
-        const R u1 = (R)(tdy - __hiloint2double((int)vr.a.w, (int)vr.a.z));
-        const R u2 = (R)(tdz - __hiloint2double((int)vr.b.y, (int)vr.b.x));
-        R cxx, cxy, cxz, cyy, cyz, czz;
-        if (kDouble) {
-          const gptr<double> ic = icovd + (size_t)slot * 6;
-          cxx = (R)ic[0]; cxy = (R)ic[1]; cxz = (R)ic[2]; cyy = (R)ic[3]; cyz = (R)ic[4]; czz = (R)ic[5];
-        } else {
-          cxx = __uint_as_float(vr.b.z); cxy = __uint_as_float(vr.b.w); cxz = __uint_as_float(vr.c.x);
-          cyy = __uint_as_float(vr.c.y); cyz = __uint_as_float(vr.c.z); czz = __uint_as_float(vr.c.w);
+    } else {
+      // ---- a direct rule: phase A lists the stencil's occupied cells inside the box, phase B2 works a point's run of them off
+      const int xc = min(max(c0, 0), div0 - 1);
+      uint32_t slot1 = 0, nnb = 0;                         // DIRECT1: the one entry; the point's entries
+      for (uint32_t wbase = 0; wbase == 0 || wbase < total; wbase += kCap) {
+        uint2 wa[9], wb[9], wc[9];                         // a row's words at x - 1, x + 1 (rows the stencil crosses three wide) or at x
+        uint32_t rowok = 0;
+        int c1w = c1, c2w = c2;
+        asm volatile("" : "+v"(c1w), "+v"(c2w));          // (keeps the row addresses out of registers across phase B)
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+          const int dz = r / 3 - 1, dy = r % 3 - 1;
+          if (!ndt_stencil_has<NB>(dz, dy, 0) && !ndt_stencil_has<NB>(dz, dy, 1)) continue;
+          const int z = c2w + dz, y = c1w + dy;
+          const bool ok = live && z >= 0 && z < div2 && y >= 0 && y < div1;
+          rowok |= ok ? 1u << r : 0u;
+          const int rowbase = ok ? (z * div1 + y) * wx : 0;
+          if (ndt_stencil_has<NB>(dz, dy, 1)) {
+            { const u32x2 v = words[rowbase + (xa >> 5)]; wa[r] = make_uint2(v.x, v.y); }
+            { const u32x2 v = words[rowbase + (xb >> 5)]; wb[r] = make_uint2(v.x, v.y); }
+          } else {
+            const u32x2 v = words[rowbase + (xc >> 5)]; wc[r] = make_uint2(v.x, v.y);
+          }
         }
-        // x_trans4 * c_inv4
-        const R v0 = u0 * cxx + u1 * cxy + u2 * cxz;
-        const R v1 = u0 * cxy + u1 * cyy + u2 * cyz;
-        const R v2 = u0 * cxz + u1 * cyz + u2 * czz;
-        const R qq = u0 * v0 + u1 * v1 + u2 * v2;
-        const R e0 = kDouble ? (R)exp(-(double)gd2 * (double)qq / 2) : (R)expf(-(float)gd2 * (float)qq * 0.5f);   // :497
-        const R e1 = gd2 * e0;                                     // :501
-        // :504-505: a term whose e_x_cov_x is out of range (or NaN) adds nothing, not even its score -- here by a factor of zero
-        const bool good = !(e1 > (R)1 || e1 < (R)0 || e1 != e1);
-        S0 += good ? (R)(-P.d1d * (double)e0) : (R)0;                              // :499
-        const R e = good ? (R)(P.d1d * (double)e1) : (R)0;                          // :508
-        const R ev0 = e * v0, ev1 = e * v1, ev2 = e * v2;
-        sv0 += ev0; sv1 += ev1; sv2 += ev2;
-        SCxx += e * cxx; SCxy += e * cxy; SCxz += e * cxz; SCyy += e * cyy; SCyz += e * cyz; SCzz += e * czz;
-        if (HESS) { Wxx += ev0 * v0; Wxy += ev0 * v1; Wxz += ev0 * v2; Wyy += ev1 * v1; Wyz += ev1 * v2; Wzz += ev2 * v2; }
+        // (one walk of the stencil in the reference's z, y, x order; `emit` false counts, true writes the window's entries)
+        auto walk = [&](const bool emit, uint32_t k) {
+#pragma unroll
+          for (int r = 0; r < 9; ++r)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+              if (!ndt_stencil_has<NB>(r / 3 - 1, r % 3 - 1, dx)) continue;
+              const int x = c0 + dx;
+              const uint2 wd = !ndt_stencil_has<NB>(r / 3 - 1, r % 3 - 1, 1) ? wc[r] : (x >> 5) == (xa >> 5) ? wa[r] : wb[r];
+              if (((rowok >> r) & 1u) && x >= 0 && x < div0 && ((wd.x >> (x & 31)) & 1u)) {
+                if (emit) {
+                  const uint32_t slot = wd.y + __popc(wd.x & ((1u << (x & 31)) - 1u));
+                  if (NB == kNdtSearchDirect1) slot1 = slot;
+                  else if (k < (uint32_t)kCap) s_pair[k] = slot;
+                }
+                ++k;
+              }
+            }
+          return k;
+        };
+        if (wbase == 0) nnb = walk(false, 0u);
+        if (NB != kNdtSearchDirect1 && wbase == 0) {
+          NDT_STAMP(2);
+          const uint32_t incl = wave_incl_scan_u32(nnb);
+          off = incl - nnb;
+          total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // (the wave's earlier reads of its window are done)
+        walk(true, off - wbase);                           // (positions below the window wrap: the unsigned compare drops them)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the window is written: LDS is in order inside a wave
+        NDT_STAMP(3);
+        // ---- phase B2: the part of the point's run [off, off + nnb) that lies in this window; the next record is on its way while
+        // this one is worked on.  A record's count (the last word of its line) decides min_points: -1 stays searchable
+        uint32_t first = 0, mine = nnb;
+        if (NB != kNdtSearchDirect1) {
+          const uint32_t lo = max(off, wbase), hi = min(off + nnb, wbase + (uint32_t)kCap);
+          first = lo - wbase; mine = hi > lo ? hi - lo : 0u;
+        }
+        auto slot_at = [&](const uint32_t j) { return NB == kNdtSearchDirect1 ? slot1 : s_pair[first + j]; };
+        VoxRaw vn;
+        vn.a = vn.b = vn.c = u32x4{0, 0, 0, 0};
+        uint32_t slot_next = 0;
+        int n_next = 0;
+        if (mine) { slot_next = slot_at(0); vn = load_voxel_raw(d.vox, slot_next); n_next = ((gptr<int32_t>)(d.vox + slot_next))[15]; }
+        for (uint32_t jn = 0; jn < mine; ++jn) {
+          const VoxRaw vr = vn;
+          const uint32_t slot = slot_next;
+          const bool keep = !(n_next >= 0 && n_next < d.min_points);
+          if (jn + 1 < mine) { slot_next = slot_at(jn + 1); vn = load_voxel_raw(d.vox, slot_next); n_next = ((gptr<int32_t>)(d.vox + slot_next))[15]; }
+          npairs_lane += keep ? 1u : 0u;
+          // the pair's terms as in KDTREE's phase B2, but for `keep`: an occupied cell below min_points adds nothing
+            // x_trans - mean in double, then R (:253, :490)
+            const R u0 = (R)(tdx - __hiloint2double((int)vr.a.y, (int)vr.a.x));
+            const R u1 = (R)(tdy - __hiloint2double((int)vr.a.w, (int)vr.a.z));
+            const R u2 = (R)(tdz - __hiloint2double((int)vr.b.y, (int)vr.b.x));
+            R cxx, cxy, cxz, cyy, cyz, czz;
+            if (kDouble) {
+              const gptr<double> ic = icovd + (size_t)slot * 6;
+              cxx = (R)ic[0]; cxy = (R)ic[1]; cxz = (R)ic[2]; cyy = (R)ic[3]; cyz = (R)ic[4]; czz = (R)ic[5];
+            } else {
+              cxx = __uint_as_float(vr.b.z); cxy = __uint_as_float(vr.b.w); cxz = __uint_as_float(vr.c.x);
+              cyy = __uint_as_float(vr.c.y); cyz = __uint_as_float(vr.c.z); czz = __uint_as_float(vr.c.w);
+            }
+            // x_trans4 * c_inv4
+            const R v0 = u0 * cxx + u1 * cxy + u2 * cxz;
+            const R v1 = u0 * cxy + u1 * cyy + u2 * cyz;
+            const R v2 = u0 * cxz + u1 * cyz + u2 * czz;
+            const R qq = u0 * v0 + u1 * v1 + u2 * v2;
+            const R e0 = kDouble ? (R)exp(-(double)gd2 * (double)qq / 2) : (R)expf(-(float)gd2 * (float)qq * 0.5f);   // :497
+            const R e1 = gd2 * e0;                                     // :501
+            // :504-505: a term whose e_x_cov_x is out of range (or NaN) adds nothing, not even its score -- here by a factor of zero
+            const bool good = keep && !(e1 > (R)1 || e1 < (R)0 || e1 != e1);
+            S0 += good ? (R)(-P.d1d * (double)e0) : (R)0;                              // :499
+            const R e = good ? (R)(P.d1d * (double)e1) : (R)0;                          // :508
+            const R ev0 = e * v0, ev1 = e * v1, ev2 = e * v2;
+            sv0 += ev0; sv1 += ev1; sv2 += ev2;
+            SCxx += e * cxx; SCxy += e * cxy; SCxz += e * cxz; SCyy += e * cyy; SCyz += e * cyz; SCzz += e * czz;
+            if (HESS) { Wxx += ev0 * v0; Wxy += ev0 * v1; Wxz += ev0 * v2; Wyy += ev1 * v1; Wyz += ev1 * v2; Wzz += ev2 * v2; }
+        }
       }
     }
     NDT_STAMP(4);
@@ -1164,6 +1293,17 @@ __global__ __launch_bounds__(kNdtDerivThreads, sizeof(R) == 4 ? 4 : 3) void ndt_
   __shared__ NdtDerivShared sh;
   if (c.pose.compute_hessian) ndt_derivatives_body<R, true>(d, c.pose, d.partials + (size_t)blockIdx.x * kNdtCols, sh);
   else ndt_derivatives_body<R, false>(d, c.pose, d.partials + (size_t)blockIdx.x * kNdtCols, sh);
+}
+// the same launch under a direct neighbourhood rule (NB = kNdtSearchDirect26 / 7 / 1); the KDTREE kernel above keeps its name and code
+template <typename R, int NB>
+__global__ __launch_bounds__(kNdtDerivThreads, sizeof(R) == 4 ? 4 : 3) void ndt_derivatives_direct_ctl(const NdtDev* __restrict__ devs, const NdtCtl* __restrict__ ctl) {
+  static_assert(NB == kNdtSearchDirect26 || NB == kNdtSearchDirect7 || NB == kNdtSearchDirect1, "a direct rule");
+  const NdtCtl& c = ctl[blockIdx.y];
+  if (c.phase == kNdtDone) return;
+  const NdtDev d = devs[c.slot];
+  __shared__ NdtDerivShared sh;
+  if (c.pose.compute_hessian) ndt_derivatives_body<R, true, NB>(d, c.pose, d.partials + (size_t)blockIdx.x * kNdtCols, sh);
+  else ndt_derivatives_body<R, false, NB>(d, c.pose, d.partials + (size_t)blockIdx.x * kNdtCols, sh);
 }
 
 // A workgroup per job: the fold of the job's rows (16 thread groups take every 16th row, then one thread per column adds the group

@@ -287,12 +287,26 @@ void ndt_ctl_start(const NdtHost& n, const NdtCtlOpts& o, NdtCtl& j, int slot, c
   P.compute_hessian = 1;
 }
 
+// one computeDerivatives launch over the jobs at `ctl`, in the handle's arithmetic and under its neighbourhood rule
+template <typename R>
+void ndt_launch_derivatives_as(smhip_context* h, const NdtHost& n, const dim3 g, const NdtCtl* ctl) {
+  const dim3 b(kNdtDerivThreads);
+  switch (n.opts.search_method) {
+    case SMHIP_NDT_SEARCH_DIRECT26: hipLaunchKernelGGL((ndt_derivatives_direct_ctl<R, kNdtSearchDirect26>), g, b, 0, h->stream, n.devs_dev, ctl); break;
+    case SMHIP_NDT_SEARCH_DIRECT7: hipLaunchKernelGGL((ndt_derivatives_direct_ctl<R, kNdtSearchDirect7>), g, b, 0, h->stream, n.devs_dev, ctl); break;
+    case SMHIP_NDT_SEARCH_DIRECT1: hipLaunchKernelGGL((ndt_derivatives_direct_ctl<R, kNdtSearchDirect1>), g, b, 0, h->stream, n.devs_dev, ctl); break;
+    default: hipLaunchKernelGGL(ndt_derivatives_ctl<R>, g, b, 0, h->stream, n.devs_dev, ctl); break;
+  }
+}
+void ndt_launch_derivatives(smhip_context* h, const NdtHost& n, const dim3 g, const NdtCtl* ctl) {
+  if (n.double_math) ndt_launch_derivatives_as<double>(h, n, g, ctl);
+  else ndt_launch_derivatives_as<float>(h, n, g, ctl);
+}
+
 // one round for jobs [0, K) of the batch whose first slot is `first`
 void ndt_enqueue_round(smhip_context* h, int first, int K, int blocks, const NdtCtlOpts& o, int round, double* out_host) {
   NdtHost& n = ndt_of(h);
-  const dim3 g(blocks, K);
-  if (n.double_math) hipLaunchKernelGGL(ndt_derivatives_ctl<double>, g, dim3(kNdtDerivThreads), 0, h->stream, n.devs_dev, n.ctl_dev + first);
-  else hipLaunchKernelGGL(ndt_derivatives_ctl<float>, g, dim3(kNdtDerivThreads), 0, h->stream, n.devs_dev, n.ctl_dev + first);
+  ndt_launch_derivatives(h, n, dim3(blocks, K), n.ctl_dev + first);
   hipLaunchKernelGGL(ndt_ctl_step, dim3(K), dim3(kNdtStepThreads), 0, h->stream, n.devs_dev, n.ctl_dev + first, blocks, o, round,
                      const_cast<PairInput*>(h->dev.in), n.flags_pinned + first, n.res_pinned + first, out_host);
 }
@@ -463,13 +477,18 @@ void smhip_ndt_default_options(smhip_ndt_options* o) {
 
 smhip_status smhip_ndt_set_options(smhip_handle h, const smhip_ndt_options* o) {
   if (!h || !o) return SMHIP_ERR_INVALID_ARGUMENT;
-  if (!(o->resolution > 0) || !(o->step_size > 0) || o->max_iterations < 0 || o->min_points_per_voxel < 3) {
+  if (!(o->resolution > 0) || !(o->step_size > 0) || o->max_iterations < 0 || o->min_points_per_voxel < 3 ||
+      o->search_method < SMHIP_NDT_SEARCH_KDTREE || o->search_method > SMHIP_NDT_SEARCH_DIRECT1) {
     h->err = "bad NDT options";
     return SMHIP_ERR_INVALID_ARGUMENT;
   }
   NdtHost& n = ndt_of(h);
+  // the voxel table is a function of the target and these three: a change of anything else (the neighbourhood rule, the step,
+  // the iteration cap) keeps the tables the slots hold
+  const bool same_table = o->resolution == n.opts.resolution && o->min_points_per_voxel == n.opts.min_points_per_voxel &&
+                          o->min_covar_eigvalue_mult == n.opts.min_covar_eigvalue_mult;
   n.opts = *o;
-  for (auto& m : n.meta) m.valid = false;
+  if (!same_table) for (auto& m : n.meta) m.valid = false;
   return SMHIP_OK;
 }
 
@@ -585,10 +604,7 @@ smhip_status smhip_ndt_time_derivatives(smhip_handle h, int first_slot, int npai
   const dim3 g(std::max(1, ceil_div(ns_max, kNdtDerivThreads)), npairs);
   hipEvent_t a, b;
   HIPCHK(h, hipEventCreate(&a)); HIPCHK(h, hipEventCreate(&b));
-  auto launch = [&]() {
-    if (n.double_math) hipLaunchKernelGGL(ndt_derivatives_ctl<double>, g, dim3(kNdtDerivThreads), 0, h->stream, n.devs_dev, n.ctl_dev + first_slot);
-    else hipLaunchKernelGGL(ndt_derivatives_ctl<float>, g, dim3(kNdtDerivThreads), 0, h->stream, n.devs_dev, n.ctl_dev + first_slot);
-  };
+  auto launch = [&]() { ndt_launch_derivatives(h, n, g, n.ctl_dev + first_slot); };
   launch();                                                  // warm
   HIPCHK(h, hipEventRecord(a, h->stream));
   for (int r = 0; r < launches; ++r) launch();

@@ -12,6 +12,8 @@ from . import _capi
 NN_BRUTE = 0
 NN_GRID = 1
 NN_NABO = 2          # libnabo's tree and epsilon-approximate search (the reference's own semantics)
+# NdtHip's search_method: pclomp's NeighborSearchMethod values
+from ._capi import NDT_SEARCH_KDTREE, NDT_SEARCH_DIRECT26, NDT_SEARCH_DIRECT7, NDT_SEARCH_DIRECT1  # noqa: E402,F401
 
 
 class SmhipError(RuntimeError):
@@ -310,7 +312,8 @@ class NdtHip(IcpFastHip):
     """registrators::Ndt (pclomp NDT) on the GPU: mirrors Ndt::Align (/root/reference/registrators/ndt.cc:38-64).
     Clouds are float32 [N,3+] arrays (the reference converts InnerPointType -> pcl::PointXYZ); the
     target needs no normals.  get_fitness_score() is PCL's getFitnessScore(): mean squared 1-NN
-    distance, LOWER is better."""
+    distance, LOWER is better.  Keyword options are smhip_ndt_options' fields, e.g. NdtHip(search_method=NDT_SEARCH_DIRECT7)
+    for pclomp's direct voxel neighbourhoods (the default is the wrapper's KDTREE)."""
 
     def __init__(self, device: int = 0, max_source_points: int = 131072, max_target_points: int = 524288,
                  stream: int | None = None, pair_slots: int = 1, **ndt_options):
@@ -323,11 +326,15 @@ class NdtHip(IcpFastHip):
         self.last_ndt_stats = None
 
     def set_ndt_options(self, **kw):
+        """Fields of smhip_ndt_options by name; `search_method` is one of NDT_SEARCH_KDTREE / DIRECT26 / DIRECT7 / DIRECT1
+        (pclomp's setNeighborhoodSearchMethod).  A refused set changes nothing, here or in the handle."""
+        new = _capi.NdtOptions.from_buffer_copy(self._nopts)
         for k, v in kw.items():
-            if not hasattr(self._nopts, k):
+            if not hasattr(new, k):
                 raise KeyError(f"unknown option {k}")
-            setattr(self._nopts, k, v)
-        self._check(self._lib.smhip_ndt_set_options(self._h, ctypes.byref(self._nopts)))
+            setattr(new, k, v)
+        self._check(self._lib.smhip_ndt_set_options(self._h, ctypes.byref(new)))
+        self._nopts = new
 
     def set_input_source(self, points, slot: int = 0):
         a = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
