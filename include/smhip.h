@@ -625,7 +625,9 @@ double smhip_m2dp_match(const float* P, const float* Q, int n);
  * isam_optimizer.cc:90-93 and of the multi-trajectory optimiser's between-factors (multi_trajectory_optimizer.cc:68-81).
  * smhip_pose_graph_*_calib take a fourth kind, HANDEYE ("Odometry calibration factor" below): the reference's odometry calibration
  * factor through ODOM_CALIB_KEY (:84-93, 153-162, 209-224, 361-367), the place its IsamOptimizer puts its Huber model.
- * Not restated: IMU, ViewGraph's picture output, the multi-trajectory optimiser itself, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
+ * The multi-trajectory optimiser and its builder (joining a second drive to a finished map) are host composition over these entries:
+ * include/smhip/multi_trajectory.h.
+ * Not restated: IMU, ViewGraph's picture output, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
  * conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300). */
 #define SMHIP_POSE_GRAPH_MAX_NODES 8192
 #define SMHIP_POSE_GRAPH_MAX_EDGES 32768

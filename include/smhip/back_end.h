@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <utility>
@@ -133,6 +134,8 @@ struct DetectResult {                           // loop_detector.h:49-70
 struct LoopFrame {
   Matrix4d global_pose = Matrix4d::Identity();
   InnerCloudPtr cloud;                          // may stay empty until a CloseLoop needs it
+  std::function<InnerCloudPtr()> cloud_loader;  // asked when a CloseLoop needs the cloud and `cloud` is empty (the reference's Submap::Cloud()
+                                                // reloads from disk); what it returns is used for that match and not kept here
   descriptor::M2dp::Descriptor descriptor;      // read when use_descriptor is set
   bool has_enu = false;                         // FrameBase::related_enu_ (builder/frame_base.h:93-95): the GPS fix of the frame,
   double enu[3] = {0.0, 0.0, 0.0};              // already in ENU metres; read by IsamOptimizer when use_gps is set
@@ -326,6 +329,7 @@ class LoopDetector {
     search_window_end_ = end_index;
   }
   const std::vector<std::shared_ptr<LoopFrame>>& GetFrames() const { return all_frames_; }
+  std::pair<int, int> SearchWindow() const { return {search_window_start_, search_window_end_}; }    // (-1, -1): none set
   LoopStatus Status() const { return current_status_; }
   // what the last AddFrame that searched selected (for inspection and tests)
   const LoopCandidates& LastCandidates() const { return last_candidates_; }
@@ -340,13 +344,18 @@ class LoopDetector {
   bool CloseLoopPair(LoopEdge* edge) {                                                         // :282-318
     const size_t target_id = static_cast<size_t>(edge->close_pair_index.first), source_id = static_cast<size_t>(edge->close_pair_index.second);
     SMHIP_CHECK(all_frames_.size() > target_id && all_frames_.size() > source_id, "CHECK(all_frames_.size() > target_id && ... > source_id)");
-    SMHIP_CHECK(all_frames_[target_id]->cloud && all_frames_[source_id]->cloud, "a frame of a candidate pair has no cloud");
+    const InnerCloudPtr target_cloud = FrameCloud(*all_frames_[target_id]), source_cloud = FrameCloud(*all_frames_[source_id]);
+    SMHIP_CHECK(target_cloud && source_cloud, "a frame of a candidate pair has no cloud");
     if (!scan_matcher_) {
       scan_matcher_.reset(new registrator::IcpPointMatcherHip(settings_.device, settings_.max_points));
       scan_matcher_->InitWithOptions();
     }
-    return CloseLoop(all_frames_[target_id]->global_pose, all_frames_[target_id]->cloud, all_frames_[source_id]->global_pose,
-                     all_frames_[source_id]->cloud, settings_, edge, scan_matcher_.get());
+    return CloseLoop(all_frames_[target_id]->global_pose, target_cloud, all_frames_[source_id]->global_pose, source_cloud, settings_, edge,
+                     scan_matcher_.get());
+  }
+  static InnerCloudPtr FrameCloud(const LoopFrame& frame) {
+    if (frame.cloud) return frame.cloud;
+    return frame.cloud_loader ? frame.cloud_loader() : InnerCloudPtr();
   }
 
  private:

@@ -46,7 +46,7 @@
 //     reference has a prior of sigma 1e-6 (:87-88), for the reason DESIGN.md section 6 gives for node 0; free, it carries the
 //     reference's prior of (0.5, 0.5, 1.5, 0.1, 0.1, 0.1) (:85-86).  The vertex starts at tf_odom_lidar^-1 itself: the reference's
 //     detour through Euler angles (:154-157) is the same matrix up to rounding.
-//   * Not restated, and without an option here: IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the multi-trajectory optimiser, the
+//   * Not restated, and without an option here: IMU, ViewGraph's picture output (GetWholeGraph returns the plain list), the
 //     geodetic conversion to ENU, the loop detector's commented-out GPS guess (loop_detector.cc:291-300).  The tf_error
 //     calibration point (GPS_CALIB_KEY) is not created: enable_extrinsic_calib = true is refused.
 #ifndef SMHIP_POSE_GRAPH_H_
@@ -106,6 +106,11 @@ class PoseGraph {
     poses_.push_back(pose);
     fixed_.push_back(0);
     return static_cast<int>(poses_.size()) - 1;
+  }
+  // Vertex `index` is held where it is from now on: a solve leaves its pose's bits (what vertex 0 of AddVertex is from the start)
+  void HoldVertex(int index) {
+    SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a held vertex exists");
+    fixed_[static_cast<size_t>(index)] = 1;
   }
   void AddPriorFactor(int index, const Matrix4d& pose, const Sigmas& sigmas, double huber = 0.0) {
     SMHIP_CHECK(index >= 0 && index < static_cast<int>(poses_.size()), "a prior is on a vertex that exists");

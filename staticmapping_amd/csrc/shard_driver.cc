@@ -188,6 +188,20 @@ Args Parse(int argc, char** argv) {
         a.odom_tf[0] = std::nan("");                                                     // (refused below)
       a.odom_tf_given = true;
     }
+    else if (k == "--save-trajectory-map") a.save_trajectory_map = val();
+    else if (k == "--join-base") a.join_base = val();
+    else if (k == "--join-incremental") a.join_incremental = val();
+    else if (k == "--join-out") a.join_out = val();
+    else if (k == "--join-pcd") { a.join_pcd = val(); a.join_option_given = true; }
+    else if (k == "--join-static-map") { a.join_static_map = val(); a.join_option_given = true; }
+    else if (k == "--join-hold-base") { a.join_hold_base = std::atoi(val().c_str()) != 0; a.join_option_given = true; }
+    else if (k == "--join-connection-huber") {
+      const std::string text = val();
+      char* end = nullptr;
+      a.join_connection_huber = std::strtod(text.c_str(), &end);
+      if (text.empty() || *end != '\0') a.join_connection_huber = std::nan("");        // (refused below)
+      a.join_option_given = true;
+    }
     else if (k == "--odom-calib") a.odom_calib = true;
     else if (k == "--odom-huber") {
       const std::string text = val();
@@ -211,10 +225,23 @@ Args Parse(int argc, char** argv) {
              "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
              "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]\n"
              "  odometry (with --close-loops): [--odom odom.txt (a line per scan: 12 numbers, the odometer's pose as a row-major 3x4, nan = no reading)] "
-             "[--odom-tf 0,0,0,0,0,0 (odom -> lidar: tx,ty,tz,rx,ry,rz)] [--odom-calib (estimate it)] [--odom-huber 1]");
+             "[--odom-tf 0,0,0,0,0,0 (odom -> lidar: tx,ty,tz,rx,ry,rz)] [--odom-calib (estimate it)] [--odom-huber 1]\n"
+             "  a map to join later (with --close-loops): [--save-trajectory-map DIR (DIR/map.xml and a cloud file per submap)]\n"
+             "  joining two maps (a run of its own, without --scans): --join-base A/map.xml --join-incremental B/map.xml --join-out C/map.xml "
+             "[--join-hold-base 1] [--join-connection-huber 0] [--join-pcd whole.pcd] [--join-static-map static.pcd] [--loop-* as above; --loop-huber 1] [--loop-report FILE]");
   }
   if (a.guess != "constant" && a.guess != "ctrv") Die("--guess takes constant or ctrv (got " + a.guess + ")");
-  if (a.scans_dir.empty()) Die("--scans DIR is required");
+  if (a.Join()) {
+    if (a.join_base.empty() || a.join_incremental.empty() || a.join_out.empty()) Die("a join takes --join-base, --join-incremental and --join-out together");
+    if (!a.scans_dir.empty() || !a.close_loops.empty() || !a.map_path.empty() || !a.map_poses.empty() || !a.map_package.empty() || !a.submap_edges.empty())
+      Die("a join is a run of its own: not with --scans, --map, --map-poses, --map-package, --submap-edges or --close-loops");
+    if (!a.gps_enu.empty() || !a.odom_file.empty() || !a.save_trajectory_map.empty()) Die("a join takes no --gps-enu, --odom or --save-trajectory-map");
+    if (!std::isfinite(a.join_connection_huber) || a.join_connection_huber < 0.0) Die("bad join setting (--join-connection-huber finite and >= 0)");
+  } else if (a.join_option_given) {
+    Die("--join-hold-base, --join-connection-huber, --join-pcd and --join-static-map need --join-base, --join-incremental and --join-out");
+  }
+  if (a.scans_dir.empty() && !a.Join()) Die("--scans DIR is required");
+  if (!a.save_trajectory_map.empty() && a.close_loops.empty()) Die("--save-trajectory-map needs --close-loops");
   if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
   if (!a.map_package.empty() && (!std::isfinite(a.package.piece_width) || !(a.package.piece_width > 0.0) || !std::isfinite(a.package.border_offset) ||
                                  a.package.descript_filename.empty()))
@@ -227,8 +254,8 @@ Args Parse(int argc, char** argv) {
   if (!a.submap_edges.empty() && !a.map_poses.empty()) Die("--submap-edges needs the alignment run (not --map-poses)");
   if (!a.close_loops.empty() && !a.map_poses.empty()) Die("--close-loops needs the alignment run (not --map-poses)");
   if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
-  if (a.loop_huber_given && a.close_loops.empty()) Die("--loop-huber needs --close-loops");
-  if (!a.loop_report.empty() && a.close_loops.empty()) Die("--loop-report needs --close-loops");
+  if (a.loop_huber_given && a.close_loops.empty() && !a.Join()) Die("--loop-huber needs --close-loops");
+  if (!a.loop_report.empty() && a.close_loops.empty() && !a.Join()) Die("--loop-report needs --close-loops");
   if (a.gps_output_enu && a.gps_enu.empty()) Die("--gps-output-enu needs --gps-enu");
   if (!a.odom_file.empty() && a.close_loops.empty()) Die("--odom needs --close-loops");
   if ((a.odom_tf_given || a.odom_calib || a.odom_huber_given) && a.odom_file.empty()) Die("--odom-tf, --odom-calib and --odom-huber need --odom");
@@ -599,6 +626,7 @@ int main(int argc, char** argv) {
   Args a = Parse(argc, argv);
   if (!a.gps_enu.empty()) ReadGpsEnu(&a);
   if (!a.odom_file.empty()) ReadOdom(&a);
+  if (a.Join()) return JoinMaps(a, 0);                                   // joining two maps: one process, no scans, no RCCL
   if (a.id_file.empty()) a.id_file = "/tmp/smhip_shard_id_" + std::to_string(a.rank >= 0 ? static_cast<long>(getppid()) : static_cast<long>(getpid()));
   if (!a.map_poses.empty()) return RunMapOnly(a);                       // the map alone: one process, no RCCL
   if (a.rank >= 0) {                                                     // one rank of a launched group

@@ -24,6 +24,7 @@
 #include "../../include/smhip/back_end.h"
 #include "../../include/smhip/pose_graph.h"
 #include "../../include/smhip/map_package.h"
+#include "../../include/smhip/multi_trajectory.h"
 #include "shard_poses.h"
 
 namespace shard {
@@ -76,6 +77,15 @@ struct Args {
   double odom_tf[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool odom_tf_given = false, odom_calib = false, odom_huber_given = false;
   double odom_huber = 1.0;
+  // --save-trajectory-map DIR (with --close-loops): DIR/map.xml and a cloud file per submap, the files a later join loads
+  std::string save_trajectory_map;
+  // the join, a run of its own without --scans: --join-base A/map.xml --join-incremental B/map.xml --join-out C/map.xml
+  // [--join-hold-base 1] [--join-connection-huber K] [--join-pcd whole.pcd] [--join-static-map static.pcd]; it shares --loop-* and
+  // --loop-report, and --loop-huber defaults to the multi-trajectory optimiser's 1 there
+  std::string join_base, join_incremental, join_out, join_pcd, join_static_map;
+  bool join_hold_base = false, join_option_given = false;
+  double join_connection_huber = 0.0;
+  bool Join() const { return !join_base.empty() || !join_incremental.empty() || !join_out.empty(); }
 };
 
 [[noreturn]] inline void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
@@ -420,7 +430,13 @@ inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files,
 // --odom-huber K is the factors' threshold (default 1).  The JSON line gains "odom_factors" and "odom_tf" (the transform after the
 // final solve, row-major).  --odom without --close-loops, a FILE whose line count is not the scan count or with a line that does not
 // hold 12 numbers, a bad --odom-tf or K: exit 2 before any device work.
+// --save-trajectory-map DIR writes, beside all this, the map a later join loads (smhip/trajectory_map.h): DIR/submap_<k>.bin, the cloud
+// of submap k as it was built and matched, read back from the device, and after the final solve DIR/map.xml: one trajectory, the
+// corrected submap poses, and per submap the connections to the next submap and to the source of every accepted loop edge.  Every
+// other output is what it is without the flag.
 // Returns 0, or 3 when the device refused something (the file is then removed and no report written).
+inline std::string TrajectoryMapCloudName(int k) { return "submap_" + std::to_string(k) + ".bin"; }
+
 inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
   namespace be = smhip::back_end;
   namespace bld = smhip::builder;
@@ -437,6 +453,10 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   std::ofstream out(a.close_loops);
   if (!out) Die("cannot write " + a.close_loops);
   out.precision(8);
+  if (!a.save_trajectory_map.empty()) {
+    struct stat sb;
+    if (::mkdir(a.save_trajectory_map.c_str(), 0777) != 0 && !(::stat(a.save_trajectory_map.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode))) Die("cannot create " + a.save_trajectory_map);
+  }
   int rc = 0;
   if (S < 1) {
     for (int f = 0; f < n_frames; ++f) WritePoseLine(out, poses[f].data());
@@ -455,16 +475,7 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     io.loop_closure_huber = a.loop_huber;
     io.use_odom = !a.odom_file.empty(); io.odom_extrinsic_calib = a.odom_calib; io.odom_huber = a.odom_huber;
     be::IsamOptimizer optimizer(io, settings, h);
-    if (io.use_odom) {   // common::Vector6ToTransform: the translation, then R = Rz(rz) Ry(ry) Rx(rx)
-      const double* v = a.odom_tf;
-      const double cx = std::cos(v[3]), sx = std::sin(v[3]), cy = std::cos(v[4]), sy = std::sin(v[4]), cz = std::cos(v[5]), sz = std::sin(v[5]);
-      Matrix4d tf = Matrix4d::Identity();
-      tf(0, 0) = cz * cy; tf(0, 1) = cz * sy * sx - sz * cx; tf(0, 2) = cz * sy * cx + sz * sx;
-      tf(1, 0) = sz * cy; tf(1, 1) = sz * sy * sx + cz * cx; tf(1, 2) = sz * sy * cx - cz * sx;
-      tf(2, 0) = -sy;     tf(2, 1) = cy * sx;                tf(2, 2) = cy * cx;
-      for (int c = 0; c < 3; ++c) tf(c, 3) = v[c];
-      optimizer.SetTransformOdomToLidar(tf);
-    }
+    if (io.use_odom) optimizer.SetTransformOdomToLidar(bld::Vector6ToTransform(a.odom_tf));   // common::Vector6ToTransform: R = Rz(rz) Ry(ry) Rx(rx)
     {
       Matrix4d tracking_to_gps = Matrix4d::Identity();
       for (int c = 0; c < 3; ++c) tracking_to_gps(c, 3) = a.gps_lever[c];
@@ -496,6 +507,12 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
         if (smhip_filter_get_output(h, &pts[0].x, nullptr, m) != SMHIP_OK) { std::fprintf(stderr, "smhip_shard: cloud of submap %d: %s\n", k, smhip_last_error(h)); rc = 3; break; }
         frame->cloud.reset(new smhip::data::InnerPointCloudData(pts));
         frame->cloud->CalculateNormals();
+        if (!a.save_trajectory_map.empty()) {                              // the submap's cloud as the join will load it
+          smhip::data::InnerCloudType cloud;
+          cloud.points = pts;
+          std::string why;
+          if (!bld::WriteSubmapCloud(a.save_trajectory_map + "/" + TrajectoryMapCloudName(k), cloud, &why)) Die(why);
+        }
       }
       Matrix4d from_last = Matrix4d::Identity();
       if (k > 0) {
@@ -554,6 +571,23 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
           for (int f = 0; f < N; ++f) WritePoseLine(out, maps[k]->FrameGlobalPose(f).data());
         }
       }
+      if (!a.save_trajectory_map.empty()) {
+        // one trajectory at the corrected poses; a submap's connections are the next submap and the source of every loop edge it is the
+        // target of (isam_optimizer.cc:136, 168), which is what GetWholeGraph lists for a vertex
+        bld::TrajectoryMap map;
+        map.trajectories.emplace_back();
+        const std::vector<be::GraphItem> graph = optimizer.GetWholeGraph();
+        for (int k = 0; k < S; ++k) {
+          bld::MapSubmap s;
+          s.id.submap_index = k;
+          s.file = TrajectoryMapCloudName(k);
+          s.SetPose(frames[k]->global_pose);
+          for (const auto& c : graph[static_cast<size_t>(k)].connections) { bld::SubmapId id; id.submap_index = c.first; s.connections.push_back(id); }
+          map.trajectories[0].submaps.push_back(s);
+        }
+        std::string why;
+        if (!bld::WriteTrajectoryMap(a.save_trajectory_map + "/map.xml", map, &why)) Die(why);
+      }
       Pose last;
       std::memcpy(last.data(), (a.gps_output_enu ? be::Multiply(to_enu, frames.back()->global_pose) : frames.back()->global_pose).data(), sizeof(double) * 16);
       const Pose carry = MulPose(last, AffineInverse(poses[(S - 1) * N]));
@@ -580,6 +614,77 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.odom_tf[q], q == 15 ? "]" : ", ");
   }
   return 0;
+}
+
+// ---- the join -----------------------------------------------------------------------------------------------------------------
+// --join-base A/map.xml --join-incremental B/map.xml --join-out C/map.xml: MultiTrajectoryMapBuilder (smhip/multi_trajectory.h) end to
+// end, a run of its own without --scans.  Both files are read and checked before any device work (exit 2 with the reader's reason);
+// then the base map's submaps enter the graph, the incremental map's with loop detection against the base (the --loop-* settings;
+// --loop-huber defaults to 1 here), one solve, and the joined map goes to --join-out.  A submap file beside --join-out keeps its name
+// there, any other is named by its full path.  --join-hold-base 1 holds the base map's poses; --join-connection-huber K puts the
+// threshold K on the connections (the reference's 1; default 0); --join-pcd and --join-static-map write the whole map and the static
+// map; --loop-report a line per cross edge (nodes in the joined order).  Returns 0, or 3 when the device refused something.
+inline int JoinMaps(const Args& a, int device) {
+  namespace bld = smhip::builder;
+  const auto t0 = std::chrono::steady_clock::now();
+  long long cap = 1 << 16;
+  for (const std::string* file : {&a.join_base, &a.join_incremental}) {
+    bld::TrajectoryMap m;
+    std::string why;
+    if (!bld::ReadTrajectoryMap(*file, &m, &why)) Die(why);
+    if (m.SubmapCount() == 0) Die(*file + " holds no submap");
+    for (const bld::MapTrajectory& t : m.trajectories)
+      for (const bld::MapSubmap& s : t.submaps) { struct stat sb; if (::stat(s.Path().c_str(), &sb) == 0) cap = std::max<long long>(cap, (sb.st_size - 20) / 20); }
+  }
+  if (cap > 4194304) Die("a submap of " + std::to_string(cap) + " points exceeds the backend's limit of 4194304");
+  smhip_handle h = nullptr;
+  const smhip_status st = smhip_create(device, nullptr, 1, static_cast<int>(cap), static_cast<int>(cap), &h);
+  if (st != SMHIP_OK) Die(std::string("smhip_create (join): ") + smhip_status_string(st) + " (is this a gfx950 GPU? there is no CPU fallback)");
+  int rc = 0;
+  std::string line;
+  {
+    smhip::MultiTrajectoryMapBuilderOptions o;
+    o.loop_detect_settings = a.loop;
+    o.loop_detect_settings.device = device;
+    o.loop_detect_settings.max_points = static_cast<int>(cap);
+    o.optimizer.hold_base_map = a.join_hold_base;
+    o.optimizer.connection_huber = a.join_connection_huber;
+    o.optimizer.loop_closure_huber = a.loop_huber_given ? a.loop_huber : 1.0;
+    o.device = device;
+    smhip::MultiTrajectoryMapBuilder builder(o, h, cap);
+    auto failed = [&](const char* what) { std::fprintf(stderr, "smhip_shard: join: %s: %s\n", what, builder.LastError().c_str()); rc = 3; };
+    if (!builder.LoadBaseMap(a.join_base)) failed("base map");
+    if (rc == 0 && !builder.LoadIncrementalMap(a.join_incremental)) failed("incremental map");
+    if (rc == 0 && !builder.SaveWholeMap(a.join_out)) failed("joined map");
+    std::vector<smhip::back_end::LoopEdgeWeight> report;
+    if (rc == 0) {
+      report = builder.Optimizer()->LoopEdgeReport();
+      if (static_cast<int>(report.size()) != builder.Optimizer()->LoopEdgeCount()) { std::fprintf(stderr, "smhip_shard: join: the cross edges' report was refused\n"); rc = 3; }
+    }
+    if (rc == 0 && !a.loop_report.empty()) {
+      std::ofstream rep(a.loop_report);
+      if (!rep) Die("cannot write " + a.loop_report);
+      for (const smhip::back_end::LoopEdgeWeight& w : report) rep << Fmt("%d %d %.8g %.8g\n", w.target, w.source, w.norm, w.weight);
+    }
+    if (rc == 0 && !a.join_pcd.empty() && !builder.GenerateWholeMapPcd(a.join_pcd)) failed("whole-map PCD");
+    if (rc == 0 && !a.join_static_map.empty() && !builder.GenerateStaticMap(a.join_static_map)) failed("static map");
+    if (rc == 0) {
+      const smhip_pose_graph_stats& stats = builder.Optimizer()->LastStats();
+      int down = 0;
+      for (const smhip::back_end::LoopEdgeWeight& w : report) down += w.weight < 1.0;
+      line = Fmt("{\"driver\": \"smhip_shard (join)\", \"join_base\": \"%s\", \"join_incremental\": \"%s\", \"join_out\": \"%s\", \"join_hold_base\": %d, "
+                 "\"join_base_submaps\": %d, \"join_incremental_submaps\": %d, \"join_loop_edges\": %d, \"join_loop_edges_downweighted\": %d, "
+                 "\"join_pose_graph_stop_reason\": %d, \"join_pose_graph_final_cost\": %.6g, \"join_pcg_iterations\": %d, \"join_solve_seconds\": %.4f",
+                 a.join_base.c_str(), a.join_incremental.c_str(), a.join_out.c_str(), a.join_hold_base ? 1 : 0, builder.BaseSubmapCount(), builder.IncrementalSubmapCount(),
+                 builder.Optimizer()->LoopEdgeCount(), down, stats.stop_reason, stats.final_cost, stats.pcg_iterations, builder.SolveSeconds());
+      if (!a.join_pcd.empty()) line += Fmt(", \"join_pcd\": \"%s\", \"join_pcd_points\": %lld", a.join_pcd.c_str(), builder.WholeMapPoints());
+      if (!a.join_static_map.empty()) line += Fmt(", \"join_static_map\": \"%s\", \"join_static_map_voxels\": %d", a.join_static_map.c_str(), builder.StaticMapVoxels());
+      line += Fmt(", \"join_seconds\": %.4f}", Since(t0));
+    }
+  }
+  smhip_destroy(h);
+  if (rc == 0 && !a.quiet) std::printf("%s\n", line.c_str());
+  return rc;
 }
 
 // ---- the passes, in their order ----------------------------------------------------------------------------------------------

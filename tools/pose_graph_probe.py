@@ -10,6 +10,9 @@ room for: one with 3 loop edges, four with 60), with or without --huber.  Withou
 --odom: instead, the drive with 3 loop edges re-based to start at the identity, with an odometry calibration (HANDEYE) factor of threshold
 1 on every submap through smhip_pose_graph_optimize_calib ("Odometry calibration factor"): the calibration node is a
 chord to every submap.  The calibration is held at the truth; with --odom-calib it is free from a start 0.1 rad off.
+--join: instead, two drives of 909 submaps joined (tests/multi_trajectory_ref.py: the graph MultiTrajectoryMapBuilder solves, DESIGN.md
+section 6, "Joining maps"): the second loaded 0.5 m and 0.5 degrees off, a cross edge on every second of its submaps, once with the base
+map free and once held (profiles/pose_graph_join_probe.json).  The free solve can run for a minute: use --repeats 2 --warmup 1.
 One JSON line on stdout (and in --out when given)."""
 import argparse
 import json
@@ -83,6 +86,41 @@ def odom_case(m, a):
             "calib_rotation_error_rad": [r0, r1], "calib_translation_error_m": [t0m, t1m]}
 
 
+def join_cases(m, a):
+    """909 + 909 submaps, a cross edge on every second incremental submap from the fourth on; the base free, then held"""
+    import multi_trajectory_ref as mt
+    from staticmapping_amd import pose_graph
+    case = mt.join_case(N_NODES, N_NODES, every=2)
+    with_edge = [s for _, s, _ in case["cross"]]
+    out = []
+    for hold in (False, True):
+        g = mt.assemble(case, hold_base=hold)
+
+        def call():
+            return pose_graph.optimize_robust(m, g["poses"], g["kinds"], g["ij"], g["data"], fixed=g["fixed"], sigmas=g["sigmas"], huber=g["huber"])
+        for _ in range(a.warmup):
+            call()
+        t = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            poses, stats = call()
+            t.append(time.perf_counter() - t0)
+        rep = pose_graph.last_robust(m, len(g["kinds"]))
+        before = [mt.mutual_error(case, g["poses"], s) for s in with_edge]
+        after = [mt.mutual_error(case, poses, s) for s in with_edge]
+        out.append({"join": "909 + 909", "hold_base": hold, "nodes": int(len(g["poses"])), "factors": int(len(g["kinds"])), "cross_edges": len(with_edge),
+                    "device_median_ms": round(float(np.median(t)) * 1e3, 4), "device_min_ms": round(float(np.min(t)) * 1e3, 4), "outer_steps": stats["iterations"],
+                    "rejected_steps": stats["rejected_steps"], "pcg_iterations": stats["pcg_iterations"], "pcg_longest_solve": stats["pcg_max_iterations"],
+                    "pcg_cap": stats["pcg_cap"], "pcg_total_limit": 200000, "levels": stats["levels"],
+                    "stop": stats["stop"], "initial_cost": stats["initial_cost"], "final_cost": stats["final_cost"],
+                    "cross_edges_downweighted": int((rep["weight"][g["loops"]] < 1.0).sum()),
+                    "mutual_error_before_m": [round(float(np.min(before)), 4), round(float(np.max(before)), 4)],
+                    "mutual_error_after_m": [round(float(np.median(after)), 4), round(float(np.max(after)), 4)],
+                    "mutual_error_after_at_submap_0_m": round(mt.mutual_error(case, poses, 0), 4),
+                    "base_moved_m": float(np.linalg.norm(poses[:N_NODES, :3, 3] - case["base"][:, :3, 3], axis=1).max())})
+    return out
+
+
 def robust_case(m, a, drive, n_loops, overlap):
     """the loop case `drive` as factors, plus --bad-loops wrong loop edges, solved with the threshold --huber on the loop edges"""
     import pose_graph_robust_cases as cases
@@ -120,6 +158,7 @@ def main():
     ap.add_argument("--bad-loops", type=int, default=0, help="wrong loop edges added beside the good ones")
     ap.add_argument("--odom", action="store_true", help="an odometry calibration factor on every submap of the drive with 3 loop edges, instead of the two loop cases")
     ap.add_argument("--odom-calib", action="store_true", help="with --odom: the calibration free, from a start 0.1 rad off")
+    ap.add_argument("--join", action="store_true", help="two 909-submap drives joined, a cross edge on every second incremental submap, with the base free and held")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -135,7 +174,9 @@ def main():
         res["cases"].append(gps_case(m, a))
     if a.odom:
         res["cases"].append(odom_case(m, a))
-    for n_loops in (() if a.gps or a.odom else (3, 60)):
+    if a.join:
+        res["cases"] += join_cases(m, a)
+    for n_loops in (() if a.gps or a.odom or a.join else (3, 60)):
         # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
         g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
         if a.huber > 0.0 or a.bad_loops > 0:
