@@ -211,6 +211,26 @@ smhip_status smhip_icp_align_range(smhip_handle h, int first_slot, int npairs, c
  * *kept (may be NULL) = their number.  The target needs no normals. */
 smhip_status smhip_icp_trimmed_score(smhip_handle h, int slot, const double T[16], float dist_outlier_ratio, double* score,
                                      int32_t* kept);
+/* The 6x6 information of an alignment at T (column-major, source -> target), in the tangent convention of the pose graph's
+ * BETWEEN residual below (rotation first, T <- T * [Exp(phi), rho]).  The matches are those of ONE FindClosests pass at T, every
+ * one exact; the kept set is TrimmedDist(ratio)'s over them, the rule and the int(n * ratio) rank of smhip_icp_trimmed_score:
+ * kept = d2 finite and d2 <= limit_d2.  For a kept source point s (caller's coordinates) matched to target q with normal n:
+ * m = R^T n, r = n . (R s + t - q), J = [s x m ; m].  H = sum J J^T (row-major, symmetric), sum_r2 = sum r^2, n_finite = the
+ * matches with finite d2.  All sums are f64 from the stored f32 values, added in an order fixed by the cloud's size alone: two
+ * calls, the range call and the single calls, and either launch form of the matching pass give the same bits.  Needs a target
+ * with normals (SMHIP_ERR_NO_NORMALS).  The caller's ICP options are unchanged afterwards.  A pair without a finite
+ * correspondence has its status in out[k].status and H = 0; the call then returns the first such status, as the align calls do. */
+typedef struct smhip_icp_information {
+  double H[36];
+  double sum_r2;
+  double limit_d2;
+  int32_t kept, n_finite;
+  int32_t status, reserved;
+} smhip_icp_information;
+smhip_status smhip_icp_information_at(smhip_handle h, int slot, const double T[16], float dist_outlier_ratio,
+                                      smhip_icp_information* out);
+smhip_status smhip_icp_information_range(smhip_handle h, int first_slot, int npairs, const double* Ts, float dist_outlier_ratio,
+                                         smhip_icp_information* out);
 /* Asynchronous halves of the batch call: enqueue leaves everything on the stream (needs
  * early_exit = 0 or accepts running all max_iteration launches), fetch blocks and copies out. */
 smhip_status smhip_icp_enqueue_batch(smhip_handle h, int npairs, const double* guesses);
@@ -625,6 +645,8 @@ double smhip_m2dp_match(const float* P, const float* Q, int n);
  * isam_optimizer.cc:90-93 and of the multi-trajectory optimiser's between-factors (multi_trajectory_optimizer.cc:68-81).
  * smhip_pose_graph_*_calib take a fourth kind, HANDEYE ("Odometry calibration factor" below): the reference's odometry calibration
  * factor through ODOM_CALIB_KEY (:84-93, 153-162, 209-224, 361-367), the place its IsamOptimizer puts its Huber model.
+ * smhip_pose_graph_*_info let a BETWEEN carry a full 6x6 square-root information ("Edge information" below): the matcher's own,
+ * where the reference weighs every scan-match edge with the same constants (:80-83).
  * The multi-trajectory optimiser and its builder (joining a second drive to a finished map) are host composition over these entries:
  * include/smhip/multi_trajectory.h.
  * Not restated: IMU, ViewGraph's picture output, the tf_error calibration point of enable_extrinsic_calib (GPS_CALIB_KEY), the geodetic
@@ -761,6 +783,25 @@ smhip_status smhip_pose_graph_plan_calib(int n_nodes, const double* poses, const
 smhip_status smhip_pose_graph_optimize_calib(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
                                              const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
                                              const double* huber, const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
+/* Edge information ("Edge information"; tests/pose_graph_info_ref.py).  A BETWEEN factor may carry a full 6x6
+ * square-root information L (row-major; the factor's information is L^T L) in place of its six inverse sigmas: rw = L e, A_w = L A,
+ * B_w = L B, s_f^2 = |L e|^2, with e, A and B the unwhitened residual and Jacobians above; Huber acts on s_f as before.  This is how
+ * the matcher's own information (smhip_icp_information, include/smhip/edge_information.h) reaches the optimiser.
+ * The *_info entries take the argument lists of the *_calib ones plus, after huber: info_index, one per factor -- -1 = use the sigmas,
+ * otherwise the index of an entry of sqrt_info, below n_factors -- or NULL = none; sqrt_info, 36 doubles per entry.  With info_index
+ * NULL or all -1 every output has the bits of the *_calib call.  A factor with an L still needs valid sigmas; the kernel does not
+ * read them.  Refused beside the refusals of the *_calib forms, before anything is touched, SMHIP_ERR_INVALID_ARGUMENT: an index
+ * below -1 or not below n_factors; an L on a factor that is no BETWEEN; an L with a non-finite entry; a singular L (the smallest pivot
+ * of an LU with partial pivoting at or below 1e-12 times its largest entry).  smhip_pose_graph_last and smhip_pose_graph_last_robust
+ * serve these calls too. */
+smhip_status smhip_pose_graph_plan_info(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds,
+                                        const int32_t* ij, const double* data, const double* sigmas, const double* huber,
+                                        const int32_t* info_index, const double* sqrt_info, int32_t* csr_offsets, int32_t* csr_edges,
+                                        char* why, int why_len);
+smhip_status smhip_pose_graph_optimize_info(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_factors,
+                                            const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
+                                            const double* huber, const int32_t* info_index, const double* sqrt_info,
+                                            const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

@@ -27,6 +27,7 @@
 #include <thread>
 #include <vector>
 
+#include "smhip/edge_information.h"
 #include "smhip/m2dp.h"
 #include "smhip/registrator.h"
 
@@ -75,6 +76,8 @@ struct LoopEdge {
   Matrix4d init_guess = Matrix4d::Identity();
   Matrix4d transform = Matrix4d::Identity();
   double score = 0.0;
+  bool has_information = false;                 // LoopDetectorSettings::edge_information: the accepted match's own information,
+  EdgeInformation information;                  // measured at `transform` (smhip/edge_information.h)
 };
 
 struct LoopDetectorSettings {                   // back_end/loop_detector_options.h:29-40
@@ -90,6 +93,8 @@ struct LoopDetectorSettings {                   // back_end/loop_detector_option
   float max_close_loop_distance = 25.f;
   float max_close_loop_z_distance = 1.f;
   float m2dp_match_score = 0.99f;
+  bool edge_information = false;     // (not in the reference) CloseLoop measures an accepted match's 6x6 information and leaves it on the edge
+  EdgeInformationOptions edge_information_options;
 };
 
 // LoopDetector::CloseLoop for one candidate pair of frames.  `scan_matcher` plays the stack matcher of :304; handing in
@@ -107,6 +112,11 @@ inline bool CloseLoop(const Matrix4d& target_global_pose, const InnerCloudPtr& t
   const double match_score = scan_matcher->GetFitnessScore();
   if (match_score > settings.accept_scan_match_score) {                                     // :309
     edge->score = -std::log(match_score);                                                   // :312
+    if (settings.edge_information) {         // nothing is computed unless asked; a match whose information cannot be had keeps the sigmas
+      AlignInformation info;
+      edge->has_information = scan_matcher->GetInformation(edge->transform, &info);
+      if (edge->has_information) edge->information = MakeEdgeInformation(info, settings.edge_information_options);
+    }
     return true;
   }
   return false;
@@ -376,6 +386,8 @@ struct SubmapPairMatchResult {
   Matrix4d guess = Matrix4d::Identity();
   double match_score = 0.0;                            // source_submap->match_score_to_previous_submap_
   bool accepted = false;
+  bool has_information = false;                        // SubmapPairMatchBatch with `information_options`: an accepted pair's own information,
+  EdgeInformation information;                         // measured at transform_to_next (smhip/edge_information.h)
 };
 
 // MapBuilder::SubmapPairMatch for one (source, target) pair of submaps
@@ -410,9 +422,14 @@ struct SubmapPairJob {
   Matrix4d source_first_frame_pose = Matrix4d::Identity(), target_first_frame_pose = Matrix4d::Identity();
 };
 
+// information_options (null: nothing is computed): with an IcpFast matcher every accepted pair's result also carries the
+// information of its match, all of them measured in ONE further call on the batch's resident clouds.  Where the pairs were aligned
+// one by one (no batch was taken), an IcpFast or IcpPointMatcher measures each pair after its Align.  A matcher that cannot measure
+// (the batch form of IcpPointMatcher, Ndt, NdtWithGicp) says so on stderr, once, and its edges keep the fixed sigmas.
 inline std::vector<SubmapPairMatchResult> SubmapPairMatchBatch(const registrator::MatcherOptions& options,
                                                                const std::shared_ptr<registrator::Interface>& matcher,
-                                                               const std::vector<SubmapPairJob>& jobs) {
+                                                               const std::vector<SubmapPairJob>& jobs,
+                                                               const EdgeInformationOptions* information_options = nullptr) {
   SMHIP_CHECK(matcher != nullptr, "CreateMatcher returned null");
   const size_t K = jobs.size();
   std::vector<SubmapPairMatchResult> out(K);
@@ -431,14 +448,25 @@ inline std::vector<SubmapPairMatchResult> SubmapPairMatchBatch(const registrator
   else if (auto* pm = dynamic_cast<registrator::IcpPointMatcherHip*>(matcher.get())) batched = pm->AlignBatch(src, tgt, guess, &result, &score);
   else if (auto* ndt = dynamic_cast<registrator::NdtHip*>(matcher.get())) batched = ndt->AlignBatch(src, tgt, guess, &result, &score);   // lock-step Newton
   else if (auto* ng = dynamic_cast<registrator::NdtGicpHip*>(matcher.get())) batched = ng->AlignBatch(src, tgt, guess, &result, &score);   // lock-step NDT + BFGS
+  std::vector<AlignInformation> single_info(information_options ? K : 0);
+  std::vector<uint8_t> single_has(single_info.size(), 0);
+  bool can_measure = false;
   if (!batched) {
     result.assign(guess.begin(), guess.end());
     score.assign(K, 0.0);
+    auto* one_fast = dynamic_cast<registrator::IcpFastHip*>(matcher.get());
+    auto* one_pm = dynamic_cast<registrator::IcpPointMatcherHip*>(matcher.get());
+    can_measure = one_fast || one_pm;
     for (size_t k = 0; k < K; ++k) {
       matcher->SetInputSource(src[k]);
       matcher->SetInputTarget(tgt[k]);
       matcher->Align(guess[k], result[k]);
       score[k] = matcher->GetFitnessScore();
+      if (information_options && can_measure && score[k] >= options.accepted_min_score) {   // while the pair is still on the device
+        Matrix4d at = result[k];
+        NormalizeRotation(at);
+        single_has[k] = (one_fast ? one_fast->GetInformation(at, &single_info[k]) : one_pm->GetInformation(at, &single_info[k])) ? 1 : 0;
+      }
     }
   }
   for (size_t k = 0; k < K; ++k) {
@@ -446,6 +474,25 @@ inline std::vector<SubmapPairMatchResult> SubmapPairMatchBatch(const registrator
     out[k].match_score = score[k];
     if (score[k] >= options.accepted_min_score) { out[k].transform_to_next = result[k]; out[k].accepted = true; }   // :437-439
     else { out[k].transform_to_next = out[k].guess; out[k].accepted = false; }                 // :440-444
+  }
+  auto* fast = dynamic_cast<registrator::IcpFastHip*>(matcher.get());
+  if (information_options && !batched) {
+    for (size_t k = 0; k < K; ++k)
+      if (out[k].accepted && single_has[k]) { out[k].has_information = true; out[k].information = MakeEdgeInformation(single_info[k], *information_options); }
+  }
+  if (information_options && !(batched ? fast != nullptr : can_measure)) {
+    static bool said = false;
+    if (!said) std::fprintf(stderr, "[WARN] SubmapPairMatchBatch: this matcher cannot measure the information of its matches here; the edges keep the fixed sigmas\n");
+    said = true;
+  }
+  if (information_options && batched && fast) {
+    std::vector<Matrix4d> at(K);
+    for (size_t k = 0; k < K; ++k) at[k] = out[k].transform_to_next;
+    std::vector<AlignInformation> info;
+    std::vector<uint8_t> has;
+    if (fast->GetInformationBatch(at, &info, &has))
+      for (size_t k = 0; k < K; ++k)
+        if (out[k].accepted && has[k]) { out[k].has_information = true; out[k].information = MakeEdgeInformation(info[k], *information_options); }
   }
   return out;
 }

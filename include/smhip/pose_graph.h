@@ -63,14 +63,13 @@
 #include <vector>
 
 #include "smhip/back_end.h"
+#include "smhip/edge_information.h"
 #include "smhip/submap.h"
 
 namespace smhip {
 namespace back_end {
 
-using Sigmas = std::array<double, 6>;                                      // rotation first, as gtsam::Pose3
-inline Sigmas FrameMatchSigmas() { return {0.1, 0.1, 0.1, 0.15, 0.15, 0.15}; }    // frame_match_noise_model_, :80-81
-inline Sigmas LoopClosureSigmas() { return {0.1, 0.1, 0.1, 0.15, 0.15, 0.15}; }   // loop_closure_noise_model_, :82-83
+// (Sigmas, FrameMatchSigmas() and LoopClosureSigmas() -- :80-83 -- live in smhip/edge_information.h, which floors on them)
 inline std::array<double, 3> GpsSigmas() { return {0.15, 0.15, 0.15}; }            // gps_noise_model_, :79
 inline Sigmas GpsCoordPriorSigmas() { return {0.1, 0.1, 0.2, 1.0, 1.0, 1.0}; }     // :340-343
 inline Sigmas AloneGpsCoordPriorSigmas() { return {0.2, 0.2, 1.57, 20.0, 20.0, 20.0}; }   // :306-309
@@ -84,7 +83,11 @@ inline Sigmas OdomCalibPriorSigmas() { return {0.5, 0.5, 1.5, 0.1, 0.1, 0.1}; } 
 // ODOM_CALIB_KEY) is kept apart likewise and emitted after the chain vertices and before the frame vertex, only when it is set.
 class PoseGraph {
  public:
-  struct Edge { int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };   // huber: the factor's Huber threshold, 0 = none
+  struct Edge {
+    int i = 0, j = 0; Matrix4d transform = Matrix4d::Identity(); Sigmas sigmas = FrameMatchSigmas(); double huber = 0;   // huber: the factor's Huber threshold, 0 = none
+    bool has_information = false;                      // the edge is whitened by sqrt_information (row-major 6x6 L, information L^T L) in place
+    std::array<double, 36> sqrt_information{};         // of its sigmas (include/smhip.h, "Edge information"); the sigmas stay valid and unread
+  };
   // a PRIOR on vertex `index` around `pose`, a POINT between the frame vertex and vertex `index`, or a HANDEYE between vertex `index`
   // and the calibration vertex measured as `pose`
   struct Factor { int kind = SMHIP_POSE_GRAPH_FACTOR_PRIOR; int index = 0; Matrix4d pose = Matrix4d::Identity(); double lever[3] = {0, 0, 0}, point[3] = {0, 0, 0}; Sigmas sigmas = FrameMatchSigmas(); double huber = 0; };
@@ -100,6 +103,30 @@ class PoseGraph {
   void AddLoopCloseEdge(int target_index, int source_index, const Matrix4d& transform_tgt_to_src, const Sigmas& loop_close_noise = LoopClosureSigmas(),
                         double huber = 0.0) {
     AddEdge(target_index, source_index, transform_tgt_to_src, loop_close_noise, huber);
+  }
+  // The same two with the matcher's own information on the edge (smhip/edge_information.h): the sigmas stay the reference's, unread
+  void AddVertex(int index, const Matrix4d& pose, const Matrix4d& transform_from_last_pose, const EdgeInformation& information) {
+    AddVertex(index, pose, transform_from_last_pose, FrameMatchSigmas());
+    if (index > 0) SetInformation(&edges_.back(), information);
+  }
+  void AddLoopCloseEdge(int target_index, int source_index, const Matrix4d& transform_tgt_to_src, const EdgeInformation& information, double huber = 0.0) {
+    AddEdge(target_index, source_index, transform_tgt_to_src, LoopClosureSigmas(), huber);
+    SetInformation(&edges_.back(), information);
+  }
+  // some edge carries a square-root information
+  bool HasInformation() const {
+    for (const Edge& e : edges_) if (e.has_information) return true;
+    return false;
+  }
+  // info_index and sqrt_info of smhip_pose_graph_optimize_info in the order of FlattenFactors' factors: only BETWEENs carry one
+  void FlattenInformation(std::vector<int32_t>* info_index, std::vector<double>* sqrt_info) const {
+    info_index->assign(static_cast<size_t>(FactorCount()), -1);
+    sqrt_info->clear();
+    for (size_t k = 0; k < edges_.size(); ++k) {
+      if (!edges_[k].has_information) continue;
+      (*info_index)[k] = static_cast<int32_t>(sqrt_info->size() / 36);
+      sqrt_info->insert(sqrt_info->end(), edges_[k].sqrt_information.begin(), edges_[k].sqrt_information.end());
+    }
   }
   // A vertex that is neither constant nor tied to the previous one: what SolveGpsCorrdAlone's own graph is made of (:314-320)
   int AddLooseVertex(const Matrix4d& pose) {
@@ -185,10 +212,27 @@ class PoseGraph {
   }
   // One device solve from the current poses, which it replaces.  false (poses unchanged, the reason on stderr) when refused.  The
   // robust entry is called only when some threshold is not zero: without one the calls are those made before thresholds existed.
-  // Likewise the calib entry only when a HANDEYE factor exists.
+  // Likewise the calib entry only when a HANDEYE factor exists, and the info entry only when some edge carries an information.
   bool Optimize(smhip_handle handle, smhip_pose_graph_stats* stats = nullptr, const smhip_pose_graph_options* options = nullptr) {
     SMHIP_CHECK(handle != nullptr, "PoseGraph::Optimize needs a device handle");
     if (poses_.empty()) return true;
+    if (HasInformation()) {
+      std::vector<double> poses, data, sigmas, huber, sqrt_info;
+      std::vector<int32_t> ij, info_index;
+      std::vector<uint8_t> fixed, kinds;
+      FlattenFactors(&poses, &fixed, &kinds, &ij, &data, &sigmas);
+      if (HasHuber()) FlattenHuber(&huber);
+      FlattenInformation(&info_index, &sqrt_info);
+      const smhip_status s = smhip_pose_graph_optimize_info(handle, NodeCount(), poses.data(), fixed.data(), static_cast<int>(kinds.size()), kinds.data(),
+                                                            ij.data(), data.data(), sigmas.data(), huber.empty() ? nullptr : huber.data(), info_index.data(),
+                                                            sqrt_info.data(), options, stats);
+      if (s != SMHIP_OK) {
+        std::fprintf(stderr, "[ERROR] smhip_pose_graph_optimize_info: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+        return false;
+      }
+      SetFlatNodePoses(poses);
+      return true;
+    }
     if (HandEyeFactorCount() > 0) {
       std::vector<double> poses, data, sigmas, huber;
       std::vector<int32_t> ij;
@@ -338,6 +382,11 @@ class PoseGraph {
     e.i = i; e.j = j; e.transform = transform; e.sigmas = sigmas; e.huber = huber;
     edges_.push_back(e);
   }
+  static void SetInformation(Edge* e, const EdgeInformation& information) {
+    for (double v : information.sqrt_information) SMHIP_CHECK(std::isfinite(v), "a square-root information is finite");
+    e->has_information = true;
+    e->sqrt_information = information.sqrt_information;
+  }
   std::vector<Matrix4d> poses_;
   std::vector<uint8_t> fixed_;
   std::vector<Edge> edges_;
@@ -363,6 +412,9 @@ struct IsamOptimizerOptions {
   double loop_closure_huber = 0.0;    // the Huber threshold of every loop edge, and of nothing else.  0: none, the reference's
                                       // IsamOptimizer (:82-83); 1.0: the multi-trajectory optimiser's loop_closure_model_
                                       // (multi_trajectory_optimizer.cc:68-81)
+  bool use_edge_information = false;  // (not in the reference) a chain edge handed in with its EdgeInformation, and a loop edge the detector
+                                      // measured one for (LoopDetectorSettings::edge_information), enter the graph with it in place of
+                                      // the fixed sigmas; false: every edge as before, whatever it carries
 };
 
 // One loop edge after the last solve: s_f and w_f of include/smhip.h, "Robust factors" (weight 1: taken at full weight)
@@ -409,16 +461,22 @@ class IsamOptimizer {
   // detector reads again on its next AddFrame.  false when a solve failed (the reason on stderr): the vertex and its factors stay in
   // the graph, every frame keeps the pose it had, and a later AddFrame or RunFinalOptimazation solves the whole graph again.
   bool AddFrame(const std::shared_ptr<LoopFrame>& frame, const Matrix4d& transform_from_last) {
+    return AddFrame(frame, transform_from_last, nullptr);
+  }
+  // ... with the information of the match that gave transform_from_last (null: none); used when options.use_edge_information
+  bool AddFrame(const std::shared_ptr<LoopFrame>& frame, const Matrix4d& transform_from_last, const EdgeInformation* chain_information) {
     SMHIP_CHECK(frame != nullptr, "CHECK(frame)");
     const DetectResult result = loop_detector_->AddFrame(frame, true);                          // :199
-    return AddDetected(frame, transform_from_last, result);
+    return AddDetected(frame, transform_from_last, result, chain_information);
   }
   // TEST HOOK: the part of AddFrame after the detector (:200-292), for a detector result made by hand
-  bool AddDetected(const std::shared_ptr<LoopFrame>& frame, const Matrix4d& transform_from_last, const DetectResult& result) {
+  bool AddDetected(const std::shared_ptr<LoopFrame>& frame, const Matrix4d& transform_from_last, const DetectResult& result,
+                   const EdgeInformation* chain_information = nullptr) {
     const int frame_index = graph_.VertexCount();
     SMHIP_CHECK(frame_index == result.current_frame_index, "CHECK_EQ(frame_index, result.current_frame_index)");   // :202
     frames_.push_back(frame);
-    graph_.AddVertex(frame_index, frame->global_pose, transform_from_last, FrameMatchSigmas());  // :206-207
+    if (options_.use_edge_information && chain_information) graph_.AddVertex(frame_index, frame->global_pose, transform_from_last, *chain_information);
+    else graph_.AddVertex(frame_index, frame->global_pose, transform_from_last, FrameMatchSigmas());  // :206-207
     if (frame_index == 0 && options_.use_odom) {                                                // :153-162
       const Matrix4d calib = RigidInverse(tf_odom_lidar_);
       if (options_.odom_extrinsic_calib) graph_.SetCalibVertex(calib, OdomCalibPriorSigmas());
@@ -432,7 +490,11 @@ class IsamOptimizer {
     if (result.close_succeed) {                                                                 // :227-236
       for (const LoopEdge& edge : result.edges) {
         loop_edge_at_.push_back(static_cast<int>(graph_.Edges().size()));
-        graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, LoopClosureSigmas(), options_.loop_closure_huber);
+        if (options_.use_edge_information && edge.has_information) loop_edges_with_information_.push_back(edge);
+        if (options_.use_edge_information && edge.has_information)
+          graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, edge.information, options_.loop_closure_huber);
+        else
+          graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, LoopClosureSigmas(), options_.loop_closure_huber);
         ++loop_edges_;
       }
       ok = Update() && ok;
@@ -507,6 +569,8 @@ class IsamOptimizer {
     }
     return out;
   }
+  // the loop edges that entered the graph with their own information (use_edge_information), in the order added
+  const std::vector<LoopEdge>& LoopEdgesWithInformation() const { return loop_edges_with_information_; }
   int SolveCount() const { return solves_; }
   const smhip_pose_graph_stats& LastStats() const { return last_stats_; }
 
@@ -570,6 +634,7 @@ class IsamOptimizer {
   Solver solver_;
   Reporter reporter_;
   std::vector<int> loop_edge_at_;                   // the loop edges' places in graph_.Edges()
+  std::vector<LoopEdge> loop_edges_with_information_;
   bool main_solved_ = false;                        // the last solve was one of graph_, as it is now, and it succeeded
   PoseGraph graph_;
   std::vector<std::shared_ptr<LoopFrame>> frames_;

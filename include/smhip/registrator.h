@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../smhip.h"
+#include "align_information.h"
 
 #if defined(SMHIP_REGISTRATOR_THROW_ON_CHECK)
 #include <stdexcept>
@@ -347,6 +348,22 @@ class IcpFastHip : public Interface {
   }
   const smhip_icp_stats& LastStats() const { return stats_; }
 
+  // The 6x6 point-to-plane information of the resident pair at T (smhip_icp_information_at with this matcher's dist_outlier_ratio;
+  // smhip/edge_information.h turns it into a pose-graph edge).  Nothing is computed unless asked: one matching pass and one pass
+  // over the source per call.  false (the reason on stderr, *out untouched) without a pair or when the pair has no finite
+  // correspondence at T.
+  bool GetInformation(const Matrix4d& T, AlignInformation* out) {
+    SMHIP_CHECK(out != nullptr, "GetInformation: out");
+    if (!source_ok_ || !target_ok_ || !EnsureHandle(0, 0, true, true)) {
+      std::fprintf(stderr, "[ERROR] IcpFastHip::GetInformation: no source / target on the device\n");
+      return false;
+    }
+    smhip_icp_information info;
+    if (!Ok(smhip_icp_information_at(arena_.handle, 0, T.data(), options_.dist_outlier_ratio, &info), "smhip_icp_information_at")) return false;
+    *out = FromAbi(info);
+    return true;
+  }
+
   // Device-resident target preparation (the backend's own additions; the reference has the caller run
   // EigenPointCloud::CalculateNormals on the host, map_builder.cc:286,389, before SetInputTarget).
   // The raw cloud is uploaded and its normals are computed on the GPU (csrc/prep_normals.hip); returns the number of
@@ -435,6 +452,7 @@ class IcpFastHip : public Interface {
     SMHIP_CHECK(K > 0 && targets.size() == sources.size() && guesses.size() == sources.size() && results && scores, "AlignBatch: sizes");
     results->assign(guesses.begin(), guesses.end());
     scores->assign(K, 0.0);
+    batch_pairs_ = 0;
     if (RefuseInnerCompensation()) return false;
     int ns = 1, nt = 1;
     for (int k = 0; k < K; ++k) {
@@ -466,6 +484,33 @@ class IcpFastHip : public Interface {
     }
     for (int k = 0; k < K; ++k) std::memcpy((*results)[k].data(), &r[16 * static_cast<size_t>(k)], sizeof(double) * 16);
     if (stats) *stats = st;
+    batch_pairs_ = K;
+    return true;
+  }
+  // GetInformation for the pairs the last successful AlignBatch left in its slots, pair k at Ts[k], in ONE call
+  // (smhip_icp_information_range).  has[k]: pair k had a finite correspondence at Ts[k] and out[k] is its information.  false (the
+  // reason on stderr) when no batch is resident, the sizes differ or the device refused the call.
+  bool GetInformationBatch(const std::vector<Matrix4d>& Ts, std::vector<AlignInformation>* out, std::vector<uint8_t>* has) {
+    SMHIP_CHECK(out != nullptr && has != nullptr, "GetInformationBatch: out");
+    const int K = static_cast<int>(Ts.size());
+    out->assign(Ts.size(), AlignInformation());
+    has->assign(Ts.size(), 0);
+    if (K == 0 || K != batch_pairs_ || !batch_arena_.handle) {
+      std::fprintf(stderr, "[ERROR] IcpFastHip::GetInformationBatch: %d transforms for the %d pairs of the last AlignBatch\n", K, batch_pairs_);
+      return false;
+    }
+    std::vector<double> t(16 * Ts.size());
+    for (size_t k = 0; k < Ts.size(); ++k) std::memcpy(&t[16 * k], Ts[k].data(), sizeof(double) * 16);
+    std::vector<smhip_icp_information> info(Ts.size());
+    const smhip_status s = smhip_icp_information_range(batch_arena_.handle, 0, K, t.data(), options_.dist_outlier_ratio, info.data());
+    bool pair_failed = false;
+    for (const smhip_icp_information& i : info) pair_failed = pair_failed || i.status != SMHIP_OK;
+    if (s != SMHIP_OK && !pair_failed) {
+      std::fprintf(stderr, "[ERROR] smhip_icp_information_range: %s (%s)\n", smhip_status_string(s), smhip_last_error(batch_arena_.handle));
+      return false;
+    }
+    for (size_t k = 0; k < Ts.size(); ++k)
+      if (info[k].status == SMHIP_OK) { (*out)[k] = FromAbi(info[k]); (*has)[k] = 1; }
     return true;
   }
 
@@ -562,6 +607,7 @@ class IcpFastHip : public Interface {
   int32_t max_points_;
   DeviceArena arena_;
   DeviceArena batch_arena_;                    // AlignBatch's K-slot handle
+  int batch_pairs_ = 0;                        // pairs the last successful AlignBatch left resident in it
   std::shared_ptr<const std::vector<data::InnerPointType>> scan_;   // LoadScan's rows (to send up again after a re-size)
   bool scan_resident_ = false;                 // the filter workspace holds them
   bool compensated_source_ = false;            // the source is scan_ de-skewed by compensated_delta_, and no host copy exists
@@ -842,7 +888,7 @@ class IcpPointMatcherHip : public Interface {
     if (smhip_sample_source(h, 1, 0, prob_, static_cast<uint32_t>(seed_), &n_sampled) != SMHIP_OK ||
         smhip_prepare_target_from_target(h, 1, 0, &n_target) != SMHIP_OK) return Fail(guess, result);
     smhip_icp_options o; smhip_icp_default_options(&o);
-    o.max_iteration = 150; o.dist_outlier_ratio = 0.7f; o.early_exit = 1;           // :196-224
+    o.max_iteration = 150; o.dist_outlier_ratio = kDistOutlierRatio; o.early_exit = 1;   // :196-224
     o.nn_mode = nn_mode_; o.nn_epsilon = nn_epsilon_;                               // KDTreeMatcher knn 1, epsilon 3.16 (:186-191) when nn_mode = 2
     if (smhip_icp_set_options(h, &o) != SMHIP_OK) return Fail(guess, result);
     double score = 0.0;
@@ -853,6 +899,26 @@ class IcpPointMatcherHip : public Interface {
     return this->final_score_ >= 0.6;                                // :145-148
   }
   const smhip_icp_stats& LastStats() const { return stats_; }
+
+  static constexpr float kDistOutlierRatio = 0.7f;   // the chain's TrimmedDistOutlierFilter ratio (:196-224), Align's and GetInformation's
+  // The information of the clouds the last Align matched, at T: the ICP pair (slot 0: the sampled reading on CalculateNormals of the
+  // reference -- the score pair's raw reference has no normals), trimmed at the chain's ratio.  Nothing is computed unless asked.
+  // false (the reason on stderr, *out untouched) before an Align or when the pair has no finite correspondence at T.
+  bool GetInformation(const Matrix4d& T, AlignInformation* out) {
+    SMHIP_CHECK(out != nullptr, "GetInformation: out");
+    if (!arena_.handle || !reading_on_device_ || !reference_on_device_) {
+      std::fprintf(stderr, "[ERROR] IcpPointMatcherHip::GetInformation: no Align has matched a pair on the device\n");
+      return false;
+    }
+    smhip_icp_information info;
+    const smhip_status s = smhip_icp_information_at(arena_.handle, 0, T.data(), kDistOutlierRatio, &info);
+    if (s != SMHIP_OK) {
+      std::fprintf(stderr, "[ERROR] smhip_icp_information_at: %s (%s)\n", smhip_status_string(s), smhip_last_error(arena_.handle));
+      return false;
+    }
+    *out = FromAbi(info);
+    return true;
+  }
 
   // K independent (reading, reference) pairs through 2 K pair slots of a handle kept between calls: slots [0, K) hold the
   // ICP pairs, slots [K, 2 K) the score pairs; ONE launch sequence runs the K 150-iteration loops together.

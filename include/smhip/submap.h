@@ -200,11 +200,13 @@ inline std::vector<SubmapPair> ConsecutivePairs(const std::vector<std::shared_pt
 
 // MapBuilder::SubmapPairMatch for every pair of consecutive submaps, as ONE batch on `matcher` (back_end::SubmapPairMatchBatch):
 // result k belongs to ConsecutivePairs(submaps)[k]; transform_to_next is what submap `target` would keep
-// (SetMatchedTransformedToNext: the match when its score reaches accepted_min_score, else the guess, :436-444).
+// (SetMatchedTransformedToNext: the match when its score reaches accepted_min_score, else the guess, :436-444).  With
+// information_options every accepted pair's result also carries the information of its match (smhip/edge_information.h).
 inline std::vector<back_end::SubmapPairMatchResult> ConnectSubmaps(const registrator::MatcherOptions& options,
                                                                    const std::shared_ptr<registrator::Interface>& matcher,
                                                                    const std::vector<std::shared_ptr<Submap>>& submaps,
-                                                                   const std::shared_ptr<DeviceContext>& context = nullptr) {
+                                                                   const std::shared_ptr<DeviceContext>& context = nullptr,
+                                                                   const back_end::EdgeInformationOptions* information_options = nullptr) {
   std::vector<back_end::SubmapPairJob> jobs;
   for (const SubmapPair& p : ConsecutivePairs(submaps)) {
     back_end::SubmapPairJob j;
@@ -214,7 +216,7 @@ inline std::vector<back_end::SubmapPairMatchResult> ConnectSubmaps(const registr
     j.target_first_frame_pose = submaps[static_cast<size_t>(p.target)]->FirstFramePose();
     jobs.push_back(j);
   }
-  return back_end::SubmapPairMatchBatch(options, matcher, jobs);
+  return back_end::SubmapPairMatchBatch(options, matcher, jobs, information_options);
 }
 
 }  // namespace builder

@@ -28,6 +28,11 @@ class IcpStats(ctypes.Structure):
                 ("refined_iterations", ctypes.c_int32), ("searched_queries", ctypes.c_int32), ("fused_iterations", ctypes.c_int32)]
 
 
+class IcpInformation(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_double * 36), ("sum_r2", ctypes.c_double), ("limit_d2", ctypes.c_double),
+                ("kept", ctypes.c_int32), ("n_finite", ctypes.c_int32), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class IcpProfile(ctypes.Structure):
     _fields_ = [("ms_prepare", ctypes.c_double), ("ms_find_closests", ctypes.c_double),
                 ("ms_error_elements", ctypes.c_double), ("ms_solve", ctypes.c_double),
@@ -135,6 +140,9 @@ SIGNATURES = {
     "smhip_icp_align_range": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                              ctypes.POINTER(IcpStats)]),
     "smhip_icp_trimmed_score": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_float, c_double_p, c_int32_p]),
+    "smhip_icp_information_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_float, ctypes.POINTER(IcpInformation)]),
+    "smhip_icp_information_range": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_float,
+                                                   ctypes.POINTER(IcpInformation)]),
     "smhip_prepare_target_from_target": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p]),
     "smhip_sample_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, c_int32_p]),
     "smhip_set_target_cache": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -227,6 +235,12 @@ SIGNATURES = {
     "smhip_pose_graph_optimize_calib": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
                                                        ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_double_p, c_double_p, c_double_p,
                                                        ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
+    "smhip_pose_graph_plan_info": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
+                                                  c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_int32_p, c_int32_p,
+                                                  ctypes.c_char_p, ctypes.c_int]),
+    "smhip_pose_graph_optimize_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p,
+                                                      ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -12,6 +12,7 @@
 // POINT (include/smhip.h, "Factor kinds"; tests/pose_graph_gps_ref.py) or a HANDEYE ("Odometry calibration factor";
 // tests/pose_graph_calib_ref.py); whatever its kind it has an index pair, 12 doubles of
 // data, 6 inverse sigmas and 6 rows of whitened A, B and residual, so only edge_cost and linearize_edge look at the kind.
+// A BETWEEN may carry a full 6x6 square-root information L in place of its six inverse sigmas (Dev::info_index, Dev::sqrt_info).
 // Any factor may carry a Huber threshold (include/smhip.h, "Robust factors"; tests/pose_graph_robust_ref.py): the same two
 // functions turn s_f^2 into the cost term and the rows into the weighted rows, and nothing else of the loop knows.
 #pragma once
@@ -56,6 +57,8 @@ struct Dev {
   const double* huber = nullptr;          // 1: the Huber threshold k_f, 0 = none; nullptr: no threshold anywhere ("Robust factors")
   double* wgt = nullptr;                  // 1: the weight w_f of the last linearisation (1, or k_f / s_f); nullptr: not kept
   double *rep_s = nullptr, *rep_c = nullptr;   // 1: the report's s_f and cost term (its weight goes to wgt)
+  const int32_t* info_index = nullptr;    // 1: >= 0: the BETWEEN factor is whitened by the 6x6 L at sqrt_info + 36 * index in place of its sinv (rw = L e,
+  const double* sqrt_info = nullptr;      //    A_w = L A, B_w = L B, s_f^2 = |L e|^2; DESIGN.md section 6, "Edge information"); both nullptr: no factor has one
   // probe
   const double* v = nullptr;
   double* minv = nullptr;
@@ -163,6 +166,12 @@ PG_HD void handeye_error(const double* X, const double* T, const double* Z, doub
   log_so3(RE, e);
 }
 
+// the factor's 6x6 L (row-major), or nullptr: whitened by its six inverse sigmas
+PG_HD const double* edge_sqrt_info(const Dev& d, int e) {
+  if (!d.info_index || d.info_index[e] < 0) return nullptr;
+  return d.sqrt_info + 36 * (size_t)d.info_index[e];
+}
+
 // A PRIOR on node i around P is the BETWEEN from a constant node at P measured as the identity: the same residual, and that
 // factor's B is the PRIOR's only Jacobian.
 PG_HD double edge_norm2(const Dev& d, const double* X, int e) {
@@ -188,6 +197,14 @@ PG_HD double edge_norm2(const Dev& d, const double* X, int e) {
   const bool prior = kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR;
   double err[6], Rij[9], tij[3], RE[9];
   edge_error(prior ? Z : Xi, Xj, prior ? eye : Z, err, Rij, tij, RE);
+  if (const double* L = prior ? nullptr : edge_sqrt_info(d, e)) {
+    for (int a = 0; a < 6; ++a) {
+      double w = 0.0;
+      for (int k = 0; k < 6; ++k) w += L[6 * a + k] * err[k];
+      s += w * w;
+    }
+    return s;
+  }
   for (int a = 0; a < 6; ++a) { const double w = err[a] * sinv[a]; s += w * w; }
   return s;
 }
@@ -272,6 +289,9 @@ PG_HD void linearize_edge_plain(const Dev& d, const double* X, int e) {
   const double eye[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
   const bool prior = kind == SMHIP_POSE_GRAPH_FACTOR_PRIOR;
   if (prior) { Xi = Z; Z = eye; double* t = A; A = B; B = t; }                  // (the constant twin's Jacobian is dropped below)
+  const double* L = prior ? nullptr : edge_sqrt_info(d, e);
+  const double ones[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
+  if (L) sinv = ones;                                                           // the plain rows first (times one: exact), then L times them
   double err[6], Rij[9], tij[3], RE[9], J[9];
   edge_error(Xi, Xj, Z, err, Rij, tij, RE);
   jr_inv(err, J);
@@ -289,6 +309,21 @@ PG_HD void linearize_edge_plain(const Dev& d, const double* X, int e) {
       B[6 * (3 + a) + 3 + b] = v * RE[3 * a + b];                                                                        // Rz^T Rij
     }
   if (prior) for (int k = 0; k < 36; ++k) A[k] = 0.0;
+  if (L) {
+    double LA[36], LB[36];
+    for (int a = 0; a < 6; ++a) {
+      double w = 0.0;
+      for (int k = 0; k < 6; ++k) w += L[6 * a + k] * err[k];
+      d.rw[6 * (size_t)e + a] = w;
+      for (int b = 0; b < 6; ++b) {
+        double sa = 0.0, sb = 0.0;
+        for (int k = 0; k < 6; ++k) { sa += L[6 * a + k] * A[6 * k + b]; sb += L[6 * a + k] * B[6 * k + b]; }
+        LA[6 * a + b] = sa; LB[6 * a + b] = sb;
+      }
+    }
+    for (int k = 0; k < 36; ++k) { A[k] = LA[k]; B[k] = LB[k]; }
+    return;
+  }
   for (int a = 0; a < 6; ++a) d.rw[6 * (size_t)e + a] = err[a] * sinv[a];
 }
 

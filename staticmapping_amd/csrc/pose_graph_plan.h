@@ -147,6 +147,54 @@ inline smhip_status check_and_plan_calib(bool calib, int n_nodes, const double* 
   return SMHIP_OK;
 }
 
+// nullptr, or what is wrong with a row-major 6x6 square-root information: a non-finite entry, or singular -- the smallest pivot of
+// an LU with partial pivoting at or below 1e-12 times the largest entry
+inline const char* sqrt_info_problem(const double* L) {
+  double a[36], big = 0.0;
+  for (int k = 0; k < 36; ++k) {
+    if (!std::isfinite(L[k])) return "has an entry that is not finite";
+    a[k] = L[k];
+    big = std::fmax(big, std::fabs(L[k]));
+  }
+  for (int c = 0; c < 6; ++c) {
+    int p = c;
+    for (int r = c + 1; r < 6; ++r) if (std::fabs(a[6 * r + c]) > std::fabs(a[6 * p + c])) p = r;
+    if (p != c) for (int k = 0; k < 6; ++k) { const double t = a[6 * c + k]; a[6 * c + k] = a[6 * p + k]; a[6 * p + k] = t; }
+    const double piv = a[6 * c + c];
+    if (!(std::fabs(piv) > 1.0e-12 * big)) return "is singular";
+    for (int r = c + 1; r < 6; ++r) {
+      const double f = a[6 * r + c] / piv;
+      for (int k = c; k < 6; ++k) a[6 * r + k] -= f * a[6 * c + k];
+    }
+  }
+  return nullptr;
+}
+
+// check_and_plan_calib(true, ...), then the square-root informations: info_index one per factor (-1 = its sigmas, else an entry of
+// sqrt_info: 36 doubles, row-major; an entry's index is below the factor count), nullptr = none.  *n_info: entries read.
+inline smhip_status check_and_plan_info(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                        const double* data, const double* sigmas, const double* huber, const int32_t* info_index, const double* sqrt_info,
+                                        Plan* plan, int* n_info, std::string* why) {
+  Plan made;
+  if (const smhip_status s = check_and_plan_calib(true, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &made, why)) return s;
+  auto refuse = [&](const std::string& text) { if (why) *why = "pose graph: " + text; return SMHIP_ERR_INVALID_ARGUMENT; };
+  int entries = 0;
+  for (int e = 0; info_index && e < n_factors; ++e) {
+    const int at = info_index[e];
+    if (at == -1) continue;
+    const std::string name = "edge " + std::to_string(e);
+    if (at < -1 || at >= n_factors) return refuse(name + " has a square-root information index out of range");
+    if (!sqrt_info) return refuse("null pointer");
+    if ((kinds ? kinds[e] : SMHIP_POSE_GRAPH_FACTOR_BETWEEN) != SMHIP_POSE_GRAPH_FACTOR_BETWEEN)
+      return refuse(name + " carries a square-root information and is no BETWEEN");
+    if (const char* p = sqrt_info_problem(sqrt_info + 36 * (size_t)at)) return refuse(name + "'s square-root information " + p);
+    entries = at + 1 > entries ? at + 1 : entries;
+  }
+  if (plan) *plan = made;
+  if (n_info) *n_info = entries;
+  return SMHIP_OK;
+}
+
 inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
                                           const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
   return check_and_plan_calib(false, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, plan, why);

@@ -174,6 +174,15 @@ Args Parse(int argc, char** argv) {
       a.loop_huber_given = true;
     }
     else if (k == "--loop-report") a.loop_report = val();
+    else if (k == "--edge-information") { a.edge_information = std::atoi(val().c_str()) != 0; a.edge_information_given = true; }
+    else if (k == "--edge-information-scale") {
+      const std::string text = val();
+      char* end = nullptr;
+      a.edge_information_scale = std::strtod(text.c_str(), &end);
+      if (text.empty() || *end != '\0') a.edge_information_scale = std::nan("");      // (refused below)
+      a.edge_information_scale_given = true;
+    }
+    else if (k == "--edge-report") a.edge_report = val();
     else if (k == "--gps-enu") a.gps_enu = val();
     else if (k == "--gps-lever") { if (std::sscanf(val().c_str(), "%lf,%lf,%lf", &a.gps_lever[0], &a.gps_lever[1], &a.gps_lever[2]) != 3) Die("--gps-lever takes x,y,z"); }
     else if (k == "--gps-init-num") a.gps_init_num = std::atoi(val().c_str());
@@ -222,6 +231,8 @@ Args Parse(int argc, char** argv) {
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
              "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75] "
              "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)]\n"
+             "  edge information (with --close-loops): [--edge-information 1 (scan-match edges weighted by the matcher's own 6x6 information)] "
+             "[--edge-information-scale 1] [--edge-report FILE (a line per edge: i j chain|loop kept residual_sigma strength[6] weakest[6])]\n"
              "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
              "[--gps-init-num 25] [--gps-sample-step 1] [--gps-init-angle 1.6] [--gps-output-enu (the poses in the ENU frame)]\n"
              "  odometry (with --close-loops): [--odom odom.txt (a line per scan: 12 numbers, the odometer's pose as a row-major 3x4, nan = no reading)] "
@@ -256,6 +267,10 @@ Args Parse(int argc, char** argv) {
   if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
   if (a.loop_huber_given && a.close_loops.empty() && !a.Join()) Die("--loop-huber needs --close-loops");
   if (!a.loop_report.empty() && a.close_loops.empty() && !a.Join()) Die("--loop-report needs --close-loops");
+  if ((a.edge_information_given || a.edge_information_scale_given || !a.edge_report.empty()) && a.close_loops.empty())
+    Die("--edge-information, --edge-information-scale and --edge-report need --close-loops");
+  if ((a.edge_information_scale_given || !a.edge_report.empty()) && !a.edge_information) Die("--edge-information-scale and --edge-report need --edge-information 1");
+  if (!std::isfinite(a.edge_information_scale) || !(a.edge_information_scale > 0.0)) Die("bad edge setting (--edge-information-scale finite and > 0)");
   if (a.gps_output_enu && a.gps_enu.empty()) Die("--gps-output-enu needs --gps-enu");
   if (!a.odom_file.empty() && a.close_loops.empty()) Die("--odom needs --close-loops");
   if ((a.odom_tf_given || a.odom_calib || a.odom_huber_given) && a.odom_file.empty()) Die("--odom-tf, --odom-calib and --odom-huber need --odom");

@@ -61,6 +61,12 @@ struct Args {
   double loop_huber = 0.0;
   bool loop_huber_given = false;
   std::string loop_report;
+  // --edge-information 1: every accepted consecutive-submap match and every loop edge is measured with its own 6x6 information and
+  // enters the graph with it (smhip/edge_information.h); --edge-information-scale S: EdgeInformationOptions::information_scale;
+  // --edge-report FILE: a line per measured edge
+  bool edge_information = false, edge_information_given = false, edge_information_scale_given = false;
+  double edge_information_scale = 1.0;
+  std::string edge_report;
   // --gps-enu FILE: one line per scan in file order, three numbers already in ENU metres, nan = no fix (the geodetic conversion is
   // not restated); the factors' settings (isam_optimizer.h:61-66) and the antenna in the tracking frame
   std::string gps_enu;
@@ -430,6 +436,16 @@ inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files,
 // --odom-huber K is the factors' threshold (default 1).  The JSON line gains "odom_factors" and "odom_tf" (the transform after the
 // final solve, row-major).  --odom without --close-loops, a FILE whose line count is not the scan count or with a line that does not
 // hold 12 numbers, a bad --odom-tf or K: exit 2 before any device work.
+// --edge-information 1 weighs the scan-match edges by their own geometry ("Edge information"): an accepted match
+// against the previous submap is measured at its result (smhip_icp_information_at on the pair as it lies on the device, with the
+// matcher's dist_outlier_ratio) and handed to IsamOptimizer with AddFrame's third argument; the detector measures every loop edge it
+// accepts (LoopDetectorSettings::edge_information); IsamOptimizerOptions::use_edge_information is on.  A match that was not accepted
+// (the edge is the guess) or that has no information keeps the fixed sigmas.  --edge-information-scale S (finite, > 0; default 1) is
+// EdgeInformationOptions::information_scale of both.  --edge-report FILE writes one line per edge that entered the graph with an
+// information, chain edges first, each group in the order added: i j chain|loop kept residual_sigma, the six strengths (ascending),
+// the six components of the weakest direction (rotation first; %.8g) -- the strengths are what a scale is chosen from.  The JSON line
+// gains "edge_informations".  The scale or the report without --edge-information 1, or any of the three without --close-loops: exit 2
+// before any device work.  Without the flag nothing of this runs and every output is what it was.
 // --save-trajectory-map DIR writes, beside all this, the map a later join loads (smhip/trajectory_map.h): DIR/submap_<k>.bin, the cloud
 // of submap k as it was built and matched, read back from the device, and after the final solve DIR/map.xml: one trajectory, the
 // corrected submap poses, and per submap the connections to the next submap and to the source of every accepted loop edge.  Every
@@ -448,7 +464,10 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     int gps_factors = 0; double gps_coord[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // with --gps-enu; row-major
     int downweighted = 0;                                                                             // with --loop-huber
     int odom_factors = 0; double odom_tf[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // with --odom; row-major
+    int edge_informations = 0;                                                                        // with --edge-information
   } res;
+  struct EdgeReportRow { int i, j; bool loop; be::EdgeInformation information; };
+  std::vector<EdgeReportRow> edge_report;
   std::vector<smhip::back_end::LoopEdgeWeight> loop_report;
   std::ofstream out(a.close_loops);
   if (!out) Die("cannot write " + a.close_loops);
@@ -469,11 +488,14 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     const int dlen = smhip_m2dp_length(&mo);
     be::LoopDetectorSettings settings = a.loop;
     settings.device = device;
+    settings.edge_information = a.edge_information;
+    settings.edge_information_options.information_scale = a.edge_information_scale;
     be::IsamOptimizerOptions io;
     io.use_gps = !a.gps_enu.empty();
     io.gps_factor_init_num = a.gps_init_num; io.gps_factor_sample_step = a.gps_sample_step; io.gps_factor_init_angle_rad = a.gps_init_angle;
     io.loop_closure_huber = a.loop_huber;
     io.use_odom = !a.odom_file.empty(); io.odom_extrinsic_calib = a.odom_calib; io.odom_huber = a.odom_huber;
+    io.use_edge_information = a.edge_information;
     be::IsamOptimizer optimizer(io, settings, h);
     if (io.use_odom) optimizer.SetTransformOdomToLidar(bld::Vector6ToTransform(a.odom_tf));   // common::Vector6ToTransform: R = Rz(rz) Ry(ry) Rx(rx)
     {
@@ -515,10 +537,27 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
         }
       }
       Matrix4d from_last = Matrix4d::Identity();
+      be::EdgeInformation chain_information;
+      bool has_chain_information = false;
       if (k > 0) {
         PairMatch pm;
         if (!feed.MatchToPrevious(k, poses, &pm)) { rc = 3; break; }
         std::memcpy(from_last.data(), pm.transform_to_next.data(), sizeof(double) * 16);
+        if (a.edge_information && pm.accepted) {                           // the pair is still on the device: measure it at its result
+          smhip_icp_options o;
+          smhip_icp_default_options(&o);                                   // SetIcpOptions leaves the matcher's dist_outlier_ratio at its default
+          smhip_icp_information info;
+          if (smhip_icp_information_at(h, 0, pm.transform_to_next.data(), o.dist_outlier_ratio, &info) != SMHIP_OK) {
+            std::fprintf(stderr, "smhip_shard: information of submaps %d -> %d: %s\n", k - 1, k, smhip_last_error(h)); rc = 3; break;
+          }
+          if (info.status == SMHIP_OK) {
+            be::EdgeInformationOptions eo;
+            eo.information_scale = a.edge_information_scale;
+            chain_information = be::MakeEdgeInformation(be::FromAbi(info), eo);
+            has_chain_information = true;
+            edge_report.push_back({k - 1, k, false, chain_information});
+          }
+        }
         frame->global_pose = be::Multiply(frames.back()->global_pose, from_last);
       } else {
         frame->global_pose = maps[0]->GlobalPose();
@@ -537,13 +576,17 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
         if (z[15] != 0.0) { frame->has_odom = true; std::memcpy(frame->odom.data(), z.data(), sizeof(double) * 16); }
       }
       frames.push_back(frame);
-      if (!optimizer.AddFrame(frame, from_last)) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
+      if (!(has_chain_information ? optimizer.AddFrame(frame, from_last, &chain_information) : optimizer.AddFrame(frame, from_last))) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
     }
     if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
     if (rc == 0 && (a.loop_huber > 0.0 || !a.loop_report.empty())) {
       loop_report = optimizer.LoopEdgeReport();
       if (static_cast<int>(loop_report.size()) != optimizer.LoopEdgeCount()) { std::fprintf(stderr, "smhip_shard: the loop edges' report was refused\n"); rc = 3; }
       for (const be::LoopEdgeWeight& w : loop_report) res.downweighted += w.weight < 1.0;
+    }
+    if (rc == 0 && a.edge_information) {
+      for (const be::LoopEdge& e : optimizer.LoopEdgesWithInformation()) edge_report.push_back({e.close_pair_index.first, e.close_pair_index.second, true, e.information});
+      res.edge_informations = static_cast<int>(edge_report.size());
     }
     if (rc == 0) {
       res.loop_edges = optimizer.LoopEdgeCount(); res.solves = optimizer.SolveCount();
@@ -601,10 +644,21 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     if (!rep) Die("cannot write " + a.loop_report);
     for (const smhip::back_end::LoopEdgeWeight& w : loop_report) rep << Fmt("%d %d %.8g %.8g\n", w.target, w.source, w.norm, w.weight);
   }
+  if (!a.edge_report.empty()) {
+    std::ofstream rep(a.edge_report);
+    if (!rep) Die("cannot write " + a.edge_report);
+    for (const EdgeReportRow& e : edge_report) {
+      rep << Fmt("%d %d %s %d %.8g", e.i, e.j, e.loop ? "loop" : "chain", e.information.kept, e.information.residual_sigma);
+      for (double v : e.information.strength) rep << Fmt(" %.8g", v);
+      for (double v : e.information.weakest) rep << Fmt(" %.8g", v);
+      rep << "\n";
+    }
+  }
   *fields += Fmt(", \"close_loops_file\": \"%s\", \"loop_submaps\": %d, \"loop_edges\": %d, \"pose_graph_solves\": %d, \"pose_graph_stop_reason\": %d, "
                  "\"pose_graph_final_cost\": %.6g, \"loop_largest_correction_m\": %.4f, \"close_loops_seconds\": %.4f", a.close_loops.c_str(), S,
                  res.loop_edges, res.solves, res.stop_reason, res.final_cost, res.moved_m, Since(t0));
   if (a.loop_huber > 0.0) *fields += Fmt(", \"loop_edges_downweighted\": %d", res.downweighted);
+  if (a.edge_information) *fields += Fmt(", \"edge_informations\": %d", res.edge_informations);
   if (!a.gps_enu.empty()) {
     *fields += Fmt(", \"gps_factors\": %d, \"gps_coord\": [", res.gps_factors);
     for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.gps_coord[q], q == 15 ? "]" : ", ");

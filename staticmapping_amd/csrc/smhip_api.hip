@@ -1296,6 +1296,29 @@ smhip_status smhip_icp_trimmed_score(smhip_handle h, int slot, const double T[16
   return s;
 }
 
+// The same one-iteration pass for the slots [first, first + npairs) with every match exact, for the information unit
+// (smhip_icp_information.hip), which then reads the matches, distances and limits the pass left on the device.  Returns what the
+// align calls return: the first failing pair's status, with every pair's own in stats[k].status.  The caller's options are put
+// back, and the pass teaches the handle nothing about where a batch's searches thin out.
+extern "C++" {
+namespace smhip_host {
+smhip_status trimmed_pass_range(smhip_context* h, int first, int npairs, const double* Ts, float dist_outlier_ratio, smhip_icp_stats* stats) {
+  const smhip_icp_options saved = h->opts;
+  smhip_icp_options o = saved;
+  o.max_iteration = 1; o.early_exit = 0; o.dist_outlier_ratio = dist_outlier_ratio; o.exact_matches = 1;
+  h->opts = o;
+  sync_options(h);
+  smhip_status s = enqueue_range(h, first, npairs, Ts);
+  if (s == SMHIP_OK) s = fetch_range(h, first, npairs, nullptr, nullptr, stats);
+  else for (int p = 0; p < npairs; ++p) stats[p] = smhip_icp_stats{};
+  h->opts = saved;
+  sync_options(h);
+  h->hist_pairs = 0;
+  return s;
+}
+}  // namespace smhip_host
+}
+
 smhip_status smhip_set_target_cache(smhip_handle h, int enable) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   h->target_cache = enable ? 1 : 0;

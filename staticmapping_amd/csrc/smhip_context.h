@@ -98,6 +98,7 @@ struct smhip_context {
   float* d2_pinned = nullptr;
   int32_t* ids_dev = nullptr;    // scratch for exported matches
   float* d2_dev = nullptr;
+  smhip_icp_information* info_dev = nullptr;   // [slots] results of the information unit (smhip_icp_information.hip), allocated on first use
   std::vector<void*> allocs;
   std::string err;
   int last_npairs = 0;
@@ -159,5 +160,6 @@ smhip_status enqueue_prepare_kept(smhip_context* h, int first, int K);
 Half whole_batch(smhip_context* h, int np, int first);
 smhip_status enqueue_find_closests_half(smhip_context* h, const Half& f, int ns_max);
 smhip_status fill_inputs(smhip_context* h, int np, const double* guesses, int* ns_max, int* nt_max, int first = 0);
+smhip_status trimmed_pass_range(smhip_context* h, int first, int npairs, const double* Ts, float dist_outlier_ratio, smhip_icp_stats* stats);
 
 }  // namespace smhip_host

@@ -60,8 +60,8 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_solve(const pg::Dev d) 
 }
 
 // doubles and words of the device state per node / per edge, and of the staging the host fills
-constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6 + 4;      // (+ huber, wgt, rep_s, rep_c)
-constexpr int kNodeI = 2, kEdgeI = 5;           // fixed, csr_off (+1); ij, csr_edge, kind
+constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6 + 4 + 36;      // (+ huber, wgt, rep_s, rep_c; sqrt_info)
+constexpr int kNodeI = 2, kEdgeI = 6;           // fixed, csr_off (+1); ij, csr_edge, kind, info_index
 
 }  // namespace
 
@@ -74,6 +74,7 @@ struct smhip_pose_graph_state {
   pg::Plan plan;
   int last_n = -1, last_m = 0;     // what smhip_pose_graph_last can run again (-1: nothing)
   bool last_huber = false;         // that call uploaded thresholds
+  bool last_info = false;          // ... and square-root informations
 };
 
 namespace {
@@ -97,11 +98,13 @@ smhip_status pg_ensure(smhip_context* h) {
   d.g = take(6 * N); d.x = take(6 * N); d.r = take(6 * N); d.z = take(6 * N); d.p = take(6 * N); d.q = take(6 * N); d.b = take(6 * N);
   d.A = take(36 * M); d.B = take(36 * M); d.rw = take(6 * M); d.u = take(6 * M);
   d.wgt = take(M); d.rep_s = take(M); d.rep_c = take(M);
+  d.sqrt_info = take(36 * M);
   d.out_d = take(pg::kOutDoubles);
   int32_t* q = st->ints;
   auto takei = [&q](size_t count) { int32_t* r = q; q += count; return r; };
   // (uploaded: fixed, csr_off, ij, csr_edge, kind)
   d.fixed = takei(N); d.csr_off = takei(N + 1); d.ij = takei(2 * M); d.csr_edge = takei(2 * M); d.kind = takei(M);
+  d.info_index = takei(M);
   d.out_i = takei(pg::kOutInts);
   st->host_d.resize(12 * N + 12 * M + 6 * M);
   st->host_i.resize(N + (N + 1) + 2 * M + 2 * M + M);
@@ -118,10 +121,12 @@ void pack12(const double* m, double* o) {
 }
 
 smhip_status pg_plan(bool calib, int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij, const double* data,
-                     const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+                     const double* sigmas, const double* huber, int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len,
+                     bool info = false, const int32_t* info_index = nullptr, const double* sqrt_info = nullptr) {
   pg::Plan plan;
   std::string text;
-  const smhip_status s = pg::check_and_plan_calib(calib, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &plan, &text);
+  const smhip_status s = info ? pg::check_and_plan_info(n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, info_index, sqrt_info, &plan, nullptr, &text)
+                              : pg::check_and_plan_calib(calib, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, &plan, &text);
   if (why && why_len > 0) { std::strncpy(why, text.c_str(), (size_t)why_len - 1); why[why_len - 1] = '\0'; }
   if (s) return s;
   if (csr_offsets) std::memcpy(csr_offsets, plan.csr_offsets.data(), sizeof(int32_t) * plan.csr_offsets.size());
@@ -129,17 +134,24 @@ smhip_status pg_plan(bool calib, int n_nodes, const double* poses, const uint8_t
   return SMHIP_OK;
 }
 
-// every optimise entry; calib: HANDEYE factors are accepted (smhip_pose_graph_optimize_calib)
+// every optimise entry; calib: HANDEYE factors are accepted (smhip_pose_graph_optimize_calib); info: the *_info entry, whose BETWEEN
+// factors may carry a 6x6 square-root information (a call in which none does uploads nothing more and launches what *_calib launches)
 smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
                          const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
-                         const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats) {
+                         const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats,
+                         bool info = false, const int32_t* info_index = nullptr, const double* sqrt_info = nullptr) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   smhip_pose_graph_options o;
   smhip_pose_graph_default_options(&o);
   if (opts) o = *opts;
   if (o.max_iterations < 1) { h->err = "pose graph: max_iterations must be at least 1"; return SMHIP_ERR_INVALID_ARGUMENT; }
   pg::Plan plan;
-  if (const smhip_status s = pg::check_and_plan_calib(calib, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, &plan, &h->err)) return s;
+  int n_info = 0;
+  if (info) {
+    if (const smhip_status s = pg::check_and_plan_info(n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, info_index, sqrt_info, &plan, &n_info, &h->err)) return s;
+  } else if (const smhip_status s = pg::check_and_plan_calib(calib, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, &plan, &h->err)) {
+    return s;
+  }
   HIPCHK(h, hipSetDevice(h->device));
   if (const smhip_status s = pg_ensure(h)) return s;
   smhip_pose_graph_state* st = h->pose_graph;
@@ -175,6 +187,13 @@ smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_
   const bool robust = huber != nullptr && n_edges > 0;
   if (robust) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.huber), huber, sizeof(double) * (size_t)n_edges, hipMemcpyHostToDevice, s));
   else d.huber = nullptr;
+  const bool with_info = n_info > 0;
+  if (with_info) {
+    HIPCHK(h, hipMemcpyAsync(const_cast<int32_t*>(d.info_index), info_index, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.sqrt_info), sqrt_info, sizeof(double) * 36 * (size_t)n_info, hipMemcpyHostToDevice, s));
+  } else {
+    d.info_index = nullptr; d.sqrt_info = nullptr;
+  }
   HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.pose0), hd, sizeof(double) * 12 * (size_t)n_nodes, hipMemcpyHostToDevice, s));
   if (n_edges > 0) {
     HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.Z), hd + 12 * N, sizeof(double) * 12 * (size_t)n_edges, hipMemcpyHostToDevice, s));
@@ -193,7 +212,7 @@ smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_
   HIPCHK(h, hipMemcpyAsync(out_d, d.out_d, sizeof(out_d), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(out_i, d.out_i, sizeof(out_i), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  st->last_n = n_nodes; st->last_m = n_edges; st->last_huber = robust;
+  st->last_n = n_nodes; st->last_m = n_edges; st->last_huber = robust; st->last_info = with_info;
   if (stats) {
     stats->initial_cost = out_d[pg::kOutInitial]; stats->final_cost = out_d[pg::kOutFinal]; stats->damping = out_d[pg::kOutLambda];
     stats->stop_reason = out_i[pg::kOutStop]; stats->iterations = out_i[pg::kOutIterations];
@@ -280,6 +299,19 @@ smhip_status smhip_pose_graph_optimize_calib(smhip_handle h, int n_nodes, double
   return pg_optimize(true, h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, opts, stats);
 }
 
+smhip_status smhip_pose_graph_plan_info(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
+                                        const double* data, const double* sigmas, const double* huber, const int32_t* info_index, const double* sqrt_info,
+                                        int32_t* csr_offsets, int32_t* csr_edges, char* why, int why_len) {
+  return pg_plan(true, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, csr_offsets, csr_edges, why, why_len, true, info_index, sqrt_info);
+}
+
+smhip_status smhip_pose_graph_optimize_info(smhip_handle h, int n_nodes, double* poses_inout, const uint8_t* fixed, int n_edges, const uint8_t* kinds,
+                                            const int32_t* edge_ij, const double* edge_Z, const double* edge_sigmas, const double* huber,
+                                            const int32_t* info_index, const double* sqrt_info, const smhip_pose_graph_options* opts,
+                                            smhip_pose_graph_stats* stats) {
+  return pg_optimize(true, h, n_nodes, poses_inout, fixed, n_edges, kinds, edge_ij, edge_Z, edge_sigmas, huber, opts, stats, true, info_index, sqrt_info);
+}
+
 smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, double* residuals, double* A, double* B, double* gradient, const double* v, double* minv_v) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   smhip_pose_graph_state* st = h->pose_graph;
@@ -295,6 +327,7 @@ smhip_status smhip_pose_graph_last(smhip_handle h, int n_nodes, int n_edges, dou
   pg::Dev d = st->dev;
   d.n = n; d.m = m; d.max_it = 0; d.pcg_cap = 0; d.probe = 1;
   if (!st->last_huber) d.huber = nullptr;
+  if (!st->last_info) { d.info_index = nullptr; d.sqrt_info = nullptr; }
   if (v) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(d.v), v, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, s));
   else HIPCHK(h, hipMemsetAsync(const_cast<double*>(d.v), 0, sizeof(double) * 6 * (size_t)n, s));
   hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
@@ -323,6 +356,7 @@ smhip_status smhip_pose_graph_last_robust(smhip_handle h, int n_factors, double*
   pg::Dev d = st->dev;
   d.n = st->last_n; d.m = m; d.max_it = 0; d.pcg_cap = 0; d.probe = 2;
   if (!st->last_huber) d.huber = nullptr;
+  if (!st->last_info) { d.info_index = nullptr; d.sqrt_info = nullptr; }
   hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
   HIPCHK(h, hipGetLastError());
   if (norm) HIPCHK(h, hipMemcpyAsync(norm, d.rep_s, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));

@@ -239,6 +239,27 @@ class IcpFastHip:
     def synchronize(self):
         self._check(self._lib.smhip_synchronize(self._h))
 
+    # -- the information of an alignment (smhip_icp_information_at / _range) ----
+    @staticmethod
+    def _information_dict(o):
+        return dict(H=np.array(o.H, dtype=np.float64).reshape(6, 6), sum_r2=o.sum_r2, limit_d2=o.limit_d2, kept=o.kept,
+                    n_finite=o.n_finite, status=o.status)
+
+    def information(self, T, ratio: float = 0.7, slot: int = 0) -> dict:
+        """The 6x6 point-to-plane information of the slot's pair at T (source -> target): H [6, 6] in the pose graph's tangent
+        (rotation first), sum_r2, limit_d2, kept, n_finite, status."""
+        return self.information_range(slot, [T], ratio)[0]
+
+    def information_range(self, first_slot: int, Ts, ratio: float = 0.7):
+        """The same for the slots first_slot .. first_slot + len(Ts) - 1 in one call: a list of dicts.  A pair without a finite
+        correspondence keeps its status in its dict (H zero); the error is raised for it as the align calls raise it."""
+        g = self._pack_guesses(len(Ts), Ts)
+        out = (_capi.IcpInformation * len(Ts))()
+        st = self._lib.smhip_icp_information_range(self._h, first_slot, len(Ts), g.ctypes.data_as(_capi.c_double_p), ratio, out)
+        self.last_information = [self._information_dict(o) for o in out]
+        self._check(st)
+        return self.last_information
+
     # -- introspection ---------------------------------------------------
     def get_matches(self, n: int, slot: int = 0):
         ids = np.zeros(n, dtype=np.int32)

@@ -220,6 +220,69 @@ def optimize_calib(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, hub
     return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
 
 
+def _info(sqrt_information, n_factors):
+    """sqrt_information: None, or one entry per factor -- None / a [6, 6] L (row-major; the factor's information is L^T L) -- as
+    (info_index [F] int32, sqrt_info [K, 36]) of the ABI"""
+    if sqrt_information is None:
+        return None, None
+    if len(sqrt_information) != n_factors:
+        raise ValueError("one square-root information (or None) per factor")
+    index = np.full(n_factors, -1, np.int32)
+    rows = []
+    for e, L in enumerate(sqrt_information):
+        if L is not None:
+            index[e] = len(rows)
+            rows.append(np.asarray(L, np.float64).reshape(36))
+    return index, (np.ascontiguousarray(np.stack(rows)) if rows else None)
+
+
+def plan_info(poses, kinds, ij, data, fixed=None, sigmas=None, huber=None, sqrt_information=None, info_index=None, sqrt_info=None):
+    """plan_calib() plus sqrt_information: per factor None or the 6x6 L a BETWEEN is whitened by in place of its sigmas (include/smhip.h,
+    "Edge information").  info_index / sqrt_info give the ABI's two arrays directly instead.  An index out of range, an L on a factor
+    that is no BETWEEN, a non-finite or singular L raise PoseGraphRefused."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    if sqrt_information is not None:
+        info_index, sqrt_info = _info(sqrt_information, len(E))
+    I = None if info_index is None else np.ascontiguousarray(np.asarray(info_index, np.int32).reshape(-1))
+    Ls = None if sqrt_info is None else np.ascontiguousarray(np.asarray(sqrt_info, np.float64).reshape(-1, 36))
+    off = np.zeros(len(P) + 1, np.int32)
+    inc = np.zeros(max(2 * len(E), 1), np.int32)
+    why = ctypes.create_string_buffer(256)
+    s = _capi.load_library().smhip_pose_graph_plan_info(len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                        _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                        _ptr(H, _capi.c_double_p), _ptr(I, _capi.c_int32_p), _ptr(Ls, _capi.c_double_p),
+                                                        off.ctypes.data_as(_capi.c_int32_p), inc.ctypes.data_as(_capi.c_int32_p), why, len(why))
+    if s != 0:
+        raise PoseGraphRefused(s, why.value.decode())
+    return off, inc[:off[-1]]
+
+
+def optimize_info(matcher, poses, kinds, ij, data, fixed=None, sigmas=None, huber=None, sqrt_information=None, info_index=None, sqrt_info=None,
+                  max_iterations: int | None = None):
+    """optimize_calib() in which a BETWEEN may carry a full 6x6 square-root information; the arguments of plan_info().  Without one
+    every output has the bits of optimize_calib().  Returns (poses [N, 4, 4], stats dict); last() and last_robust() serve this call too."""
+    P, F, K, E, D, S = _factor_arrays(poses, fixed, kinds, ij, data, sigmas)
+    H = _huber(huber, len(E))
+    if sqrt_information is not None:
+        info_index, sqrt_info = _info(sqrt_information, len(E))
+    I = None if info_index is None else np.ascontiguousarray(np.asarray(info_index, np.int32).reshape(-1))
+    Ls = None if sqrt_info is None else np.ascontiguousarray(np.asarray(sqrt_info, np.float64).reshape(-1, 36))
+    lib = matcher._lib
+    o = _capi.PoseGraphOptions()
+    lib.smhip_pose_graph_default_options(ctypes.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = max_iterations
+    st = _capi.PoseGraphStats()
+    matcher._check(lib.smhip_pose_graph_optimize_info(matcher._h, len(P), _ptr(P, _capi.c_double_p), _ptr(F, c_uint8_p), len(E), _ptr(K, c_uint8_p),
+                                                      _ptr(E, _capi.c_int32_p), _ptr(D, _capi.c_double_p), _ptr(S, _capi.c_double_p),
+                                                      _ptr(H, _capi.c_double_p), _ptr(I, _capi.c_int32_p), _ptr(Ls, _capi.c_double_p),
+                                                      ctypes.byref(o), ctypes.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in _capi.PoseGraphStats._fields_}
+    stats["stop"] = STOP_REASONS.get(st.stop_reason, "?")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), stats
+
+
 def last_robust(matcher, n_factors: int):
     """The report of the last optimise call on the handle, whichever it was, which had n_factors factors (another count is refused): dict(norm [F]
     = s_f, weight [F] = w_f, cost [F] = the cost term) at the poses that call ended at.  After a call without thresholds every weight is 1."""
