@@ -291,6 +291,23 @@ smhip_status smhip_icp_single_launch_counts(smhip_handle h, int64_t* launches_us
  * call forgets what earlier batches taught the handle -- e.g. after a warm-up batch of made-up clouds (smhip_shard) -- so that the
  * next batch starts from the defaults a new handle has. */
 smhip_status smhip_icp_forget_search_history(smhip_handle h);
+/* Inner motion compensation: de-skew of the source inside every IcpFast iteration (registrator::Interface::EnableInnerCompensation).
+ * The reference's branch for it (icp_fast.cc:486-491 -> cloud_types.cc:306-321) is undefined behaviour as written, so what runs is
+ * DEFINED HERE (tests/icp_compensation_ref.py is the text): a continuous-time point-to-plane ICP in which the guess is the pose at
+ * the start of the sweep, the motion during the sweep is the unknown and the result is the pose at its end.  With n rows uploaded
+ * and i the CALLER's row index, f_i = (double) i / n; in every iteration
+ *     P_i = R((double)(float) f_i) * (T(-mu) guess s_i) + T_iter.t * (double)(float) f_i
+ * with R Eigen's slerp from the identity to T_iter's rotation (not normalised), and EACH COORDINATE OF P_i IS ROUNDED TO FLOAT: the
+ * step cloud is a float cloud, which is what the search kernels stream.  The normal equations are A = sum f_i^2 J_i J_i^T and
+ * b = -sum f_i J_i r_i with the unrounded f_i.  Search, quantile, solve, T_iter = dT * T_iter, CheckConvergence, the score and
+ * result = T(mu) T_iter T(-mu) guess are those of the rigid Align.
+ * enable != 0 allocates the step cloud's array for every slot of the handle (12 bytes per source point; nothing is allocated
+ * inside an Align) and makes every form of Align -- single, batch, range, enqueue / fetch / export -- run the mode; 0 (default)
+ * puts the rigid Align back, bit for bit.  The mode searches every query in every iteration (certificates assume a rigid step) and
+ * runs with nn_mode SMHIP_NN_GRID only: an Align under another nn_mode returns SMHIP_ERR_INVALID_ARGUMENT before anything is
+ * touched.  smhip_icp_find_closests, smhip_icp_trimmed_score and smhip_icp_information_* stay rigid passes. */
+smhip_status smhip_icp_set_inner_compensation(smhip_handle h, int enable);
+smhip_status smhip_icp_get_inner_compensation(smhip_handle h, int* enabled);
 /* what the handle was created with / what a slot currently holds (any pointer may be NULL) */
 smhip_status smhip_get_capacity(smhip_handle h, int* pair_slots, int* max_source_points, int* max_target_points);
 smhip_status smhip_get_cloud_sizes(smhip_handle h, int slot, int* n_source, int* n_target, int* has_normals);

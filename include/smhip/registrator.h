@@ -200,7 +200,8 @@ class Interface {
   // -- the new `transform` shadows the argument inside its own initialiser, so the branch interpolates towards an
   // uninitialised matrix: undefined behaviour, and nothing in the reference ever calls the setter.  There is no defined
   // result to reproduce, so IcpFastHip::Align / AlignBatch REFUSE to run with the flag set (error + false) instead of quietly
-  // running the uncompensated iteration.
+  // running the uncompensated iteration -- unless the matcher's inner option "inner_compensation_mode" is 1: then the flag selects
+  // the compensated iteration as smhip.h defines it (smhip_icp_set_inner_compensation).  The other matchers do not read the flag, as in the reference.
   void EnableInnerCompensation() { inner_compensation_ = true; }
   void DisableInnerCompensation() { inner_compensation_ = false; }
   bool InnerCompensationEnabled() const { return inner_compensation_; }
@@ -309,6 +310,10 @@ class IcpFastHip : public Interface {
     // that align at the same time from several threads (the back end's pool of six) set it false: cooperative launches of several
     // handles run one after the other on the device's cooperative queue (six threads: 583 Aligns/s against 781 as separate launches).
     SMHIP_REG_REGISTRATOR_INNER_OPTION("single_launch", OptionItemDataType::kBool, options_.single_launch);
+    // 0 (default): EnableInnerCompensation() is refused (the reference's branch has no defined result).  1: the flag selects the
+    // compensated iteration this library defines (smhip_icp_set_inner_compensation): guess = the pose at the start of the sweep,
+    // result = the pose at its end, row i of the source at i / size of the sweep.
+    SMHIP_REG_REGISTRATOR_INNER_OPTION("inner_compensation_mode", OptionItemDataType::kInt32, options_.inner_compensation_mode);
   }
 
   void InitWithOptions() override { EnsureHandle(0, 0, true, true); }
@@ -518,7 +523,7 @@ class IcpFastHip : public Interface {
   enum TargetKind { kNoTarget, kTargetWithNormals, kTargetRaw };
   // see Interface::EnableInnerCompensation: the reference's compensated branch has no defined result
   bool RefuseInnerCompensation() const {
-    if (!this->inner_compensation_) return false;
+    if (!this->inner_compensation_ || options_.inner_compensation_mode == 1) return false;
     std::fprintf(stderr, "[ERROR] IcpFastHip: inner compensation is enabled, and the reference's branch for it (icp_fast.cc:487-489 -> "
                          "cloud_types.cc:306-321) reads an uninitialised transform: no defined result to reproduce. Call DisableInnerCompensation().\n");
     return true;
@@ -566,7 +571,11 @@ class IcpFastHip : public Interface {
     o.grid_cell = options_.grid_cell;
     o.exact_matches = options_.exact_matches ? 1 : 0;
     o.no_single_kernel = options_.single_launch ? 0 : 1;
-    return Ok(smhip_icp_set_options(h, &o), "smhip_icp_set_options");
+    if (!Ok(smhip_icp_set_options(h, &o), "smhip_icp_set_options")) return false;
+    const bool compensate = this->inner_compensation_ && options_.inner_compensation_mode == 1;
+    int now = 0;
+    if (smhip_icp_get_inner_compensation(h, &now) == SMHIP_OK && (now != 0) == compensate) return true;
+    return Ok(smhip_icp_set_inner_compensation(h, compensate ? 1 : 0), "smhip_icp_set_inner_compensation");
   }
   // Handle with room for ns / nt points (0 = whatever it has).  After a re-creation the clouds the old handle held
   // are uploaded again from the shared_ptrs kept for that purpose, except the one the caller is about to upload itself.
@@ -602,6 +611,7 @@ class IcpFastHip : public Interface {
     float grid_cell = 0.25f;
     bool exact_matches = false;
     bool single_launch = true;
+    int32_t inner_compensation_mode = 0;     // 1: EnableInnerCompensation() selects the compensated iteration (smhip.h)
   } options_;
   int32_t device_ = 0;
   int32_t max_points_;

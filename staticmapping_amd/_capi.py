@@ -147,6 +147,8 @@ SIGNATURES = {
     "smhip_sample_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, c_int32_p]),
     "smhip_set_target_cache": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "smhip_icp_forget_search_history": (ctypes.c_int, [ctypes.c_void_p]),
+    "smhip_icp_set_inner_compensation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "smhip_icp_get_inner_compensation": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "smhip_icp_single_launch_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "smhip_get_capacity": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
     "smhip_get_cloud_sizes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int32_p, c_int32_p, c_int32_p]),

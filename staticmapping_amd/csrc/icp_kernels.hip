@@ -12,6 +12,9 @@
 //                                                               (icp_fast.cc:65-90, 100-166, 256-303)
 //   finalize            [K2/K4] exact quantile inside the boundary bin, 6x6 solve, SE(3) update,
 //                       CheckConvergence, score                  (icp_fast.cc:204-254, 306-323, 377-405, 513-523)
+//   comp_apply / accumulate_comp / finalize_comp
+//                       inner motion compensation: the step cloud de-skewed by T_iter in every iteration, the sums weighted by
+//                       the points' sweep factors (the intent of icp_fast.cc:486-491, 284-289; defined in include/smhip.h)
 //
 // Everything here is HBM/L2-bound gather, scan and reduction work: wave64 shuffles + LDS, no MFMA.
 #include <type_traits>
@@ -510,6 +513,89 @@ __device__ __forceinline__ void transform_point(const double* M, const float4 s,
   px = fma(M[0], x, fma(M[1], y, fma(M[2], z, M[3])));      // ApplyTransform, cloud_types.cc:288-302
   py = fma(M[4], x, fma(M[5], y, fma(M[6], z, M[7])));
   pz = fma(M[8], x, fma(M[9], y, fma(M[10], z, M[11])));
+}
+
+// ------------------------------------------------------------------------------------------
+// Inner motion compensation ("de-skew inside every iteration"; DESIGN.md section 6, restated in tests/icp_compensation_ref.py).
+// The reference's branch (icp_fast.cc:486-491 -> cloud_types.cc:306-321) is undefined behaviour as written; its intent -- point i of
+// the step cloud moved by InterpolateTransform(I, T_iter, factor_i), factor_i = i / size (cloud_types.cc:340-343) -- is DEFINED HERE:
+//     P0_i = T(-mu) guess s_i                                          as the rigid iteration
+//     f_i  = (double) i / n            i = the CALLER's row index (src.w), n = the rows uploaded
+//     P_i  = R((double)(float) f_i) P0_i + T_iter.t * (double)(float) f_i      common::InterpolateTransform takes a const float
+//     with R = q_I.slerp(f, Quaternion(T_iter.R)).toRotationMatrix(), Eigen's, not normalised (as filt_motion_comp)
+//     each coordinate of P_i ROUNDED TO FLOAT: the step cloud is a float cloud, so the search and refinement kernels stream it as the
+//     plain 12-byte source array they were written for, under an identity pose chain.
+// The row's index is the one its upload gave it (smhip_set_source_*: the caller's row); an index outside [0, n) -- a source made on
+// the device by sampling or a filter keeps its producer's -- is clamped into it.
+__device__ __forceinline__ double comp_factor(float w, int ns) {
+  const int orig = min(max(__float_as_int(w), 0), ns - 1);
+  return (double)orig / (double)ns;
+}
+// One launch per iteration and part, before the search: grid (ceil(ns_max / 256), pairs), a row of the grid per pair.  Every
+// workgroup derives the slerp's plan from the pair's T_iter (device state: nothing goes through the host) in double with
+// contraction off, once; its threads then move a row each: 16 bytes in (src: x y z index), 12 bytes out (comp3).  The first
+// workgroup of a pair also declares the pair's pose chain the identity and its motion potential zero: the launches that follow
+// read positions from comp3 and apply st->M to them, and no bound of theirs may lean on a rigid step (certificates never run in
+// this mode, plan::Inputs::compensation).  finalize_tail keeps T_iter and forms the result from it and G, whatever M holds.
+__global__ __launch_bounds__(256) void comp_apply(IcpDev b) {
+#pragma clang fp contract(off)
+  const int pair = b.pair_base + blockIdx.y;
+  PairState* st = &b.state[pair];
+  if (st->done) return;
+  const int ns = st->ns;
+  if ((int)(blockIdx.x * blockDim.x) >= ns) return;
+  __shared__ double s_p[9];              // q_b (x y z w), theta, sin(theta), T_iter's translation
+  __shared__ int s_f[2];                 // linear, negate
+  if (threadIdx.x == 0) {
+    const double* T = st->T_iter;        // row-major 4x4
+    auto R = [&](int r, int c) { return T[4 * r + c]; };
+    double q[3], w, t = R(0, 0) + R(1, 1) + R(2, 2);          // Eigen::Quaternion(Matrix3)
+    if (t > 0) {
+      t = sqrt(t + 1.0); w = 0.5 * t; t = 0.5 / t;
+      q[0] = (R(2, 1) - R(1, 2)) * t; q[1] = (R(0, 2) - R(2, 0)) * t; q[2] = (R(1, 0) - R(0, 1)) * t;
+    } else {
+      int i = 0; if (R(1, 1) > R(0, 0)) i = 1; if (R(2, 2) > R(i, i)) i = 2;
+      const int j = (i + 1) % 3, k = (j + 1) % 3;
+      t = sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0); q[i] = 0.5 * t; t = 0.5 / t;
+      w = (R(k, j) - R(j, k)) * t; q[j] = (R(j, i) + R(i, j)) * t; q[k] = (R(k, i) + R(i, k)) * t;
+    }
+    const double d = 1.0 * w + 0.0 * q[0] + 0.0 * q[1] + 0.0 * q[2], abs_d = fabs(d);   // q_I . q_b
+    const int linear = abs_d >= 1.0 - 2.220446049250313e-16 ? 1 : 0;
+    double theta = 0.0, sin_theta = 0.0;
+    if (!linear) { theta = acos(abs_d); sin_theta = sin(theta); }
+    s_p[0] = q[0]; s_p[1] = q[1]; s_p[2] = q[2]; s_p[3] = w; s_p[4] = theta; s_p[5] = sin_theta;
+    s_p[6] = T[3]; s_p[7] = T[7]; s_p[8] = T[11];
+    s_f[0] = linear; s_f[1] = d < 0 ? 1 : 0;
+    if (blockIdx.x == 0) {
+      for (int k = 0; k < 12; ++k) { const double v = (k % 5 == 0) ? 1.0 : 0.0; st->M[k] = v; st->M_prev[k] = v; }
+      st->pot_a = 0; st->pot_b = 0; st->step_a = 0; st->step_b = 0;
+    }
+  }
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  const size_t g = (size_t)pair * b.ns_cap + i;
+  const float4 s = b.src[g];
+  double x, y, z;
+  transform_point(st->G, s, x, y, z);                                        // P0: the rigid iteration's start
+  const double t = (double)(float)comp_factor(s.w, ns);
+  double scale0, scale1;                                                     // Eigen/src/Geometry/Quaternion.h, slerp
+  if (s_f[0]) { scale0 = 1.0 - t; scale1 = t; }
+  else { scale0 = sin((1.0 - t) * s_p[4]) / s_p[5]; scale1 = sin(t * s_p[4]) / s_p[5]; }
+  if (s_f[1]) scale1 = -scale1;
+  const double qx = scale0 * 0.0 + scale1 * s_p[0], qy = scale0 * 0.0 + scale1 * s_p[1], qz = scale0 * 0.0 + scale1 * s_p[2];
+  const double qw = scale0 * 1.0 + scale1 * s_p[3];
+  const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;                  // toRotationMatrix
+  const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
+  const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
+  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+  const double r00 = 1.0 - (tyy + tzz), r01 = txy - twz, r02 = txz + twy;
+  const double r10 = txy + twz, r11 = 1.0 - (txx + tzz), r12 = tyz - twx;
+  const double r20 = txz - twy, r21 = tyz + twx, r22 = 1.0 - (txx + tyy);
+  const double nx = ((r00 * x + r01 * y) + r02 * z) + s_p[6] * t;
+  const double ny = ((r10 * x + r11 * y) + r12 * z) + s_p[7] * t;
+  const double nz = ((r20 * x + r21 * y) + r22 * z) + s_p[8] * t;
+  *reinterpret_cast<float3*>(b.comp3 + 3 * g) = make_float3((float)nx, (float)ny, (float)nz);
 }
 
 // wave-wide min / max of an int, uniform result: the same DPP pattern as wave_incl_scan with min / max in place of +, the
@@ -2153,6 +2239,26 @@ __device__ __forceinline__ void accumulate_terms(const double* M, const float4 s
   transform_point(M, s4, px, py, pz);
   accumulate_terms_p(px, py, pz, q4, n4, acc);
 }
+// The compensated iteration's row: J scaled by the point's sweep factor f, r as it is -- acc += upper(f J (f J)^T), f J r, 1.
+__device__ __forceinline__ void accumulate_terms_f(const double* M, const float4 s4, const float4 q4, const float4 n4, double f, double* acc) {
+  double px, py, pz;
+  transform_point(M, s4, px, py, pz);
+  const double nx = n4.x, ny = n4.y, nz = n4.z;
+  double J[6];
+  J[0] = f * (py * nz - pz * ny);
+  J[1] = f * (pz * nx - px * nz);
+  J[2] = f * (px * ny - py * nx);
+  J[3] = f * nx; J[4] = f * ny; J[5] = f * nz;
+  const double r = (px - (double)q4.x) * nx + (py - (double)q4.y) * ny + (pz - (double)q4.z) * nz;
+  int c = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int e = a; e < 6; ++e) acc[c++] += J[a] * J[e];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+  acc[28] += 1.0;
+}
 // Block reduction of kAccCols-3 = 29 doubles; thread 0 ends up with the totals in acc[].
 // v of the lanes a DPP control reads from, 0.0 where the control has no source lane or the row is masked off
 template <int CTRL, int ROW_MASK>
@@ -2269,7 +2375,10 @@ __device__ __forceinline__ void block_reduce_pair_sums(const double* acc, bool o
 
 // One block (kAccThreads * ITEMS source points) of a pair's ErrorElements / ComputePointToPlane sums with the quantile's bin known:
 // row `blk` of partials, the bin's members as records in the block's four wave segments.
-template <int ITEMS>
+// COMP = true, the compensated iteration (comp_apply above): b.src3 is the step cloud, Mc the identity, a match below the bin is
+// weighted by its point's sweep factor (accumulate_terms_f), and a record carries the point's ROW in rec_j instead of its match --
+// finalize_body<true> finds match and factor again from the row.  COMP = false compiles to what it was.
+template <int ITEMS, bool COMP = false>
 __device__ __forceinline__ void accumulate_block(const IcpDev& b, PairState* st, int pair, int blk, const double* Mc,
                                                  uint32_t* s_w, uint32_t* s_q, double (*s_red)[29], double* s_out) {
   const int ns = st->ns;
@@ -2292,10 +2401,13 @@ __device__ __forceinline__ void accumulate_block(const IcpDev& b, PairState* st,
   float d_1 = b.d2[so + ic];
   float4 s_1 = ld_src(b, so + ic);
   int j_1 = b.idx[so + ic];
+  float w_1 = 0.f, w_2 = 0.f;            // COMP: the row's caller index (src.w), streamed with the rest
+  if constexpr (COMP) w_1 = b.src[so + ic].w;
   ic = min(base + kAccThreads + (int)threadIdx.x, ns - 1);
   float d_2 = b.d2[so + ic];
   float4 s_2 = ld_src(b, so + ic);
   int j_2 = b.idx[so + ic];
+  if constexpr (COMP) w_2 = b.src[so + ic].w;
   // only a query below the quantile's bin uses its matched point and normal (the 30 % trimmed ones and the bin's own members do
   // not): its d2 arrived with its match id -- one round ahead of the gather -- so the gather is issued for those lanes alone
   float4 q_1 = make_float4(0, 0, 0, 0), n_1 = make_float4(0, 0, 0, 0);
@@ -2307,21 +2419,25 @@ __device__ __forceinline__ void accumulate_block(const IcpDev& b, PairState* st,
     const float4 s4 = s_1;
     const float4 q4 = q_1, n4 = n_1;
     const int jm = j_1;
-    d_1 = d_2; s_1 = s_2; j_1 = j_2;
+    const float wm = w_1;
+    d_1 = d_2; s_1 = s_2; j_1 = j_2; w_1 = w_2;
     if (it + 1 < ITEMS && (__float_as_uint(d_1) >> kHistShift) < qbin) { q_1 = b.tq[to + max(j_1, 0)]; n_1 = b.tn[to + max(j_1, 0)]; }
     if (it + 2 < ITEMS) {
       ic = min(i + 2 * kAccThreads, ns - 1);
       d_2 = b.d2[so + ic];
       s_2 = ld_src(b, so + ic);
       j_2 = b.idx[so + ic];
+      if constexpr (COMP) w_2 = b.src[so + ic].w;
     }
     bool boundary = false;
     if (i < ns) {
       const uint32_t key = __float_as_uint(d);
       if (key < 0x7f800000u) {
         const uint32_t bin = key >> kHistShift;
-        if (bin < qbin) accumulate_terms(Mc, s4, q4, n4, acc);
-        else boundary = bin == qbin;
+        if (bin < qbin) {
+          if constexpr (COMP) accumulate_terms_f(Mc, s4, q4, n4, comp_factor(wm, ns), acc);
+          else accumulate_terms(Mc, s4, q4, n4, acc);
+        } else boundary = bin == qbin;
       }
     }
     // the quantile bin's members are left for finalize as records (source point, d2, match: all it needs of them), compacted
@@ -2331,7 +2447,7 @@ __device__ __forceinline__ void accumulate_block(const IcpDev& b, PairState* st,
     if (boundary) {
       const size_t at = segbase + wcount + __popcll(bm & ((1ull << (threadIdx.x & 63)) - 1ull));
       b.rec_a[at] = make_float4(s4.x, s4.y, s4.z, d);
-      b.rec_j[at] = jm;
+      b.rec_j[at] = COMP ? i : jm;
     }
     wcount += (int)__popcll(bm);
   }
@@ -2356,6 +2472,25 @@ __global__ __launch_bounds__(kAccThreads) void accumulate(IcpDev b, int nblk) {
   __shared__ double s_red[4][29];
   __shared__ double s_out[29];
   accumulate_block<ITEMS>(b, st, pair, blk, Mc, s_w, s_q, s_red, s_out);
+}
+
+// `accumulate` of the compensated iteration: A = sum f_i^2 J_i J_i^T, b = -sum f_i J_i r_i over the step cloud comp_apply left
+// (icp_fast.cc:130, 284-289: the columns of F and wF scaled by the point's factor).
+template <int ITEMS>
+__global__ __launch_bounds__(kAccThreads) void accumulate_comp(IcpDev b, int nblk) {
+  int pair, blk;
+  if (!xcd_block(nblk, b.npairs, b.pair_base, pair, blk)) return;
+  PairState* st = &b.state[pair];
+  if (st->done) return;
+  if (blk * (kAccThreads * ITEMS) >= st->ns) return;
+  double Mc[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Mc[k] = st->M[k];       // the identity (comp_apply)
+  __shared__ uint32_t s_w[17];
+  __shared__ uint32_t s_q[4];
+  __shared__ double s_red[4][29];
+  __shared__ double s_out[29];
+  accumulate_block<ITEMS, true>(b, st, pair, blk, Mc, s_w, s_q, s_red, s_out);
 }
 
 
@@ -3513,7 +3648,11 @@ __device__ __forceinline__ uint32_t finalize_tail(const B& b, PairState* st, int
   return n_listed;
 }
 
-__global__ __launch_bounds__(256) void finalize(IcpDev b) {
+// COMP = true: the compensated iteration (comp_apply, accumulate_comp) -- a record's rec_j is its point's ROW, from which the match
+// (idx) and the sweep factor (src.w) are read again, and its terms are weighted like accumulate_comp's.  Everything else -- the
+// select, the fold, the tail -- is the same code; COMP = false compiles to what `finalize` was.
+template <bool COMP>
+__device__ __forceinline__ void finalize_body(const IcpDev& b) {
   const int pair = b.pair_base + blockIdx.x;
   PairState* st = &b.state[pair];
   if (st->done) return;
@@ -3716,6 +3855,7 @@ __global__ __launch_bounds__(256) void finalize(IcpDev b) {
         uint32_t pos[kW];
         int jj[kW], sg[kW];
         float4 s4[kW], q4[kW], n4[kW];
+        [[maybe_unused]] double fk[kW];
 #pragma unroll
         for (int k = 0; k < kW; ++k) {
           const int e = min(e0 + 256 * k, nb - 1);
@@ -3733,19 +3873,36 @@ __global__ __launch_bounds__(256) void finalize(IcpDev b) {
         for (int k = 0; k < kW; ++k) pos[k] = rec_at(sg[k], min(e0 + 256 * k, nb - 1) - (int)s_off[sg[k]]);
 #pragma unroll
         for (int k = 0; k < kW; ++k) { s4[k] = ra[pos[k]]; jj[k] = max(rj[pos[k]], 0); }
+        if constexpr (COMP) {
+#pragma unroll
+          for (int k = 0; k < kW; ++k) {
+            const size_t row = (size_t)pair * b.ns_cap + jj[k];
+            fk[k] = comp_factor(b.src[row].w, ns);
+            jj[k] = max(b.idx[row], 0);
+          }
+        }
 #pragma unroll
         for (int k = 0; k < kW; ++k) { q4[k] = b.tq[to + jj[k]]; n4[k] = b.tn[to + jj[k]]; }
 #pragma unroll
         for (int k = 0; k < kW; ++k)
-          if (use[k]) accumulate_terms(st->M, s4[k], q4[k], n4[k], acc);
+          if (use[k]) {
+            if constexpr (COMP) accumulate_terms_f(st->M, s4[k], q4[k], n4[k], fk[k], acc);
+            else accumulate_terms(st->M, s4[k], q4[k], n4[k], acc);
+          }
       }
     } else {
       for (int e = threadIdx.x; e < nb; e += blockDim.x) {
         const uint32_t at = member(e);
         const float4 a = ra[at];
         if (__float_as_uint(a.w) <= limit_key) {
-          const int j = max(rj[at], 0);
-          accumulate_terms(st->M, a, b.tq[to + j], b.tn[to + j], acc);
+          if constexpr (COMP) {
+            const size_t row = (size_t)pair * b.ns_cap + max(rj[at], 0);
+            const int j = max(b.idx[row], 0);
+            accumulate_terms_f(st->M, a, b.tq[to + j], b.tn[to + j], comp_factor(b.src[row].w, ns), acc);
+          } else {
+            const int j = max(rj[at], 0);
+            accumulate_terms(st->M, a, b.tq[to + j], b.tn[to + j], acc);
+          }
         }
       }
     }
@@ -3785,6 +3942,9 @@ __global__ __launch_bounds__(256) void finalize(IcpDev b) {
   }
 #endif
 }
+
+__global__ __launch_bounds__(256) void finalize(IcpDev b) { finalize_body<false>(b); }
+__global__ __launch_bounds__(256) void finalize_comp(IcpDev b) { finalize_body<true>(b); }
 
 // The score of the iteration an alignment left the loop with (icp_fast.cc:516-522: exp(-mean distance of that iteration's kept
 // matches), formed there and nowhere else): one pass over the pair's distances of that iteration -- `d2` keeps them once the pair is

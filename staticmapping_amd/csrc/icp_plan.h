@@ -98,7 +98,18 @@ struct Inputs {
   int profiling = 0;
   int part_stride = 0, seg_stride = 0;
   int side_streams = 0;           // side streams the handle has
+  // Inner motion compensation (smhip_icp_set_inner_compensation): every iteration of an Align starts with comp_apply, which writes the
+  // step cloud the other launches then read under an identity pose chain.  The runner-up certificates and the motion potential
+  // assume a rigid step, so the mode takes the certificate-free plan: no nn_certify*, no fused pass, no icp_one (compensated()).
+  int compensation = 0;
 };
+
+// the inputs an Align is planned with: as given, or -- compensation -- with everything that leans on a rigid step switched off
+inline Inputs compensated(const Inputs& in) {
+  Inputs c = in;
+  if (c.compensation) { c.certify = 0; c.no_fused_sums = 1; c.no_single_kernel = 1; }
+  return c;
+}
 
 // ---- the batch -----------------------------------------------------------------------------------------------------------
 struct Part {
@@ -146,7 +157,8 @@ inline Part whole_part(int np, int nt_max) {
 // is the batch one whose iterations may take the two-launch certificate form without being told to?
 inline bool two_launch_sized(int np) { return np >= kTwoLaunchMinPairs; }
 
-inline Batch plan_batch(const Inputs& in, int npairs, int ns_max, int nt_max) {
+inline Batch plan_batch(const Inputs& given, int npairs, int ns_max, int nt_max) {
+  const Inputs in = compensated(given);
   Batch b;
   int want = std::min(parts_wanted(in, npairs), 1 + in.side_streams);
   while (want > 1 && npairs < kMinPartPairs * want) --want;
@@ -205,6 +217,8 @@ enum class Kernel : uint8_t {
   NaboOneShallow, NaboOneDeep, NaboFourShallow, NaboFourDeep, NaboValidate, AccumulateListed,
   // sums and solve
   AccumulateSmall, AccumulateBatch, IterationSumsSmall, IterationSumsBatch, Finalize,
+  // inner motion compensation: the step cloud, then the factor-weighted sums and the solve over them (behind the others: their values stay)
+  CompApply, AccumulateCompSmall, AccumulateCompBatch, FinalizeComp,
 };
 
 // profiling brackets: category 0 prepare, 1 the refinement launches of FindClosests (validate / ring / fallback), 2 error_elements,
@@ -348,7 +362,8 @@ inline Iteration plan_search_only(const Inputs& in, const Part& p, int ns_max) {
 }
 
 // one iteration of one part of an Align: FindClosests, the sums, finalize
-inline Iteration plan_iteration(const Inputs& in, const Part& p, int ns_max, int iteration, int first_fused) {
+inline Iteration plan_iteration(const Inputs& given, const Part& p, int ns_max, int iteration, int first_fused) {
+  const Inputs in = compensated(given);
   Iteration it;
   it.first_fused = first_fused;
   it.acc_items = p.acc_items;
@@ -365,16 +380,20 @@ inline Iteration plan_iteration(const Inputs& in, const Part& p, int ns_max, int
     it.sums_items = (p.acc_items == kAccItemsBatch && (iteration - it.first_fused < in.sums_long_for || !short_chunks_fit(ns_max))) ? kAccItemsBatch : kAccItemsSmall;
     if (iteration < 2) it.sums_items = p.acc_items;
   }
+  // compensation: the step cloud first, a row of the grid per pair (it reads the pair's T_iter from device state)
+  if (in.compensation) it.add(Kernel::CompApply, kCatPrepare, ceil_div(ns_max, 256), p.np);
   plan_search(in, p, ns_max, iteration, it);
   const bool batch_items = p.acc_items == kAccItemsBatch;
   if (fused_ball && iteration >= 2) {
     // fused iteration: only the pairs whose prediction missed need `accumulate`, the others the sums of their listed matches --
     // one fixed grid that takes both kinds of work (iteration_sums) instead of workgroups per pair that look at a flag
     it.add(it.sums_items == kAccItemsBatch ? Kernel::IterationSumsBatch : Kernel::IterationSumsSmall, kCatSums, in.sums_blocks);
+  } else if (in.compensation) {
+    it.add_xcd(batch_items ? Kernel::AccumulateCompBatch : Kernel::AccumulateCompSmall, kCatSums, ceil_div(ns_max, kAccThreads * p.acc_items), p.np);
   } else {
     it.add_xcd(batch_items ? Kernel::AccumulateBatch : Kernel::AccumulateSmall, kCatSums, ceil_div(ns_max, kAccThreads * p.acc_items), p.np);
   }
-  it.add(Kernel::Finalize, kCatSolve, p.np);
+  it.add(in.compensation ? Kernel::FinalizeComp : Kernel::Finalize, kCatSolve, p.np);
   return it;
 }
 

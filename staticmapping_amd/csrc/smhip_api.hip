@@ -265,6 +265,7 @@ static plan::Inputs plan_inputs(const smhip_context* h) {
   in.profiling = h->profile != 0;
   in.part_stride = h->dev.part_stride; in.seg_stride = h->dev.seg_stride;
   in.side_streams = h->n_side;
+  in.compensation = h->inner_comp;
   return in;
 }
 
@@ -326,6 +327,10 @@ static smhip_status enqueue_launches(smhip_context* h, const Half& f, const plan
       case K::AccumulateBatch:    hipLaunchKernelGGL(accumulate<kAccItemsBatch>, g, acc, 0, st, d, l.nb); break;
       case K::AccumulateSmall:    hipLaunchKernelGGL(accumulate<kAccItemsSmall>, g, acc, 0, st, d, l.nb); break;
       case K::Finalize:           hipLaunchKernelGGL(finalize, g, t256, 0, st, d); break;
+      case K::CompApply:          hipLaunchKernelGGL(comp_apply, g, t256, 0, st, d); break;
+      case K::AccumulateCompBatch: hipLaunchKernelGGL(accumulate_comp<kAccItemsBatch>, g, acc, 0, st, d, l.nb); break;
+      case K::AccumulateCompSmall: hipLaunchKernelGGL(accumulate_comp<kAccItemsSmall>, g, acc, 0, st, d, l.nb); break;
+      case K::FinalizeComp:       hipLaunchKernelGGL(finalize_comp, g, t256, 0, st, d); break;
     }
   }
   return SMHIP_OK;
@@ -1040,6 +1045,10 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
     if (h) h->err = "bad slot range / guesses";
     return SMHIP_ERR_INVALID_ARGUMENT;
   }
+  // inner compensation is defined over the grid search alone (the reference-search and brute modes are out of its scope): refused
+  // before anything is touched
+  if (h->inner_comp && h->opts.nn_mode != SMHIP_NN_GRID) { h->err = "inner compensation runs with nn_mode SMHIP_NN_GRID only"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (h->inner_comp && !h->dev.comp3) { h->err = "inner compensation: the step cloud's array is missing (internal)"; return SMHIP_ERR_NOT_READY; }
   HIPCHK(h, hipSetDevice(h->device));
   int ns_max = 0, nt_max = 0;
   // in_pinned may still be in flight from a previous enqueue on this stream
@@ -1073,6 +1082,12 @@ static smhip_status enqueue_range(smhip_handle h, int first, int npairs, const d
     halves[k].part = p;
     halves[k].part.nt_max = nt_max_of(h, first + p.first, p.np);
     halves[k].d.acc_items = p.acc_items;
+    if (in.compensation) {
+      // the iteration kernels of this Align stream the step cloud comp_apply writes (IcpDev goes by value: the slot's own src3 is
+      // neither moved nor overwritten) and search every query: no certificate survives a step that is not rigid
+      halves[k].d.src3 = h->dev.comp3;
+      halves[k].d.certify = 0;
+    }
   }
   auto fork = [&]() -> smhip_status {
     if (nh > 1) {
@@ -1285,10 +1300,13 @@ smhip_status smhip_icp_trimmed_score(smhip_handle h, int slot, const double T[16
   o.max_iteration = 1; o.early_exit = 0; o.dist_outlier_ratio = dist_outlier_ratio;
   h->opts = o;
   sync_options(h);
+  const int comp_was = h->inner_comp;
+  h->inner_comp = 0;                       // a rigid pass at T, whatever mode the handle's Aligns run in
   double result[16];
   smhip_icp_stats st{};
   s = enqueue_range(h, slot, 1, T);
   if (s == SMHIP_OK) s = fetch_range(h, slot, 1, result, score, &st);
+  h->inner_comp = comp_was;
   h->opts = saved;
   sync_options(h);
   h->has_normals[slot] = had;
@@ -1308,9 +1326,12 @@ smhip_status trimmed_pass_range(smhip_context* h, int first, int npairs, const d
   o.max_iteration = 1; o.early_exit = 0; o.dist_outlier_ratio = dist_outlier_ratio; o.exact_matches = 1;
   h->opts = o;
   sync_options(h);
+  const int comp_was = h->inner_comp;
+  h->inner_comp = 0;                       // (rigid, as smhip_icp_trimmed_score)
   smhip_status s = enqueue_range(h, first, npairs, Ts);
   if (s == SMHIP_OK) s = fetch_range(h, first, npairs, nullptr, nullptr, stats);
   else for (int p = 0; p < npairs; ++p) stats[p] = smhip_icp_stats{};
+  h->inner_comp = comp_was;
   h->opts = saved;
   sync_options(h);
   h->hist_pairs = 0;
@@ -1322,6 +1343,23 @@ smhip_status trimmed_pass_range(smhip_context* h, int first, int npairs, const d
 smhip_status smhip_set_target_cache(smhip_handle h, int enable) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
   h->target_cache = enable ? 1 : 0;
+  return SMHIP_OK;
+}
+
+smhip_status smhip_icp_set_inner_compensation(smhip_handle h, int enable) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (enable && !h->dev.comp3) {           // the step cloud's array, for every slot, here and never inside an Align
+    HIPCHK(h, hipSetDevice(h->device));
+    const smhip_status s = dev_alloc(h, &h->dev.comp3, (size_t)h->dev.slots * (size_t)h->dev.ns_cap * 3);
+    if (s) return s;
+  }
+  h->inner_comp = enable ? 1 : 0;
+  return SMHIP_OK;
+}
+
+smhip_status smhip_icp_get_inner_compensation(smhip_handle h, int* enabled) {
+  if (!h || !enabled) return SMHIP_ERR_INVALID_ARGUMENT;
+  *enabled = h->inner_comp;
   return SMHIP_OK;
 }
 

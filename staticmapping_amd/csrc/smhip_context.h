@@ -59,6 +59,7 @@ struct smhip_context {
   unsigned long long gen_counter = 0;
   int nabo_listed_blocks = kNaboListedBlocks;   // workgroups per pair of the list walk (SMHIP_NABO_LISTED_BLOCKS overrides, tuning only)
   int target_cache = 1;             // smhip_set_target_cache
+  int inner_comp = 0;               // smhip_icp_set_inner_compensation: Aligns de-skew the source inside every iteration (dev.comp3 allocated)
   unsigned long long cache_hits = 0;
   PairInput* in_pinned = nullptr;
   PairState* state_pinned = nullptr;

@@ -227,6 +227,10 @@ struct IcpDev {
   float rho;                 // dist_outlier_ratio as float (widened to double exactly like the reference)
   float grid_cell;
   int32_t debug_flags;       // diagnostic builds only (SMHIP_DEBUG_FLAGS with -DSMHIP_PHASE_TIMING=1): bit 4 = per-phase timing of nn_ball_lds
+  // Inner motion compensation (smhip_icp_set_inner_compensation).  Last in the struct: no kernel written before
+  // the mode reads them, and the offsets of everything above stay where they were.
+  float* comp3;              // [slots][ns_cap][3] the step cloud of the compensated iteration as float (comp_apply writes it once per iteration;
+                             //                 the launches of a compensated Align get src3 = comp3).  Null until the mode is enabled.
 };
 
 }  // namespace smhip

@@ -59,7 +59,7 @@ class IcpFastHip:
     """
 
     def __init__(self, device: int = 0, pair_slots: int = 1, max_source_points: int = 131072,
-                 max_target_points: int = 131072, stream: int | None = None, **options):
+                 max_target_points: int = 131072, stream: int | None = None, inner_compensation: bool = False, **options):
         self._lib = _capi.load_library()
         self._h = ctypes.c_void_p()
         st = self._lib.smhip_create(device, ctypes.c_void_p(stream) if stream else None, pair_slots,
@@ -74,6 +74,8 @@ class IcpFastHip:
         self._lib.smhip_icp_default_options(ctypes.byref(self._opts))
         if options:
             self.set_options(**options)
+        if inner_compensation:
+            self.set_inner_compensation(True)
 
     # -- lifetime --------------------------------------------------------
     def close(self):
@@ -170,6 +172,18 @@ class IcpFastHip:
         """Keep the target-side structures (ICP search grid, NDT voxel table) across single-pair calls while the target is
         unchanged (default on); off = rebuild on every Align like the reference.  Results are identical either way."""
         self._check(self._lib.smhip_set_target_cache(self._h, 1 if enable else 0))
+
+    def set_inner_compensation(self, enable: bool = True):
+        """De-skew the source inside every iteration of Align (smhip_icp_set_inner_compensation; defined in include/smhip.h and
+        restated in tests/icp_compensation_ref.py): the guess is the pose at the start of the sweep, the result the pose at its
+        end, row i of n uploaded rows lies at i / n of the sweep.  Off (default): the rigid Align, bit for bit."""
+        self._check(self._lib.smhip_icp_set_inner_compensation(self._h, 1 if enable else 0))
+
+    @property
+    def inner_compensation(self) -> bool:
+        v = ctypes.c_int(0)
+        self._check(self._lib.smhip_icp_get_inner_compensation(self._h, ctypes.byref(v)))
+        return bool(v.value)
 
     def forget_search_history(self):
         """The next batch chooses where to switch search forms as a new handle's first batch does (smhip_icp_forget_search_history)."""
