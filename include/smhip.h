@@ -604,6 +604,15 @@ smhip_status smhip_filter_statistic_last(smhip_handle h, float* distance, int n,
  * selects.  With voxel_size == 0 no index is formed and every row is carried. */
 smhip_status smhip_submap_build_f32(smhip_handle h, int n_frames, const float* const* rows, int stride_floats, const int* n,
                                     const double* local_poses, float voxel_size, int* n_out);
+/* smhip_submap_build_f32 with every frame DE-SKEWED first ("Motion compensation after optimisation"):
+ * motions holds 16 doubles per frame (column-major), the sensor's motion during that frame's sweep; a row goes through
+ * MotionCompensation under its frame's motion (as smhip_filter_output_to_source_compensated computes it, the coordinates rounded to
+ * float), then through the local TransformPoint.  Key, factor and source_index are smhip_submap_build_f32's.  The contract is that
+ * call's, and a null or non-finite motion is refused before anything is touched.  A row whose factor is outside [0, 1] or NaN is
+ * reported as the voxel index beyond +-2^20 is: SMHIP_ERR_INVALID_ARGUMENT after the rows were written (such a row is transformed as
+ * it is), with the unfiltered concatenation as the resident cloud. */
+smhip_status smhip_submap_build_compensated_f32(smhip_handle h, int n_frames, const float* const* rows, int stride_floats, const int* n,
+                                                const double* local_poses, const double* motions, float voxel_size, int* n_out);
 /* device CalculateNormals of the filter workspace's current cloud (a filter chain's output or a built submap) -> target of
  * `slot`, without a download (submap.cc:160-161); *n_out = the target's size.  SMHIP_ERR_NOT_READY when no cloud is there;
  * otherwise as smhip_prepare_target_f32 on the same rows. */
@@ -862,6 +871,18 @@ smhip_status smhip_mrvm_insert_f32(smhip_mrvm_handle h, const float* points, int
  * everything smhip_mrvm_insert_f32 refuses; warnings as there. */
 smhip_status smhip_mrvm_insert_transformed_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
                                                float intensity_scale);
+/* Motion compensation after optimisation: smhip_mrvm_insert_transformed_f32 of the frame DE-SKEWED by `motion`,
+ * the sensor's motion during the frame's sweep (column-major 4x4; pose^-1 * the next frame's pose), `pose` being the sensor pose at
+ * the START of the sweep.  One kernel per row: MotionCompensation (map_builder.cc:232-257) exactly as
+ * smhip_filter_output_to_source_compensated computes it (InterpolateTransform(I, motion, factor) in double, each coordinate cast to
+ * float), then TransformPoint under `pose` as above; the de-skewed cloud is never stored.  The factor is the row's fifth float
+ * (stride 5) or the collector's (float)((double)i / n) (stride 4) and is carried into the stored point; the ray origin stays the
+ * pose's translation cast to float.  Refused before the map is touched: a null or non-finite motion and everything
+ * smhip_mrvm_insert_transformed_f32 refuses.  A row whose factor is outside [0, 1] or NaN: SMHIP_ERR_INVALID_ARGUMENT with the map
+ * bit for bit as it was (the kernel's flag is read before any kernel that writes the table runs, which costs one stream
+ * synchronise the plain insert does not have). */
+smhip_status smhip_mrvm_insert_compensated_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                               const double motion[16], float intensity_scale);
 smhip_status smhip_mrvm_last_skipped(smhip_mrvm_handle h, int* n);
 smhip_status smhip_mrvm_voxel_count(smhip_mrvm_handle h, int* n);
 smhip_status smhip_mrvm_set_max_table_log2(smhip_mrvm_handle h, int max_table_log2);   /* 10..28; default 28 */

@@ -208,6 +208,8 @@ SIGNATURES = {
     "smhip_filter_statistic_last": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, c_double_p]),
     "smhip_submap_build_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(c_float_p), ctypes.c_int, c_int32_p, c_double_p,
                                               ctypes.c_float, ctypes.POINTER(ctypes.c_int)]),
+    "smhip_submap_build_compensated_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(c_float_p), ctypes.c_int, c_int32_p, c_double_p,
+                                                          c_double_p, ctypes.c_float, ctypes.POINTER(ctypes.c_int)]),
     "smhip_filter_output_to_target": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "smhip_m2dp_default_options": (None, [ctypes.POINTER(M2dpOptions)]),
     "smhip_m2dp_length": (ctypes.c_int, [ctypes.POINTER(M2dpOptions)]),
@@ -250,6 +252,7 @@ SIGNATURES = {
     "smhip_mrvm_set_offset_z": (None, [ctypes.c_void_p, ctypes.c_float]),
     "smhip_mrvm_insert_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p]),
     "smhip_mrvm_insert_transformed_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_float]),
+    "smhip_mrvm_insert_compensated_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_float]),
     "smhip_mrvm_voxel_count": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "smhip_mrvm_set_max_table_log2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "smhip_mrvm_table_log2": (ctypes.c_int, [ctypes.c_void_p]),

@@ -75,6 +75,12 @@ inline MotionCompArgs motion_comp_args(const double m[16] /* column-major 4x4 */
 // whether the last call met such a row.  Asynchronous on `st`.
 hipError_t filt_motion_compensate(FilterWorkspace* w, hipStream_t st, const MotionCompArgs& a, float4* out);
 bool filt_motion_bad_factor(const FilterWorkspace* w);
+// The same flag for a kernel of another unit that de-skews the rows it builds (smhip_submap.hip, between filt_build_begin and
+// filt_build_commit): filt_motion_flag_begin clears it on `st` and hands it out (nullptr: the clear failed), the kernel raises it by
+// a plain store, filt_motion_flag_end sends it to pinned memory behind the kernel; filt_motion_bad_factor reads it once `st` has been
+// synchronised.
+int32_t* filt_motion_flag_begin(FilterWorkspace* w, hipStream_t st);
+hipError_t filt_motion_flag_end(FilterWorkspace* w, hipStream_t st);
 
 // GroundRemoval2::ClusterGround, filter_ground_removal2.cc:318-320: search_angle_ / 180. * M_PI / delta_alpha in double with
 // delta_alpha = (float)(M_PI * 2 / segment_num_), truncated as x86 does (INT_MIN outside the int range)

@@ -35,6 +35,7 @@
 
 #include "../../include/smhip.h"
 #include "cloud_filters.h"
+#include "motion_comp_point.h"
 #include "voxel_key.h"
 
 namespace smhip {
@@ -495,6 +496,12 @@ hipError_t filt_motion_compensate(FilterWorkspace* w, hipStream_t st, const Moti
   return hipMemcpyAsync(w->host_pinned + 3, w->counts + 2, 4, hipMemcpyDeviceToHost, st);
 }
 bool filt_motion_bad_factor(const FilterWorkspace* w) { return w->host_pinned[3] != 0; }
+int32_t* filt_motion_flag_begin(FilterWorkspace* w, hipStream_t st) {
+  return w && hipMemsetAsync(w->counts + 2, 0, 4, st) == hipSuccess ? w->counts + 2 : nullptr;
+}
+hipError_t filt_motion_flag_end(FilterWorkspace* w, hipStream_t st) {
+  return hipMemcpyAsync(w->host_pinned + 3, w->counts + 2, 4, hipMemcpyDeviceToHost, st);
+}
 
 const float4* filt_points(const FilterWorkspace* w) { return w->pts[w->cur]; }
 const float* filt_factors(const FilterWorkspace* w) { return w->fac[w->cur]; }

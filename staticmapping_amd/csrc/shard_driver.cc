@@ -148,6 +148,7 @@ Args Parse(int argc, char** argv) {
     else if (k == "--map-average") a.map_average = true;
     else if (k == "--map-rgb") a.map_rgb = true;
     else if (k == "--map-max-table-log2") a.map_max_table_log2 = std::atoi(val().c_str());
+    else if (k == "--map-compensate") { a.map_compensate = std::atoi(val().c_str()) != 0; a.map_compensate_given = true; }
     else if (k == "--map-package") a.map_package = val();
     else if (k == "--package-piece-width") a.package.piece_width = std::atof(val().c_str());
     else if (k == "--package-border-offset") a.package.border_offset = std::atof(val().c_str());
@@ -223,7 +224,7 @@ Args Parse(int argc, char** argv) {
              "[--iterations 20] [--early-exit 0|1] [--guess-tx metres] [--guess constant|ctrv (ctrv: pair k + 1 starts from pair k's motion; one GPU, one matcher)] [--max-pairs N] [--readers 8] [--matchers 1|2] [--warmup 1|0] [--parts 0..4]\n"
              "  static map: [--map map.pcd] [--map-poses kitti_pose.txt (map only)] [--map-every 1] [--map-part-every 0] [--map-resolution 0.1] "
              "[--map-threshold 0.6] [--map-hit 0.55] [--map-miss 0.48] [--map-points-per-cell 10] [--map-z-offset 0] [--map-average] [--map-rgb] "
-             "[--map-max-table-log2 28]\n"
+             "[--map-max-table-log2 28] [--map-compensate 0|1 (with --map or --map-package: every frame de-skewed by its motion to the next pose of the file)]\n"
              "  map package: [--map-package DIR (from the poses as written, or --map-poses; submaps of --submap-frames frames at --submap-voxel, a "
              "trailing group that is not full is dropped; the pieces' maps take the --map-* settings)] [--package-piece-width 500] "
              "[--package-border-offset 100] [--package-prefix part_] [--package-descript map_package.xml]\n"
@@ -254,6 +255,7 @@ Args Parse(int argc, char** argv) {
   if (a.scans_dir.empty() && !a.Join()) Die("--scans DIR is required");
   if (!a.save_trajectory_map.empty() && a.close_loops.empty()) Die("--save-trajectory-map needs --close-loops");
   if (!a.map_poses.empty() && a.map_path.empty() && a.map_package.empty()) Die("--map-poses needs --map PATH");
+  if (a.map_compensate_given && a.map_path.empty() && a.map_package.empty()) Die("--map-compensate needs --map or --map-package");
   if (!a.map_package.empty() && (!std::isfinite(a.package.piece_width) || !(a.package.piece_width > 0.0) || !std::isfinite(a.package.border_offset) ||
                                  a.package.descript_filename.empty()))
     Die("bad package setting (--package-piece-width finite and > 0, --package-border-offset finite, --package-descript not empty)");

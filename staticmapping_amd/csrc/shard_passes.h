@@ -25,6 +25,7 @@
 #include "../../include/smhip/pose_graph.h"
 #include "../../include/smhip/map_package.h"
 #include "../../include/smhip/multi_trajectory.h"
+#include "../../include/smhip/sweep_motion.h"
 #include "shard_poses.h"
 
 namespace shard {
@@ -45,6 +46,8 @@ struct Args {
   int map_every = 1, map_part_every = 0, map_points_per_cell = 10, map_max_table_log2 = 28;
   float map_resolution = 0.1f, map_threshold = 0.6f, map_hit = 0.55f, map_miss = 0.48f, map_z_offset = 0.f;
   bool map_average = false, map_rgb = false;
+  // --map-compensate 1: --map and --map-package de-skew every frame by its sweep motion, taken from the pose file (smhip/sweep_motion.h)
+  bool map_compensate = false, map_compensate_given = false;
   // the map package (--map-package); defaults: MapPackageOptions, builder/map_package.h:36-41
   std::string map_package;
   smhip::MapPackageOptions package;
@@ -130,6 +133,9 @@ inline std::vector<int> MapFrames(const Args& a, int n_frames) {
 // separate_step, :860-890, counted in frames rather than submaps); otherwise the whole map goes to PATH.  Every file is a PCD file
 // with its rows in voxel-key order (SMHIP_MRVM_SORTED).  Returns 0, or 3 when the map refused a frame: the files of this run are then
 // removed.  map_voxels / map_points are summed over the parts.  Like every pass, it appends its fields of the summary line when it returns 0.
+// --map-compensate 1 ("Motion compensation after optimisation"): frame k is de-skewed on its way in by
+// SweepMotions(poses)[k], the step from its pose to its successor's in the pose file whatever --map-every says
+// (smhip_mrvm_insert_compensated_f32; poses[k] is read as the pose at the start of the sweep).
 inline int BuildMap(const Args& a, const std::vector<std::string>& files, const std::vector<int>& frames, const std::vector<Pose>& poses, int device,
                     std::string* fields) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -167,6 +173,7 @@ inline int BuildMap(const Args& a, const std::vector<std::string>& files, const 
     }
   };
   fresh_map();
+  const std::vector<Pose> motions = a.map_compensate ? smhip::SweepMotions(poses) : std::vector<Pose>();
   ScanPrefetcher scans(files, frames, a.readers, 2 * std::max(1, a.readers) + 2, /*hold_until_release=*/false, slot_floats);
   int in_part = 0, part = 0, rc = 0;
   for (size_t i = 0; i < frames.size(); ++i) {
@@ -177,7 +184,8 @@ inline int BuildMap(const Args& a, const std::vector<std::string>& files, const 
     if (n == 0) {
       std::fprintf(stderr, "smhip_shard: map: %s is empty, skipped\n", files[fi].c_str());     // InsertPointCloud: "cloud is empty.", :61-64
     } else {
-      const smhip_status st = smhip_mrvm_insert_transformed_f32(h, rows, 4, n, poses[fi].data(), 255.f);
+      const smhip_status st = a.map_compensate ? smhip_mrvm_insert_compensated_f32(h, rows, 4, n, poses[fi].data(), motions[fi].data(), 255.f)
+                                               : smhip_mrvm_insert_transformed_f32(h, rows, 4, n, poses[fi].data(), 255.f);
       if (st != SMHIP_OK) {
         std::fprintf(stderr, "smhip_shard: map: frame %d refused: %s\n", fi, smhip_mrvm_last_error(h));
         rc = 3;
@@ -215,7 +223,8 @@ struct PairMatch { smhip_status status = SMHIP_OK; double score = 0.0; bool acce
 // from the raw rows under N local poses (smhip_submap_build_f32: VoxelGrid of --submap-voxel, 0 = none).  The cloud never leaves the
 // device: it is the filter output of `h`, becomes the source against the previous submap's CalculateNormals target (MatchToPrevious),
 // then the target of the next (KeepAsTarget).  The local poses are the caller's: the passes do not all invert the first pose the
-// same way.  `label` names the pass in messages.
+// same way.  `label` names the pass in messages.  Build(k, local, motions) with motions != nullptr (N times 16 doubles) de-skews
+// every frame by its sweep motion first (smhip_submap_build_compensated_f32).
 struct SubmapFeed {
   const Args& a;
   const std::vector<std::string>& files;
@@ -257,7 +266,7 @@ struct SubmapFeed {
   }
 
   // Submap k under local[16 * f] (column-major).  Returns its point count, or -1 when the device refused it (said on stderr).
-  int Build(int k, const double* local) {
+  int Build(int k, const double* local, const double* motions = nullptr) {
     std::vector<const float*> rows(N);
     std::vector<int> n(N);
     for (int f = 0; f < N; ++f) {
@@ -267,7 +276,8 @@ struct SubmapFeed {
       if (n[f] < 0) Die("cannot read " + files[fi]);
     }
     int m = 0;
-    const smhip_status st = smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local, voxel, &m);
+    const smhip_status st = motions ? smhip_submap_build_compensated_f32(h, N, rows.data(), 4, n.data(), local, motions, voxel, &m)
+                                    : smhip_submap_build_f32(h, N, rows.data(), 4, n.data(), local, voxel, &m);
     scans->ReleaseHeld();                                                 // the call returned: the rows have left the host buffers
     if (st == SMHIP_OK) return m;
     std::fprintf(stderr, "smhip_shard: submap %d refused: %s\n", k, smhip_last_error(h));
@@ -360,7 +370,7 @@ inline int BuildSubmapEdges(const Args& a, const std::vector<std::string>& files
 // device and downloaded, then smhip::SaveTrajectoriesAsMapPackage over them; the pieces' voxel maps take the --map-* settings.  The
 // plan is made from the poses alone before any device work: a refused plan ends the run with 2, and so does a directory the
 // description cannot be written into.  Returns 0, or 3 when the device refused a submap or an insert or a piece could not be written
-// (this run's files are then removed).
+// (this run's files are then removed).  --map-compensate 1: the submaps are built from frames de-skewed by SweepMotions(poses).
 inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files, int n_frames, const std::vector<Pose>& poses, int device, std::string* fields) {
   const auto t0 = std::chrono::steady_clock::now();
   const int N = a.submap_frames, S = n_frames / N;                        // a trailing group that is not full is dropped
@@ -380,8 +390,10 @@ inline int BuildMapPackage(const Args& a, const std::vector<std::string>& files,
   int rc = 0;
   {
     SubmapFeed feed(a, files, S, N, device, "map package");     // (gone, with its device memory, before the pieces' maps are made)
+    const std::vector<Pose> motions = a.map_compensate ? smhip::SweepMotions(poses) : std::vector<Pose>();
     for (int k = 0; k < S; ++k) {
-      const int m = feed.Build(k, LocalPosesAsWritten(poses, k, N).data());
+      // (a vector of Pose is 16 doubles per frame, one after the other: frames kN .. kN + N - 1 are the submap's)
+      const int m = feed.Build(k, LocalPosesAsWritten(poses, k, N).data(), a.map_compensate ? motions[static_cast<size_t>(k) * N].data() : nullptr);
       if (m < 0) { rc = 3; break; }
       smhip::MapPackageSubmap& sub = submaps[static_cast<size_t>(k)];
       std::memcpy(sub.global_pose.data(), poses[k * N].data(), sizeof(double) * 16);
@@ -752,6 +764,7 @@ inline int RunPasses(const Args& a, const std::vector<std::string>& files, int n
   if (rc == 0 && !a.submap_edges.empty()) rc = BuildSubmapEdges(a, files, n_frames, poses, device, fields);
   if (rc == 0 && !a.close_loops.empty()) rc = CloseLoops(a, files, n_frames, poses, device, fields);
   if (rc == 0 && !a.map_package.empty()) rc = BuildMapPackage(a, files, n_frames, poses, device, fields);
+  if (rc == 0 && a.map_compensate) *fields += ", \"map_compensated\": 1";
   return rc;
 }
 

@@ -24,6 +24,9 @@
 // Three more for the map package (builder/map_package.cc:143-198): the clipped insert (mrvm_clip_flags, a scan, mrvm_transform_kept),
 // the SORTED output cut to a box and moved to its centre (mrvm_row_counts_clipped, mrvm_sorted_rows_clipped), and mrvm_clear_table,
 // which empties the map for the next piece without giving the table back.
+//
+// And one for the map built after the trajectory is final: the compensated insert (mrvm_transform_comp), mrvm_transform with the
+// row de-skewed by the sensor's motion during the sweep first.
 #include <cstring>
 #include <string.h>
 
@@ -37,6 +40,7 @@
 #include <vector>
 
 #include "../../include/smhip.h"
+#include "motion_comp_point.h"
 
 namespace {
 
@@ -57,7 +61,7 @@ struct MrvmDev {
   int32_t* touched;             // [T] voxels with a hit or a miss in the current cloud
   uint32_t* counters;           // 0 touched (this insert), 1 voxels in the table, 2 flags: bit 0 = a point of THIS insert lies beyond the
                                 // coordinate range (reset per insert), bit 1 = table full (sticky: a voxel was lost), 3 output rows,
-                                // 4 dump rows, 5 points of this insert skipped for their coordinates
+                                // 4 dump rows, 5 points of this insert skipped for their coordinates, 6 the compensated insert's factor flag
   const uint8_t* tables;        // hit map [256], miss map [256]
   const float* cloud;           // [n][5] the current cloud (InnerPointType rows)
   int32_t* endslot;             // [n]
@@ -138,6 +142,34 @@ __global__ __launch_bounds__(256) void mrvm_transform(const float* raw, int stri
     o[i] = ((t.m[4 * i] * x + t.m[4 * i + 1] * y) + t.m[4 * i + 2] * z) + t.m[4 * i + 3];
   o[3] = r[3] * scale;                           // intensity (kitti_reader.cc:113 scales by 255)
   o[4] = stride > 4 ? r[4] : 0.f;                // factor
+}
+
+// The compensated insert (smhip_mrvm_insert_compensated_f32): MotionCompensation (map_builder.cc:232-257; motion_comp_point.h, the
+// arithmetic filt_motion_comp has) of the raw row under the sensor's motion during the frame's sweep, each coordinate rounded to
+// float as a stored de-skewed cloud would hold it, then mrvm_transform's TransformPoint -- the de-skewed cloud itself is never
+// stored.  The factor is the row's fifth float, or for 4-float rows the collector's i / n (data_collector.h:202-204), and is carried
+// into the world row.  A factor outside [0, 1] or NaN (CHECK(factor >= 0. && factor <= 1.), common/math.h:202) raises *bad by a
+// plain store; the host reads it before any kernel that writes the table runs.
+__global__ __launch_bounds__(256) void mrvm_transform_comp(const float* raw, int stride, int n, MrvmPose t, smhip::MotionCompArgs a, float scale,
+                                                           float* cloud, uint32_t* bad) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float* r = raw + (size_t)stride * j;
+  float x = r[0], y = r[1], z = r[2];
+  const float f = stride > 4 ? r[4] : (float)((double)j / (double)n);
+  if (smhip::motion_comp_factor_ok(f)) {
+    const float3 q = smhip::motion_comp_point(a, x, y, z, f);
+    x = q.x; y = q.y; z = q.z;
+  } else {
+    *bad = 1u;                                   // (every writer stores the same value)
+  }
+  float* o = cloud + 5 * (size_t)j;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    o[i] = ((t.m[4 * i] * x + t.m[4 * i + 1] * y) + t.m[4 * i + 2] * z) + t.m[4 * i + 3];
+  o[3] = r[3] * scale;
+  o[4] = f;
 }
 
 // The clipped insert of the map package (builder/map_package.cc:169-179): only the rows whose TRANSFORMED x, y lie in the closed
@@ -651,8 +683,10 @@ void smhip_mrvm_set_offset_z(smhip_mrvm_handle h, float offset) { if (h) h->set.
 // world-frame rows on the device.
 // clip != nullptr (with a pose): the map package's clipped insert -- the rows are flagged and counted before anything of the map
 // is touched, and with none kept the call returns there; otherwise the insert runs over the *n_kept rows mrvm_transform_kept wrote.
+// comp != nullptr (with a pose, no clip): the compensated insert -- mrvm_transform_comp writes the world rows and its factor flag is
+// read before anything of the map is touched (one synchronise the plain insert does not have); a bad factor returns there.
 static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int stride_floats, int n, const float origin[3], const MrvmPose* pose,
-                                float intensity_scale, const MrvmBox* clip = nullptr, int* n_kept = nullptr) {
+                                float intensity_scale, const MrvmBox* clip = nullptr, int* n_kept = nullptr, const smhip::MotionCompArgs* comp = nullptr) {
   if (n > h->max_cloud) { h->err = "cloud larger than max_cloud_points"; return SMHIP_ERR_CAPACITY; }
   {   // every ray starts at the origin: a non-finite or far-away one would walk ~2^21 voxels per ray for nothing.  Checked before
       // anything is touched, so a refused cloud leaves the map as it was.
@@ -690,10 +724,24 @@ static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int st
     if (kept <= 0) return SMHIP_OK;                         // no insert at all (map_package.cc:177-180): the map is as it was
     n = kept;
   }
+  if (comp) {                                               // counters[6]: the factor flag, no other kernel's
+    std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);
+    MCHK(h, hipMemcpyAsync(h->raw_dev, h->stage, sizeof(float) * (size_t)stride_floats * n, hipMemcpyHostToDevice, h->stream));
+    MCHK(h, hipMemsetAsync(h->d.counters + 6, 0, 4, h->stream));
+    hipLaunchKernelGGL(mrvm_transform_comp, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->raw_dev, stride_floats, n, *pose, *comp, intensity_scale,
+                       h->cloud_dev, h->d.counters + 6);
+    MCHK(h, hipGetLastError());
+    MCHK(h, hipMemcpyAsync(h->counters_host + 9, h->d.counters + 6, 4, hipMemcpyDeviceToHost, h->stream));
+    MCHK(h, hipStreamSynchronize(h->stream));
+    if (h->counters_host[9] != 0u) {
+      h->err = "a row's factor is outside [0, 1] or NaN (CHECK(factor >= 0. && factor <= 1.), common/math.h:202): cloud refused";
+      return SMHIP_ERR_INVALID_ARGUMENT;
+    }
+  }
   h->voxels_stale = true;
   mrvm_grow_for(h, n);                                      // room for the voxels this cloud can add, like the reference's std::map
   if (pose) {
-    if (!clip) std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);   // (clipped: the raw rows are on the device already)
+    if (!clip && !comp) std::memcpy(h->stage, points, sizeof(float) * (size_t)stride_floats * n);   // (clipped, compensated: the raw rows are on the device already)
   } else {
     for (int i = 0; i < n; ++i) {
       const float* r = points + (size_t)stride_floats * i;
@@ -708,10 +756,10 @@ static smhip_status mrvm_insert(smhip_mrvm_handle h, const float* points, int st
   if (clip) {                                               // the flags and their scan are still in run_start / scan_out: both are rewritten below
     hipLaunchKernelGGL(mrvm_transform_kept, dim3((n_raw + 255) / 256), b, 0, h->stream, h->raw_dev, stride_floats, n_raw, *pose, intensity_scale,
                        h->d.run_start, h->scan_out, h->cloud_dev);
-  } else if (pose) {
+  } else if (pose && !comp) {                               // (compensated: mrvm_transform_comp has written the world rows above)
     MCHK(h, hipMemcpyAsync(h->raw_dev, h->stage, sizeof(float) * (size_t)stride_floats * n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(mrvm_transform, g, b, 0, h->stream, h->raw_dev, stride_floats, n, *pose, intensity_scale, h->cloud_dev);
-  } else {
+  } else if (!pose) {
     MCHK(h, hipMemcpyAsync(h->cloud_dev, h->stage, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   }
   hipLaunchKernelGGL(mrvm_begin, dim3(1), dim3(1), 0, h->stream, d);                                    // touched count, this cloud's flags
@@ -767,6 +815,24 @@ smhip_status smhip_mrvm_insert_transformed_f32(smhip_mrvm_handle h, const float*
     for (int c = 0; c < 4; ++c) t.m[4 * r + c] = static_cast<float>(pose[4 * c + r]);                  // transform.cast<float>()
   const float origin[3] = {t.m[3], t.m[7], t.m[11]};                                                 // GlobalTranslation().cast<float>()
   return mrvm_insert(h, rows, stride_floats, n, origin, &t, intensity_scale);
+}
+
+smhip_status smhip_mrvm_insert_compensated_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],
+                                               const double motion[16], float intensity_scale) {
+  if (!h || !pose) return SMHIP_ERR_INVALID_ARGUMENT;
+  if (!motion) { h->err = "null motion"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (!rows || n <= 0) { h->err = "cloud is empty."; return SMHIP_ERR_INVALID_ARGUMENT; }
+  if (stride_floats != 4 && stride_floats != 5) { h->err = "raw rows are x y z intensity [factor]: stride 4 or 5"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 16; ++k) {
+    if (!std::isfinite(pose[k])) { h->err = "pose is not finite: cloud refused"; return SMHIP_ERR_INVALID_ARGUMENT; }
+    if (!std::isfinite(motion[k])) { h->err = "motion is not finite: cloud refused"; return SMHIP_ERR_INVALID_ARGUMENT; }
+  }
+  MrvmPose t;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) t.m[4 * r + c] = static_cast<float>(pose[4 * c + r]);
+  const float origin[3] = {t.m[3], t.m[7], t.m[11]};                                                 // the ray origin stays the pose's translation
+  const smhip::MotionCompArgs a = smhip::motion_comp_args(motion);
+  return mrvm_insert(h, rows, stride_floats, n, origin, &t, intensity_scale, nullptr, nullptr, &a);
 }
 
 smhip_status smhip_mrvm_insert_transformed_clipped_f32(smhip_mrvm_handle h, const float* rows, int stride_floats, int n, const double pose[16],

@@ -77,6 +77,27 @@ class MultiResolutionVoxelMapHip:
         self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
         self.last_skipped = n.value
 
+    def insert_compensated(self, rows, pose, motion, intensity_scale: float = 1.0):
+        """insert_transformed of the frame de-skewed by `motion` [4, 4], the sensor's motion during its sweep (inv(pose) @ the next
+        frame's pose), `pose` being the sensor pose at the start of the sweep: MotionCompensation (map_builder.cc:232-257) per row,
+        the coordinates rounded to float, then TransformPoint -- one kernel, the de-skewed cloud is never stored.  The factor is
+        rows[:, 4], or float32(i / N) for [N, 4] rows, and is stored with the point.  A factor outside [0, 1] or NaN raises and
+        leaves the map bit for bit as it was."""
+        p = np.ascontiguousarray(rows, dtype=np.float32)
+        T = np.asarray(pose, dtype=np.float64)
+        M = np.asarray(motion, dtype=np.float64)
+        if p.ndim != 2 or T.shape != (4, 4) or M.shape != (4, 4):
+            raise ValueError("rows must be [N, 4|5], pose and motion [4, 4]")
+        cm = np.ascontiguousarray(T.T).ravel()
+        mm = np.ascontiguousarray(M.T).ravel()
+        self._check(self._lib.smhip_mrvm_insert_compensated_f32(self._h, p.ctypes.data_as(_capi.c_float_p), p.shape[1], p.shape[0],
+                                                                cm.ctypes.data_as(_capi.c_double_p), mm.ctypes.data_as(_capi.c_double_p),
+                                                                float(intensity_scale)))
+        self.last_warning = self._lib.smhip_mrvm_last_error(self._h).decode()
+        n = ctypes.c_int32()
+        self._lib.smhip_mrvm_last_skipped(self._h, ctypes.byref(n))
+        self.last_skipped = n.value
+
     def insert_transformed_clipped(self, rows, pose, bb_min, bb_max, intensity_scale: float = 1.0) -> int:
         """insert_transformed of the rows whose transformed x, y lie in the closed box [bb_min, bb_max] (builder/map_package.cc:169-179;
         float coordinates against double bounds, a NaN fails), in their order.  Returns the number of rows kept; with none the map is

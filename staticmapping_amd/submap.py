@@ -18,7 +18,7 @@ def text_voxel_size(voxel_size: float) -> float:
     return float(np.float32(float("%f" % float(np.float32(voxel_size)))))
 
 
-def _launch(matcher, frames, local_poses, voxel_size) -> int:
+def _launch(matcher, frames, local_poses, voxel_size, motions=None) -> int:
     arrs = [np.ascontiguousarray(np.asarray(f, dtype=np.float32)) for f in frames]
     strides = {a.shape[1] for a in arrs if a.ndim == 2}
     if any(a.ndim != 2 for a in arrs) or len(strides) > 1:
@@ -31,15 +31,25 @@ def _launch(matcher, frames, local_poses, voxel_size) -> int:
     n = np.ascontiguousarray([len(a) for a in arrs], dtype=np.int32)
     rows = (_capi.c_float_p * max(1, k))(*[a.ctypes.data_as(_capi.c_float_p) for a in arrs])
     n_out = ctypes.c_int()
-    matcher._check(matcher._lib.smhip_submap_build_f32(matcher._h, k, rows, stride, n.ctypes.data_as(_capi.c_int32_p),
-                                                       poses.ctypes.data_as(_capi.c_double_p), float(voxel_size), ctypes.byref(n_out)))
+    if motions is None:
+        matcher._check(matcher._lib.smhip_submap_build_f32(matcher._h, k, rows, stride, n.ctypes.data_as(_capi.c_int32_p),
+                                                           poses.ctypes.data_as(_capi.c_double_p), float(voxel_size), ctypes.byref(n_out)))
+        return n_out.value
+    mot = np.ascontiguousarray([np.asarray(M, dtype=np.float64).T.reshape(16) for M in motions], dtype=np.float64).reshape(-1)
+    if len(mot) != 16 * k:
+        raise ValueError("one 4x4 sweep motion per frame")
+    matcher._check(matcher._lib.smhip_submap_build_compensated_f32(matcher._h, k, rows, stride, n.ctypes.data_as(_capi.c_int32_p),
+                                                                   poses.ctypes.data_as(_capi.c_double_p), mot.ctypes.data_as(_capi.c_double_p),
+                                                                   float(voxel_size), ctypes.byref(n_out)))
     return n_out.value
 
 
-def build_submap_resident(matcher, frames, local_poses, voxel_size: float = 0.0) -> int:
+def build_submap_resident(matcher, frames, local_poses, voxel_size: float = 0.0, motions=None) -> int:
     """Submap::InsertFrame's cloud for a full submap, left on the device as the filter workspace's current cloud; returns its
-    size.  Follow with output_to_target() / filters.output_to_source() or read it with get_submap()."""
-    return _launch(matcher, frames, local_poses, voxel_size)
+    size.  Follow with output_to_target() / filters.output_to_source() or read it with get_submap().  motions: one 4x4 per frame,
+    the sensor's motion during that frame's sweep -- every frame is de-skewed by it before its local pose is applied
+    (smhip_submap_build_compensated_f32)."""
+    return _launch(matcher, frames, local_poses, voxel_size, motions)
 
 
 def get_submap(matcher, n: int):
@@ -51,10 +61,11 @@ def get_submap(matcher, n: int):
     return out, src
 
 
-def build_submap(matcher, frames, local_poses, voxel_size: float = 0.0):
+def build_submap(matcher, frames, local_poses, voxel_size: float = 0.0, motions=None):
     """frames: float32 [n_k, 4] (KITTI rows; factor = i / n_k) or [n_k, 5] arrays; local_poses: one 4x4 per frame (frame ->
-    first frame); voxel_size 0 = enable_voxel_filter false.  Returns (cloud [M, 5] float32, source_index [M] int32)."""
-    return get_submap(matcher, _launch(matcher, frames, local_poses, voxel_size))
+    first frame); voxel_size 0 = enable_voxel_filter false; motions: as build_submap_resident.  Returns (cloud [M, 5] float32,
+    source_index [M] int32)."""
+    return get_submap(matcher, _launch(matcher, frames, local_poses, voxel_size, motions))
 
 
 def output_to_target(matcher, slot: int = 0) -> int:
@@ -75,6 +86,7 @@ class SubmapBuilder:
         self.frame_count, self.enable_voxel_filter, self.voxel_size = int(frame_count), bool(enable_voxel_filter), float(voxel_size)
         self.frames, self.local_poses = [], []
         self.global_pose = None
+        self.motions = None                                               # set_motions: the frames are de-skewed when the cloud is built
 
     def full(self) -> bool:
         return len(self.frames) == self.frame_count
@@ -90,6 +102,10 @@ class SubmapBuilder:
             self.local_poses.append(np.linalg.inv(self.global_pose) @ P)  # :87
         self.frames.append(np.ascontiguousarray(np.asarray(cloud, dtype=np.float32)))
 
+    def set_motions(self, motions):
+        """One 4x4 per frame, the sensor's motion during that frame's sweep (None: no compensation)."""
+        self.motions = None if motions is None else [np.asarray(M, dtype=np.float64) for M in motions]
+
     def first_frame_pose(self):
         return self.global_pose
 
@@ -102,7 +118,7 @@ class SubmapBuilder:
     def build_resident(self, matcher) -> int:
         if not self.full():
             raise RuntimeError("the submap is not full: it has no cloud yet")
-        return build_submap_resident(matcher, self.frames, self.local_poses, self.device_voxel_size())
+        return build_submap_resident(matcher, self.frames, self.local_poses, self.device_voxel_size(), self.motions)
 
     def cloud(self, matcher):
         """Submap::Cloud() without its normals: (rows [M, 5], source_index [M])."""
