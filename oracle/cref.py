@@ -40,7 +40,18 @@ def lib():
         _LIB.smref_calculate_normals.restype = ctypes.c_int
         _LIB.smref_normals_partition.argtypes = [dp, ctypes.c_int, ip, ip, ip]
         _LIB.smref_normals_partition.restype = ctypes.c_int
+        _LIB.smref_solve6.argtypes = [dp, dp, dp]
+        _LIB.smref_solve6.restype = ctypes.c_int
     return _LIB
+
+
+def solve6(A, b):
+    """The C restatement's SolvePossiblyUnderdeterminedLinearSystem on one 6x6 -> (x, the rank it solved at; 6 = Cholesky)."""
+    A, pa = _d(np.asarray(A).reshape(6, 6))
+    b, pb = _d(b)
+    x = np.zeros(6)
+    rank = lib().smref_solve6(pa, pb, x.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return x, rank
 
 
 def _d(a):

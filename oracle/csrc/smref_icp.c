@@ -272,7 +272,7 @@ void jacobi_eig(int n, double* A /*n*n, destroyed*/, double* V, double* w) {
 }
 
 /* icp_fast.cc:204-254: invertible -> Cholesky; else min-norm (pseudo-inverse) */
-static void solve_possibly_underdetermined6(const double* A, const double* b, double* x) {
+static int solve_possibly_underdetermined6(const double* A, const double* b, double* x) {
   double E[36], V[36], w[6];
   memcpy(E, A, sizeof(E));
   jacobi_eig(6, E, V, w);
@@ -296,7 +296,7 @@ static void solve_possibly_underdetermined6(const double* A, const double* b, do
       double y[6];
       for (int i = 0; i < 6; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s -= L[6 * i + k] * y[k]; y[i] = s / L[6 * i + i]; }
       for (int i = 5; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < 6; ++k) s -= L[6 * k + i] * x[k]; x[i] = s / L[6 * i + i]; }
-      return;
+      return 6;
     }
   }
   for (int i = 0; i < 6; ++i) x[i] = 0;
@@ -307,6 +307,12 @@ static void solve_possibly_underdetermined6(const double* A, const double* b, do
     c /= w[k];
     for (int i = 0; i < 6; ++i) x[i] += c * V[6 * i + k];
   }
+  return rank < 6 ? rank : 5;   /* rank 6 here: Cholesky broke down */
+}
+
+/* the 6x6 solve alone, for the tests that pin it on constructed matrices: returns the rank it solved at (6 = Cholesky) */
+int smref_solve6(const double* A, const double* b, double* x) {
+  return solve_possibly_underdetermined6(A, b, x);
 }
 
 static void angle_axis_to_T(const double x[6], double T[16]) { /* icp_fast.cc:306-321 */

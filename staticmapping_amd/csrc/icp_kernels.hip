@@ -21,6 +21,7 @@
 #include "smhip_device.h"
 #include "kd_median_tree.h"
 #include "grid_lookup.h"
+#include "icp_tail_math.h"
 
 namespace smhip {
 
@@ -3373,111 +3374,8 @@ __global__ __launch_bounds__(kAccThreads) void accumulate_listed(IcpDev b) {
 // ------------------------------------------------------------------------------------------
 // K4: exact quantile, solve, update, convergence
 // ------------------------------------------------------------------------------------------
-__device__ __noinline__ void jacobi_eig6(double* A, double* V, double* w) {
-  for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) V[6 * i + j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0;
-    for (int i = 0; i < 6; ++i) for (int j = i + 1; j < 6; ++j) off += A[6 * i + j] * A[6 * i + j];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 6; ++p)
-      for (int q = p + 1; q < 6; ++q) {
-        const double apq = A[6 * p + q];
-        if (fabs(apq) < 1e-300) continue;
-        const double theta = (A[6 * q + q] - A[6 * p + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 6; ++k) { const double akp = A[6 * k + p], akq = A[6 * k + q]; A[6 * k + p] = c * akp - s * akq; A[6 * k + q] = s * akp + c * akq; }
-        for (int k = 0; k < 6; ++k) { const double apk = A[6 * p + k], aqk = A[6 * q + k]; A[6 * p + k] = c * apk - s * aqk; A[6 * q + k] = s * apk + c * aqk; }
-        for (int k = 0; k < 6; ++k) { const double vkp = V[6 * k + p], vkq = V[6 * k + q]; V[6 * k + p] = c * vkp - s * vkq; V[6 * k + q] = s * vkp + c * vkq; }
-      }
-  }
-  for (int i = 0; i < 6; ++i) w[i] = A[6 * i + i];
-}
-
-// SolvePossiblyUnderdeterminedLinearSystem (icp_fast.cc:204-254): Cholesky when A is numerically
-// invertible, otherwise the minimum-norm solution of the rank-reduced system (pseudo-inverse).
-__device__ __forceinline__ void solve6(const double* A, const double* rhs, double* x) {
-  // fully unrolled so that L lives in registers: with run-time indices it sits in scratch memory and every access is a
-  // memory round trip (the serial tail of finalize took 9-19 us that way)
-  double L[36];
-  double dmax = 0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dmax = fmax(dmax, fabs(A[6 * i + i]));
-  bool ok = dmax > 0 && isfinite(dmax);
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      double s = A[6 * i + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[6 * i + k] * L[6 * j + k];
-      if (i == j) {
-        ok = ok && (s > 1e-13 * dmax);
-        L[6 * i + i] = sqrt(s);
-      } else {
-        L[6 * i + j] = s / L[6 * j + j];
-      }
-    }
-  if (ok) {
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      double s = rhs[i];
-#pragma unroll
-      for (int k = 0; k < i; ++k) s -= L[6 * i + k] * y[k];
-      y[i] = s / L[6 * i + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-      double s = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 6; ++k) s -= L[6 * k + i] * x[k];
-      x[i] = s / L[6 * i + i];
-    }
-    return;
-  }
-  double E[36], V[36], w[6];
-#pragma unroll
-  for (int i = 0; i < 36; ++i) E[i] = A[i];
-  jacobi_eig6(E, V, w);
-  double wmax = 0;
-  for (int i = 0; i < 6; ++i) wmax = fmax(wmax, fabs(w[i]));
-  const double thresh = 2.220446049250313e-16 * 6 * wmax;
-  for (int i = 0; i < 6; ++i) x[i] = 0;
-  for (int k = 0; k < 6; ++k) {
-    if (!(fabs(w[k]) > thresh)) continue;
-    double c = 0;
-    for (int i = 0; i < 6; ++i) c += V[6 * i + k] * rhs[i];
-    c /= w[k];
-    for (int i = 0; i < 6; ++i) x[i] += c * V[6 * i + k];
-  }
-}
-
-__device__ void quat_from_rot(const double* T, double* q) {   // Eigen::Quaterniond(Matrix3d), T row-major 4x4
-  const double r00 = T[0], r01 = T[1], r02 = T[2], r10 = T[4], r11 = T[5], r12 = T[6], r20 = T[8], r21 = T[9], r22 = T[10];
-  const double tr = r00 + r11 + r22;
-  if (tr > 0) {
-    const double s = sqrt(tr + 1.0) * 2;
-    q[0] = 0.25 * s; q[1] = (r21 - r12) / s; q[2] = (r02 - r20) / s; q[3] = (r10 - r01) / s;
-  } else if (r00 >= r11 && r00 >= r22) {
-    const double s = sqrt(1.0 + r00 - r11 - r22) * 2;
-    q[0] = (r21 - r12) / s; q[1] = 0.25 * s; q[2] = (r01 + r10) / s; q[3] = (r02 + r20) / s;
-  } else if (r11 >= r22) {
-    const double s = sqrt(1.0 + r11 - r00 - r22) * 2;
-    q[0] = (r02 - r20) / s; q[1] = (r01 + r10) / s; q[2] = 0.25 * s; q[3] = (r12 + r21) / s;
-  } else {
-    const double s = sqrt(1.0 + r22 - r00 - r11) * 2;
-    q[0] = (r10 - r01) / s; q[1] = (r02 + r20) / s; q[2] = (r12 + r21) / s; q[3] = 0.25 * s;
-  }
-}
-
-__device__ double quat_angular_distance(const double* a, const double* c) {
-  const double w = a[0] * c[0] + a[1] * c[1] + a[2] * c[2] + a[3] * c[3];
-  const double x = -a[0] * c[1] + a[1] * c[0] - a[2] * c[3] + a[3] * c[2];
-  const double y = -a[0] * c[2] + a[2] * c[0] - a[3] * c[1] + a[1] * c[3];
-  const double z = -a[0] * c[3] + a[3] * c[0] - a[1] * c[2] + a[2] * c[1];
-  return 2.0 * atan2(sqrt(x * x + y * y + z * z), fabs(w));
-}
+// (jacobi_eig6, solve6, quat_from_rot, quat_angular_distance, the angle-axis step, the motion-potential bound and CheckConvergence:
+// icp_tail_math.h, which a host compiler reads too)
 
 // The serial end of an iteration, on ONE thread: the iteration's counters folded into the totals, the next search radius and
 // quantile band, the 6x6 solve, the pose update with its motion potential, CheckConvergence and -- when the loop ends -- the result
@@ -3560,81 +3458,17 @@ __device__ __forceinline__ uint32_t finalize_tail(const B& b, PairState* st, int
   solve6(A, rhs, x);                                                          // :304
   // transform = AngleAxis(|x[0:3]|, x[0:3] / |x[0:3]|), translation = x[3:6]    :306-312
   double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  {
-    const double ang = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    const double ax = x[0] / ang, ay = x[1] / ang, az = x[2] / ang;
-    const double c = cos(ang), s = sin(ang), v = 1.0 - c;
-    double R[9] = {c + v * ax * ax, v * ax * ay - s * az, v * ax * az + s * ay,
-                   v * ax * ay + s * az, c + v * ay * ay, v * ay * az - s * ax,
-                   v * ax * az - s * ay, v * ay * az + s * ax, c + v * az * az};
-    bool has_nan = false;
-    for (int i = 0; i < 9; ++i) has_nan |= isnan(R[i]);
-    for (int i = 0; i < 3; ++i) has_nan |= isnan(x[3 + i]);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) dT[4 * i + j] = has_nan ? ((i == j) ? 1.0 : 0.0) : R[3 * i + j];   // :315-321
-    dT[3] = x[3]; dT[7] = x[4]; dT[11] = x[5];
-  }
+  angle_axis_step(x, dT);                                                     // :315-321
   double Tn[16];
   mat4_mul_rm(dT, st->T_iter, Tn);                                            // :506-510
   for (int i = 0; i < 16; ++i) st->T_iter[i] = Tn[i];
   double Mn[16];
   mat4_mul_rm(Tn, st->G, Mn);
-  {   // motion potential: this step's ||dR|| and |dt| (what bounds |M_new s - M_old s| <= ||dR|| |s| + |dt|), and their running sums.
-      // ||dR|| is the SPECTRAL norm of the 3x3 difference (the largest singular value: what |dR s| <= ||dR|| |s| needs), from the
-      // closed-form largest eigenvalue of dR^T dR with 1e-6 of slack and never more than the Frobenius norm; for the difference of
-      // two rotations the Frobenius norm is sqrt(2) times larger, and with it sqrt(2) times the certified motion of far points.
-    double D[9], fa = 0, fb = 0;
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) { D[3 * r + c] = Mn[4 * r + c] - st->M[4 * r + c]; fa += D[3 * r + c] * D[3 * r + c]; }
-      const double d = Mn[4 * r + 3] - st->M[4 * r + 3];
-      fb += d * d;
-    }
-    double S[6];                                           // D^T D: xx xy xz yy yz zz
-    S[0] = D[0] * D[0] + D[3] * D[3] + D[6] * D[6]; S[1] = D[0] * D[1] + D[3] * D[4] + D[6] * D[7]; S[2] = D[0] * D[2] + D[3] * D[5] + D[6] * D[8];
-    S[3] = D[1] * D[1] + D[4] * D[4] + D[7] * D[7]; S[4] = D[1] * D[2] + D[4] * D[5] + D[7] * D[8]; S[5] = D[2] * D[2] + D[5] * D[5] + D[8] * D[8];
-    double lam = fa;                                       // trace = squared Frobenius norm >= the largest eigenvalue
-    {
-      const double q = (S[0] + S[3] + S[5]) / 3.0;
-      const double p1 = S[1] * S[1] + S[2] * S[2] + S[4] * S[4];
-      const double p2 = (S[0] - q) * (S[0] - q) + (S[3] - q) * (S[3] - q) + (S[5] - q) * (S[5] - q) + 2.0 * p1;
-      if (p2 > 0.0 && isfinite(p2)) {
-        const double p = sqrt(p2 / 6.0), ip = 1.0 / p;
-        const double b0 = (S[0] - q) * ip, b3 = (S[3] - q) * ip, b5 = (S[5] - q) * ip, b1 = S[1] * ip, b2 = S[2] * ip, b4 = S[4] * ip;
-        double r = 0.5 * (b0 * (b3 * b5 - b4 * b4) - b1 * (b1 * b5 - b4 * b2) + b2 * (b1 * b4 - b3 * b2));
-        r = fmin(1.0, fmax(-1.0, r));
-        const double est = (q + 2.0 * p * cos(acos(r) / 3.0)) * (1.0 + 2e-6) + 1e-300;
-        if (isfinite(est) && est > 0.0) lam = fmin(lam, est);
-      } else if (p2 == 0.0) {
-        lam = fmin(lam, q * (1.0 + 2e-6));
-      }
-    }
-    st->step_a = sqrt(lam) * (1.0 + 1e-9); st->step_b = sqrt(fb) * (1.0 + 1e-9);
-    st->pot_a += st->step_a; st->pot_b += st->step_b;
-  }
+  motion_potential_step(Mn, st->M, &st->step_a, &st->step_b);              // this step's ||dR|| and |dt|, and their running sums
+  st->pot_a += st->step_a; st->pot_b += st->step_b;
   for (int i = 0; i < 12; ++i) { st->M_prev[i] = st->M[i]; st->M[i] = Mn[i]; }
   const int it = ++st->iter;                                                  // :513
-  // history ring (latest at n_hist-1, at most 5 kept)
-  int nh = st->n_hist;
-  if (nh == 5) {
-    for (int k = 0; k < 4; ++k) {
-      for (int c = 0; c < 4; ++c) st->quat[k][c] = st->quat[k + 1][c];
-      for (int c = 0; c < 3; ++c) st->trans[k][c] = st->trans[k + 1][c];
-    }
-    nh = 4;
-  }
-  quat_from_rot(Tn, st->quat[nh]);
-  st->trans[nh][0] = Tn[3]; st->trans[nh][1] = Tn[7]; st->trans[nh][2] = Tn[11];
-  st->n_hist = ++nh;
-  bool converged = false;
-  if (b.early_exit && nh > 4) {                                               // :377-405 (kSmoothLength = 4)
-    double rd = 0, td = 0;
-    for (int k = nh - 1; k >= nh - 4; --k) {
-      rd += fabs(quat_angular_distance(st->quat[k], st->quat[k - 1]));
-      const double dx = st->trans[k][0] - st->trans[k - 1][0], dy = st->trans[k][1] - st->trans[k - 1][1], dz = st->trans[k][2] - st->trans[k - 1][2];
-      td += sqrt(dx * dx + dy * dy + dz * dz);
-    }
-    converged = (rd / 4 < 1e-3) && (td / 4 < 1e-2);
-  }
+  const bool converged = history_push_converged(st->quat, st->trans, &st->n_hist, Tn, b.early_exit != 0);   // :377-405
   if (converged || it >= b.max_iteration) {                                   // :516-522
     // (the score of this iteration's kept matches, :518-521, is formed by final_score once the batch has left its loop)
     // result = T_mean * T_iter * T_mean^-1 * guess  (:527), written column-major
