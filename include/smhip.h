@@ -828,6 +828,51 @@ smhip_status smhip_pose_graph_optimize_info(smhip_handle h, int n_nodes, double*
                                             const uint8_t* kinds, const int32_t* ij, const double* data, const double* sigmas,
                                             const double* huber, const int32_t* info_index, const double* sqrt_info,
                                             const smhip_pose_graph_options* opts, smhip_pose_graph_stats* stats);
+/* Marginal covariances ("Marginal covariances"; tests/pose_graph_marginals_ref.py): how well each pose is known --
+ * what the reference asks of gtsam::Marginals::marginalCovariance (back_end/isam_optimizer.h:32).
+ *   H = sum_f w_f J_f^T J_f is the Gauss-Newton matrix of the LAST optimise call on the handle, whichever of the five entries it was:
+ *   the rows whitened (Huber weights and square-root informations applied as the linearisation applies them), at the poses that call's
+ *   loop ENDED at (the state smhip_pose_graph_last_robust reports on), lambda = 0, fixed nodes left out.
+ *   For a free node k:  Sigma_k = (X + X^T) / 2 with X = [H^-1]_kk, a 6x6 in the optimiser's tangent chart, rotation first:
+ *   R <- R Exp(dw), t <- t + R dv, so its translation part is in the node's BODY frame; the world-frame position covariance is
+ *   R_k Sigma_vv R_k^T.  For a fixed node Sigma_k = 0.  Cross blocks [H^-1]_{r,k} (row node r, column node k) come from the same
+ *   solves, unsymmetrised; a cross block with a fixed node is 0.
+ * Covariances are relative to the gauge: the held nodes, or the PRIOR factors.  With node 0 held, Sigma_k says how well node k is
+ * known relative to node 0, not in the world.
+ * Column c of node k solves H x = e_{6k+c} by the optimiser's own conjugate gradients from x = 0, preconditioned by the
+ * block-tridiagonal part of H, stopped at r^T M^-1 r <= (1e-10)^2 r0^T M^-1 r0 and capped at that call's pcg_cap.  Two launches: one
+ * workgroup linearises and factors, then min(n_query, max_workgroups) workgroups take the queries w, w + G, w + 2G, ..., six solves
+ * each.  A query's bits do not depend on the workgroup that ran it, on max_workgroups or on what else was queried.
+ * query: n_query node indices (repeats allowed); cov: 36 doubles per query, row-major.  rows: n_rows node indices and blocks:
+ * n_query x n_rows x 36 doubles, block (q, r) = [H^-1]_{rows[r], query[q]}, row-major; n_rows 0 with NULLs for none.  opts: NULL =
+ * defaults; stats: may be NULL.  The poses, and what smhip_pose_graph_last and smhip_pose_graph_last_robust return afterwards, are
+ * not changed.  The workspace, (7 x 6 n_nodes + 6 n_factors) doubles per workgroup, is grown to fit a call and never shrunk.
+ * Refused before anything is touched, nothing written --
+ *   SMHIP_ERR_NOT_READY: no optimise call reached its launch, or the last one ended NUMERIC;
+ *   SMHIP_ERR_INVALID_ARGUMENT: n_nodes is not the last call's, n_query < 1, a null query or cov, an index out of range, n_rows > 0
+ *     with a null rows or blocks, max_workgroups < 0;
+ *   SMHIP_ERR_CAPACITY, from the sizes alone: ceil(n_query / G) x 6 x pcg_cap > SMHIP_POSE_GRAPH_MAX_PCG_TOTAL (ask in several calls).
+ *     max_workgroups above 4 per CU is clamped to that (a workgroup of 1024 threads fills a CU, and each costs a slice of the workspace);
+ *     cov and blocks together more than 2^27 doubles (1 GiB) are refused likewise.
+ * Found by the kernels, SMHIP_ERR_NO_MATCH with cov and blocks not written: a pivot of the factorisation that is not positive; a
+ * column whose solve ended without meeting the tolerance -- at pcg_cap, or because a sum was not positive or not finite (stats are
+ * written in this case; pcg_iterations saturates at INT32_MAX).
+ * Out of scope: using the covariances inside LoopDetector's distance gate (the obvious follow-up), a selected-inversion shortcut for
+ * the chain part, joint marginals of more than two nodes, incremental reuse between calls. */
+typedef struct smhip_pose_graph_marginals_options {
+  int32_t max_workgroups;       /* 0 = one per CU */
+  int32_t reserved[3];
+} smhip_pose_graph_marginals_options;
+typedef struct smhip_pose_graph_marginals_stats {
+  int32_t workgroups;           /* G */
+  int32_t pcg_iterations;       /* summed over every column of every query */
+  int32_t pcg_max_iterations;   /* the longest single column, <= pcg_cap */
+  int32_t pcg_cap;              /* the last optimise call's */
+} smhip_pose_graph_marginals_stats;
+void smhip_pose_graph_marginals_default_options(smhip_pose_graph_marginals_options* o);
+smhip_status smhip_pose_graph_marginals(smhip_handle h, int n_nodes, int n_query, const int32_t* query, double* cov, int n_rows,
+                                        const int32_t* rows, double* blocks, const smhip_pose_graph_marginals_options* opts,
+                                        smhip_pose_graph_marginals_stats* stats);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

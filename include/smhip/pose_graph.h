@@ -23,6 +23,10 @@
 //                                                                 Gauss-Newton at a relative error of 1e-6 (:330); here the stop
 //                                                                 rules of smhip_pose_graph_optimize apply, with max_iterations 100
 //   IsamOptimizer::GetGpsCoordTransform :370-383
+//   marginal covariances             isam_optimizer.h:32          what gtsam/nonlinear/Marginals.h is included for: PoseGraph::Marginals,
+//                                                                 IsamOptimizer::MarginalCovariance / JointMarginalCovariance / CalibCovariance /
+//                                                                 GpsCoordCovariance over smhip_pose_graph_marginals (include/smhip.h, "Marginal
+//                                                                 covariances": the chart, the gauge and what is out of scope)
 //   the odometry calibration factor  :84-93, 153-162, 209-224,    use_odom: vertex 0 brings the calibration vertex (ODOM_CALIB_KEY) at tf_odom_lidar^-1,
 //                                    361-367                      and every frame with an odometer reading a HANDEYE factor (include/smhip.h,
 //                                                                 "Odometry calibration factor") of sigmas (0.2, 0.2, 0.2, 1.5, 1.5, 2) under
@@ -306,6 +310,47 @@ class PoseGraph {
     }
     return true;
   }
+  // The graph's own node numbering, which Marginals takes: the vertices 0 .. VertexCount() - 1, then the calibration vertex (when
+  // set), then the frame vertex (when set); -1 for a vertex that is not there
+  int CalibNodeIndex() const { return has_calib_ ? static_cast<int>(poses_.size()) : -1; }
+  int FrameNodeIndex() const { return has_frame_ ? static_cast<int>(poses_.size()) + (has_calib_ ? 1 : 0) : -1; }
+  // smhip_pose_graph_marginals for the solve Optimize ran last on `handle`, with this graph as it was then (what GTSAM's
+  // Marginals::marginalCovariance answers in the reference): cov[q] = Sigma of nodes[q], 36 doubles row-major, in the optimiser's
+  // tangent chart -- rotation first, the translation part in the node's BODY frame (WorldPositionCovariance turns it) -- relative to
+  // the held vertices and the priors; zeros for a held vertex.  rows / blocks: cross blocks [H^-1]_{rows[r], nodes[q]} at
+  // blocks[q * rows->size() + r], unsymmetrised (both null: none).  false (the reason on stderr) when refused.
+  bool Marginals(smhip_handle handle, const std::vector<int>& nodes, std::vector<std::array<double, 36>>* cov, const std::vector<int>* rows = nullptr,
+                 std::vector<std::array<double, 36>>* blocks = nullptr, smhip_pose_graph_marginals_stats* stats = nullptr,
+                 const smhip_pose_graph_marginals_options* options = nullptr) const {
+    SMHIP_CHECK(handle != nullptr, "PoseGraph::Marginals needs a device handle");
+    SMHIP_CHECK(cov != nullptr && (rows == nullptr) == (blocks == nullptr), "cov, and rows with blocks or neither");
+    const std::vector<int32_t> query(nodes.begin(), nodes.end());
+    const std::vector<int32_t> row(rows ? rows->begin() : nodes.end(), rows ? rows->end() : nodes.end());
+    cov->assign(query.size(), std::array<double, 36>{});
+    if (blocks) blocks->assign(query.size() * row.size(), std::array<double, 36>{});
+    const smhip_status s = smhip_pose_graph_marginals(handle, NodeCount(), static_cast<int>(query.size()), query.data(), cov->empty() ? nullptr : (*cov)[0].data(),
+                                                      static_cast<int>(row.size()), row.empty() ? nullptr : row.data(),
+                                                      blocks && !blocks->empty() ? (*blocks)[0].data() : nullptr, options, stats);
+    if (s != SMHIP_OK) {
+      std::fprintf(stderr, "[ERROR] smhip_pose_graph_marginals: %s (%s)\n", smhip_status_string(s), smhip_last_error(handle));
+      return false;
+    }
+    return true;
+  }
+  // R_k Sigma_vv R_k^T (9 doubles, row-major) for the node `index` of the numbering above and its Sigma from Marginals
+  std::array<double, 9> WorldPositionCovariance(int index, const std::array<double, 36>& cov36) const {
+    SMHIP_CHECK(index >= 0 && index < NodeCount(), "a node that exists");
+    const Matrix4d& X = index == CalibNodeIndex() ? calib_pose_ : index == FrameNodeIndex() ? frame_pose_ : poses_[static_cast<size_t>(index)];
+    std::array<double, 9> out{};
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k)
+          for (int l = 0; l < 3; ++l) s += X(a, k) * cov36[static_cast<size_t>(6 * (3 + k) + 3 + l)] * X(b, l);
+        out[static_cast<size_t>(3 * a + b)] = s;
+      }
+    return out;
+  }
   // the C ABI's arrays: 16 doubles per pose and per measurement (column-major), index pairs, 6 sigmas per edge
   void Flatten(std::vector<double>* poses, std::vector<int32_t>* ij, std::vector<double>* Z, std::vector<double>* sigmas) const {
     poses->clear(); ij->clear(); Z->clear(); sigmas->clear();
@@ -448,6 +493,46 @@ class IsamOptimizer {
   IsamOptimizer& operator=(const IsamOptimizer&) = delete;
   void SetSolver(Solver solver) { solver_ = std::move(solver); }
   void SetReporter(Reporter reporter) { reporter_ = std::move(reporter); }
+  // TEST HOOK beside them: `marginalizer` replaces PoseGraph::Marginals, for the graph at the poses the solver left (rows and blocks
+  // both null or both set, as there)
+  using Marginalizer = std::function<bool(const PoseGraph&, const std::vector<int>& nodes, std::vector<std::array<double, 36>>* cov, const std::vector<int>* rows,
+                                          std::vector<std::array<double, 36>>* blocks)>;
+  void SetMarginalizer(Marginalizer marginalizer) { marginalizer_ = std::move(marginalizer); }
+  // What the reference would ask of gtsam::Marginals (isam_optimizer.h:32), at the poses of the last solve of the main graph (not
+  // SolveGpsCorrdAlone's own graph: ask before a frame that runs it or after the next solve).  Covariances are in the optimiser's
+  // tangent chart, rotation first, the translation part in the vertex's body frame (PoseGraph::WorldPositionCovariance turns it),
+  // and relative to vertex 0, which is held: its own is zero.  false when no solve has run, the vertex does not exist or the
+  // device refused.
+  bool MarginalCovariance(int frame_index, std::array<double, 36>* cov) const {
+    if (frame_index < 0 || frame_index >= graph_.VertexCount()) return false;
+    return NodeCovariance(frame_index, cov);
+  }
+  // the lidar-odometer extrinsic's (the calibration vertex; zero while it is held) and the map origin's in the GPS frame (the frame vertex)
+  bool CalibCovariance(std::array<double, 36>* cov) const { return graph_.HasCalibVertex() && NodeCovariance(graph_.CalibNodeIndex(), cov); }
+  bool GpsCoordCovariance(std::array<double, 36>* cov) const { return graph_.HasFrameVertex() && NodeCovariance(graph_.FrameNodeIndex(), cov); }
+  // Many vertices in one call (node indices of PoseGraph's numbering)
+  bool MarginalCovariances(const std::vector<int>& nodes, std::vector<std::array<double, 36>>* cov) const {
+    if (!main_solved_ || !cov) return false;
+    return marginalizer_ ? marginalizer_(graph_, nodes, cov, nullptr, nullptr) : graph_.Marginals(handle_, nodes, cov);
+  }
+  // The 12x12 joint of frames i and j, row-major, i first: the symmetrised diagonal blocks, and for the cross block the mean of
+  // [H^-1]_{i,j} from j's solves and the transpose of [H^-1]_{j,i} from i's, so that the joint is symmetric to the bit
+  bool JointMarginalCovariance(int i, int j, std::array<double, 144>* joint) const {
+    if (!main_solved_ || !joint || i < 0 || j < 0 || i >= graph_.VertexCount() || j >= graph_.VertexCount() || i == j) return false;
+    const std::vector<int> pair = {i, j};
+    std::vector<std::array<double, 36>> cov, blocks;
+    if (!(marginalizer_ ? marginalizer_(graph_, pair, &cov, &pair, &blocks) : graph_.Marginals(handle_, pair, &cov, &pair, &blocks))) return false;
+    for (int a = 0; a < 6; ++a)
+      for (int b = 0; b < 6; ++b) {
+        (*joint)[static_cast<size_t>(12 * a + b)] = cov[0][static_cast<size_t>(6 * a + b)];
+        (*joint)[static_cast<size_t>(12 * (6 + a) + 6 + b)] = cov[1][static_cast<size_t>(6 * a + b)];
+        // blocks[q * 2 + r] = [H^-1]_{pair[r], pair[q]}
+        const double ij = 0.5 * (blocks[2][static_cast<size_t>(6 * a + b)] + blocks[1][static_cast<size_t>(6 * b + a)]);
+        (*joint)[static_cast<size_t>(12 * a + 6 + b)] = ij;
+        (*joint)[static_cast<size_t>(12 * (6 + b) + a)] = ij;
+      }
+    return true;
+  }
   // tf_tracking_gps_: only its translation is used (:247-248), the antenna in the tracking frame
   void SetTransformTrackingToGps(const Matrix4d& t) { for (int c = 0; c < 3; ++c) gps_lever_[c] = t(c, 3); }
   // tf_odom_lidar_ (odom -> lidar): where the calibration vertex starts (its inverse, :153-157), so set it before the first frame;
@@ -624,6 +709,12 @@ class IsamOptimizer {
     graph_.SetFrameVertex(gps_coord_transform_, GpsCoordPriorSigmas());                         // :339-343
     return true;
   }
+  bool NodeCovariance(int node, std::array<double, 36>* cov) const {
+    std::vector<std::array<double, 36>> one;
+    if (!cov || !MarginalCovariances({node}, &one)) return false;
+    *cov = one[0];
+    return true;
+  }
   void UpdateAllPose() {                                                                        // :106-125
     for (size_t i = 0; i < frames_.size(); ++i) frames_[i]->global_pose = graph_.Pose(static_cast<int>(i));
   }
@@ -633,6 +724,7 @@ class IsamOptimizer {
   smhip_handle handle_ = nullptr;
   Solver solver_;
   Reporter reporter_;
+  Marginalizer marginalizer_;
   std::vector<int> loop_edge_at_;                   // the loop edges' places in graph_.Edges()
   std::vector<LoopEdge> loop_edges_with_information_;
   bool main_solved_ = false;                        // the last solve was one of graph_, as it is now, and it succeeded

@@ -114,6 +114,15 @@ class PoseGraphStats(ctypes.Structure):
                 ("pcg_cap", ctypes.c_int32), ("levels", ctypes.c_int32)]
 
 
+class PoseGraphMarginalsOptions(ctypes.Structure):
+    _fields_ = [("max_workgroups", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class PoseGraphMarginalsStats(ctypes.Structure):
+    _fields_ = [("workgroups", ctypes.c_int32), ("pcg_iterations", ctypes.c_int32), ("pcg_max_iterations", ctypes.c_int32),
+                ("pcg_cap", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/smhip.h declares
 SIGNATURES = {
     "smhip_version": (ctypes.c_int, []),
@@ -245,6 +254,9 @@ SIGNATURES = {
     "smhip_pose_graph_optimize_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_uint8), c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p,
                                                       ctypes.POINTER(PoseGraphOptions), ctypes.POINTER(PoseGraphStats)]),
+    "smhip_pose_graph_marginals_default_options": (None, [ctypes.POINTER(PoseGraphMarginalsOptions)]),
+    "smhip_pose_graph_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, c_double_p, ctypes.c_int, c_int32_p, c_double_p,
+                                                  ctypes.POINTER(PoseGraphMarginalsOptions), ctypes.POINTER(PoseGraphMarginalsStats)]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -30,9 +30,11 @@
 namespace smhip {
 namespace pose_graph {
 
-constexpr double kStepTol = 1.0e-10, kCostTol = 1.0e-12, kCostNoise = 1.0e-11, kPcgTol = 1.0e-8, kLambdaFirst = 1.0e-4, kLambdaMax = 1.0e8;
+constexpr double kStepTol = 1.0e-10, kCostTol = 1.0e-12, kCostNoise = 1.0e-11, kPcgTol = 1.0e-8, kMarginalPcgTol = 1.0e-10, kLambdaFirst = 1.0e-4, kLambdaMax = 1.0e8;
 enum { kOutInitial = 0, kOutFinal = 1, kOutLambda = 2, kOutDoubles = 3 };
 enum { kOutStop = 0, kOutIterations = 1, kOutAccepted = 2, kOutRejected = 3, kOutPcg = 4, kOutPcgMax = 5, kOutInts = 6 };
+enum { kMargPcg = 0, kMargPcgMax = 1, kMargCapped = 2, kMargInts = 3 };       // per query: iterations of its six solves, the longest, a column whose solve ended without meeting the stop rule (at the cap or otherwise)
+constexpr int kMargNodeDoubles = 7 * 6, kMargEdgeDoubles = 6;                  // a workgroup's slice of the marginals' workspace: x r z p q b g per node, u per edge
 
 struct Dev {
   int n = 0, m = 0;                       // nodes, edges
@@ -40,6 +42,7 @@ struct Dev {
   int pcg_budget = 0;                     // conjugate-gradient iterations of the whole launch (SMHIP_POSE_GRAPH_MAX_PCG_TOTAL)
   int probe = 0;                          // 1: first linearisation, gradient and M^-1 v only (smhip_pose_graph_last)
                                           // 2: the report at the poses in cur, left there by the last loop (smhip_pose_graph_last_robust)
+                                          // 3: linearise at cur, assemble and factor at lambda = 0, nothing else: what pose_graph_marginals reads
   // per node
   const double* pose0 = nullptr;          // 12: the poses as given
   double *cur = nullptr, *cand = nullptr; // 12
@@ -547,7 +550,7 @@ PG_HD double dot(const Dev& d, Ctx& c, const double* a, const double* b) {
 
 // (H + lambda blockdiag(H)) x = -g from x = 0; the iterations
 template <class Ctx>
-PG_HD int pcg(const Dev& d, Ctx& c, double lambda, int cap) {
+PG_HD int pcg(const Dev& d, Ctx& c, double lambda, int cap, double tol = kPcgTol) {
   for (int k = c.tid(); k < 6 * d.n; k += c.nthreads()) { d.r[k] = -d.g[k]; d.x[k] = 0.0; }
   c.sync();
   apply_minv(d, c, d.r, d.z);
@@ -566,7 +569,7 @@ PG_HD int pcg(const Dev& d, Ctx& c, double lambda, int cap) {
     ++it;
     apply_minv(d, c, d.r, d.z);
     const double rz1 = dot(d, c, d.r, d.z);
-    if (!(rz1 > kPcgTol * kPcgTol * rz0)) break;
+    if (!(rz1 > tol * tol * rz0)) break;
     const double beta = rz1 / rz;
     for (int k = c.tid(); k < 6 * d.n; k += c.nthreads()) d.p[k] = d.z[k] + beta * d.p[k];
     c.sync();
@@ -604,10 +607,14 @@ PG_HD void run(const Dev& d, Ctx& c) {
     }
     return;
   }
-  if (d.probe) {                                                             // (at pose0 itself: cur keeps the last loop's result for the report)
-    linearize(d, c, d.pose0);
+  if (d.probe) {                                                             // 1: at pose0 itself (cur keeps the last loop's result for the report)
+    linearize(d, c, d.probe == 3 ? cur : d.pose0);                           // 3: at cur, which is only read
     assemble(d, c);
-    factor(d, c, 0.0);
+    const bool ok = factor(d, c, 0.0);
+    if (d.probe == 3) {                                                      // ... and nothing else; a pivot that is not positive: NUMERIC
+      if (c.tid() == 0) d.out_i[kOutStop] = ok ? 0 : SMHIP_POSE_GRAPH_STOP_NUMERIC;
+      return;
+    }
     for (int k = c.tid(); k < 6 * d.n; k += c.nthreads()) d.r[k] = d.fixed[k / 6] ? 0.0 : d.v[k];
     c.sync();
     apply_minv(d, c, d.r, d.minv);
@@ -660,6 +667,71 @@ PG_HD void run(const Dev& d, Ctx& c) {
     d.out_i[kOutStop] = stop; d.out_i[kOutIterations] = it; d.out_i[kOutAccepted] = accepted; d.out_i[kOutRejected] = rejected;
     d.out_i[kOutPcg] = pcg_total; d.out_i[kOutPcgMax] = pcg_max;
   }
+}
+
+// ---- marginal covariances ("Marginal covariances"; tests/pose_graph_marginals_ref.py) -------------------------
+//
+// After run() with probe = 3 the shared arrays A, B, Hkk, Dinv, Wm, Wp hold H = sum w J^T J at cur and the factors of its
+// block-tridiagonal part M at lambda = 0; from then on they are only read.  Column c of node k of H^-1 solves H x = e_{6k+c}: the
+// optimiser's own pcg from x = 0 with g = -e_{6k+c}, stopped at kMarginalPcgTol or the cap.  A workgroup (or the one host thread)
+// works through a copy of Dev whose x r z p q b g u point into its own slice of a workspace, so workgroups share nothing they write.
+
+// d's vectors <- the slice at w: kMargNodeDoubles * n + kMargEdgeDoubles * m doubles
+PG_HD void marginal_slice(Dev* d, double* w) {
+  const size_t n6 = 6 * (size_t)d->n;
+  d->x = w; d->r = w + n6; d->z = w + 2 * n6; d->p = w + 3 * n6; d->q = w + 4 * n6; d->b = w + 5 * n6; d->g = w + 6 * n6; d->u = w + 7 * n6;
+}
+
+// One query: cov (36, row-major) = (X + X^T) / 2 with X = [H^-1]_kk; blocks (36 per row node, may be nullptr with n_rows 0) =
+// [H^-1]_{r,k}, unsymmetrised; info (kMargInts).  A fixed query node, and a fixed row node, give zeros.  The same bits whichever
+// workgroup runs it and whatever was queried before: everything it reads of its slice it has written itself.
+template <class Ctx>
+PG_HD void marginal_query(const Dev& d, Ctx& c, int k, int n_rows, const int32_t* rows, double* cov, double* blocks, int32_t* info) {
+  int total = 0, longest = 0, capped = 0;
+  if (d.fixed[k]) {
+    for (int a = c.tid(); a < 36; a += c.nthreads()) cov[a] = 0.0;
+    for (long long a = c.tid(); a < 36LL * n_rows; a += c.nthreads()) blocks[a] = 0.0;
+  } else {
+    for (int t = c.tid(); t < 6 * d.n; t += c.nthreads()) d.g[t] = 0.0;
+    c.sync();
+    for (int col = 0; col < 6; ++col) {
+      if (c.tid() == 0) d.g[6 * (size_t)k + col] = -1.0;
+      c.sync();
+      const int its = pcg(d, c, 0.0, d.pcg_cap, kMarginalPcgTol);
+      total += its;
+      longest = its > longest ? its : longest;
+      {   // Did the solve end because the stop rule was met?  pcg also leaves at the cap, on r0^T M^-1 r0 or p^T H p not positive (a
+          // singular H, a NaN in A or B), and says only how many iterations it ran; r and z are its last, so the rule is taken again:
+          // the same sums with the same bits.  Anything else -- a NaN included -- raises the flag.
+        const double rz_end = dot(d, c, d.r, d.z);
+        for (int t = c.tid(); t < 6 * d.n; t += c.nthreads()) d.q[t] = -d.g[t];
+        c.sync();
+        apply_minv(d, c, d.q, d.p);
+        const double rz0 = dot(d, c, d.q, d.p);
+        if (!(rz0 > 0.0) || !(rz_end <= kMarginalPcgTol * kMarginalPcgTol * rz0)) capped = 1;
+      }
+      for (int a = c.tid(); a < 6; a += c.nthreads()) cov[6 * a + col] = d.x[6 * (size_t)k + a];
+      for (int t = c.tid(); t < 6 * n_rows; t += c.nthreads()) {
+        const int r = rows[t / 6], a = t % 6;
+        blocks[36 * (size_t)(t / 6) + 6 * a + col] = d.fixed[r] ? 0.0 : d.x[6 * (size_t)r + a];
+      }
+      if (c.tid() == 0) d.g[6 * (size_t)k + col] = 0.0;
+      c.sync();
+    }
+    if (c.tid() == 0)
+      for (int a = 0; a < 6; ++a)
+        for (int b = a + 1; b < 6; ++b) { const double s = 0.5 * (cov[6 * a + b] + cov[6 * b + a]); cov[6 * a + b] = s; cov[6 * b + a] = s; }
+  }
+  if (c.tid() == 0) { info[kMargPcg] = total; info[kMargPcgMax] = longest; info[kMargCapped] = capped; }
+  c.sync();
+}
+
+// queries first, first + stride, ... of the call: what one workgroup of `stride` does
+template <class Ctx>
+PG_HD void marginal_queries(const Dev& d, Ctx& c, int first, int stride, int n_query, const int32_t* query, int n_rows, const int32_t* rows, double* cov,
+                            double* blocks, int32_t* info) {
+  for (long long q = first; q < n_query; q += stride)
+    marginal_query(d, c, query[q], n_rows, rows, cov + 36 * (size_t)q, blocks ? blocks + 36 * (size_t)n_rows * (size_t)q : nullptr, info + kMargInts * (size_t)q);
 }
 
 }  // namespace pose_graph

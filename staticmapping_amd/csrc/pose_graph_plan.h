@@ -195,6 +195,42 @@ inline smhip_status check_and_plan_info(int n_nodes, const double* poses, const 
   return SMHIP_OK;
 }
 
+constexpr int kMargWorkgroupsPerCu = 4;                    // max_workgroups is clamped to this many per CU
+constexpr long long kMargMaxOutputDoubles = 1LL << 27;     // cov and blocks of one call: 1 GiB
+
+// What smhip_pose_graph_marginals decides before anything is touched.  last_n: the node count of the handle's last optimise call, -1 =
+// none reached its launch; last_numeric: that call ended NUMERIC; pcg_cap: its cap; cus: the device's CU count.  SMHIP_OK and the grid
+// in *workgroups, or the refusal with its reason in *why.  The budget is decided from the sizes alone: a workgroup runs
+// ceil(n_query / G) queries of six solves of at most pcg_cap iterations one after the other.
+inline smhip_status check_marginals(int last_n, bool last_numeric, int pcg_cap, int cus, int n_nodes, int n_query, const int32_t* query, const double* cov,
+                                    int n_rows, const int32_t* rows, const double* blocks, int max_workgroups, int* workgroups, std::string* why) {
+  auto refuse = [&](smhip_status s, const std::string& text) { if (why) *why = "pose graph marginals: " + text; return s; };
+  if (last_n < 0) return refuse(SMHIP_ERR_NOT_READY, "no optimisation has been launched on this handle");
+  if (last_numeric) return refuse(SMHIP_ERR_NOT_READY, "the last optimisation ended NUMERIC: there are no poses to linearise at");
+  if (n_nodes != last_n) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "the last optimisation had " + std::to_string(last_n) + " nodes, not " + std::to_string(n_nodes));
+  if (n_query < 1) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "at least one query");
+  if (!query || !cov) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "null pointer");
+  if (n_rows < 0 || (n_rows > 0 && (!rows || !blocks))) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "rows given without rows or blocks to write");
+  if (max_workgroups < 0) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "max_workgroups is negative");
+  for (int q = 0; q < n_query; ++q)
+    if (query[q] < 0 || query[q] >= n_nodes) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "query " + std::to_string(q) + " names a node out of range");
+  for (int r = 0; r < n_rows; ++r)
+    if (rows[r] < 0 || rows[r] >= n_nodes) return refuse(SMHIP_ERR_INVALID_ARGUMENT, "row " + std::to_string(r) + " names a node out of range");
+  // More workgroups than a few per CU buy nothing (one of 1024 threads fills a CU) and each costs a slice of the workspace: clamped.
+  const int most = kMargWorkgroupsPerCu * (cus > 0 ? cus : 1);
+  int G = max_workgroups > 0 ? max_workgroups : (cus > 0 ? cus : 1);
+  if (G > most) G = most;
+  if (G > n_query) G = n_query;
+  if (36.0 * n_query * (1.0 + n_rows) > (double)kMargMaxOutputDoubles)
+    return refuse(SMHIP_ERR_CAPACITY, "cov and blocks together are more than " + std::to_string(kMargMaxOutputDoubles) + " doubles: ask for fewer nodes or rows per call");
+  const long long rounds = ((long long)n_query + G - 1) / G;
+  if (rounds * 6 * (long long)pcg_cap > SMHIP_POSE_GRAPH_MAX_PCG_TOTAL)
+    return refuse(SMHIP_ERR_CAPACITY, std::to_string(rounds) + " queries per workgroup x 6 x the cap of " + std::to_string(pcg_cap) + " iterations is more than " +
+                                          std::to_string(SMHIP_POSE_GRAPH_MAX_PCG_TOTAL) + ": ask for fewer nodes per call");
+  if (workgroups) *workgroups = G;
+  return SMHIP_OK;
+}
+
 inline smhip_status check_and_plan_robust(int n_nodes, const double* poses, const uint8_t* fixed, int n_factors, const uint8_t* kinds, const int32_t* ij,
                                           const double* data, const double* sigmas, const double* huber, Plan* plan, std::string* why) {
   return check_and_plan_calib(false, n_nodes, poses, fixed, n_factors, kinds, ij, data, sigmas, huber, plan, why);

@@ -175,6 +175,9 @@ Args Parse(int argc, char** argv) {
       a.loop_huber_given = true;
     }
     else if (k == "--loop-report") a.loop_report = val();
+    else if (k == "--pose-covariance") a.pose_covariance = val();
+    else if (k == "--pose-covariance-chunk") a.pose_covariance_chunk = std::atoi(val().c_str());
+    else if (k == "--pose-graph-dump") a.pose_graph_dump = val();
     else if (k == "--edge-information") { a.edge_information = std::atoi(val().c_str()) != 0; a.edge_information_given = true; }
     else if (k == "--edge-information-scale") {
       const std::string text = val();
@@ -231,7 +234,8 @@ Args Parse(int argc, char** argv) {
              "  submaps: [--submap-edges edges.txt] [--submap-frames 5] [--submap-voxel 0.1 (0: no voxel filter)] [--submap-min-score 0.7]\n"
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
              "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75] "
-             "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)]\n"
+             "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)] "
+             "[--pose-covariance FILE (a line per submap: index held sigma_rot[3] sigma_pos_world[3] cov[21]) [--pose-covariance-chunk 256] [--pose-graph-dump FILE]]\n"
              "  edge information (with --close-loops): [--edge-information 1 (scan-match edges weighted by the matcher's own 6x6 information)] "
              "[--edge-information-scale 1] [--edge-report FILE (a line per edge: i j chain|loop kept residual_sigma strength[6] weakest[6])]\n"
              "  GPS (with --close-loops): [--gps-enu enu.txt (a line per scan: east north up in metres, nan = no fix)] [--gps-lever 0,0,0] "
@@ -269,6 +273,11 @@ Args Parse(int argc, char** argv) {
   if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
   if (a.loop_huber_given && a.close_loops.empty() && !a.Join()) Die("--loop-huber needs --close-loops");
   if (!a.loop_report.empty() && a.close_loops.empty() && !a.Join()) Die("--loop-report needs --close-loops");
+  if (!a.pose_covariance.empty() && a.close_loops.empty()) Die("--pose-covariance needs --close-loops");
+  if ((!a.pose_graph_dump.empty() || a.pose_covariance_chunk != 256) && a.pose_covariance.empty()) Die("--pose-graph-dump and --pose-covariance-chunk need --pose-covariance");
+  if (a.pose_covariance_chunk < 1) Die("--pose-covariance-chunk takes a count of at least 1");
+  for (const std::string* path : {&a.pose_covariance, &a.pose_graph_dump})      // before any work, and without touching the file
+    if (!path->empty() && !CanWrite(*path)) Die("cannot write " + *path);
   if ((a.edge_information_given || a.edge_information_scale_given || !a.edge_report.empty()) && a.close_loops.empty())
     Die("--edge-information, --edge-information-scale and --edge-report need --close-loops");
   if ((a.edge_information_scale_given || !a.edge_report.empty()) && !a.edge_information) Die("--edge-information-scale and --edge-report need --edge-information 1");

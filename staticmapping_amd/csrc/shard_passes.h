@@ -64,6 +64,18 @@ struct Args {
   double loop_huber = 0.0;
   bool loop_huber_given = false;
   std::string loop_report;
+  // --pose-covariance FILE: after the final optimisation, every submap's marginal covariance (include/smhip.h, "Marginal covariances"):
+  // a line per submap, `index held sigma_rot[3] sigma_pos_world[3] cov[21]` -- held: 1 for the submap the graph holds (all zeros);
+  // sigma_rot: the square roots of the rotation part's diagonal, rad, in the submap's own frame; sigma_pos_world: those of the diagonal
+  // of R Sigma_vv R^T, m; cov[21]: the upper triangle of the 6x6, row by row, %.9g -- then one line each, labelled `calib` and
+  // `gps_frame` in place of the index, for the calibration and GPS-frame vertices when the graph has them.  Relative to the held submap.
+  std::string pose_covariance;
+  // --pose-covariance-chunk N: the nodes asked for in one marginals call (256: a workgroup then runs one query);
+  // --pose-graph-dump FILE: the final optimisation's input as text, so that the solve and its covariances can be replayed from the
+  // file alone: "n m", a line per node (16 numbers of the pose, column-major, then held), a line per factor (kind i j, 16 data, 6
+  // sigmas, the Huber threshold, 1 and 36 numbers of the square-root information or 0), all %.17g
+  int pose_covariance_chunk = 256;
+  std::string pose_graph_dump;
   // --edge-information 1: every accepted consecutive-submap match and every loop edge is measured with its own 6x6 information and
   // enters the graph with it (smhip/edge_information.h); --edge-information-scale S: EdgeInformationOptions::information_scale;
   // --edge-report FILE: a line per measured edge
@@ -97,6 +109,13 @@ struct Args {
   bool Join() const { return !join_base.empty() || !join_incremental.empty() || !join_out.empty(); }
 };
 
+// the file can be written, or created where it is -- decided without creating or truncating it
+inline bool CanWrite(const std::string& path) {
+  if (::access(path.c_str(), F_OK) == 0) return ::access(path.c_str(), W_OK) == 0;
+  const size_t cut = path.find_last_of('/');
+  const std::string dir = cut == std::string::npos ? "." : (cut == 0 ? "/" : path.substr(0, cut));
+  return ::access(dir.c_str(), W_OK | X_OK) == 0;
+}
 [[noreturn]] inline void Die(const std::string& m) { std::fprintf(stderr, "smhip_shard: %s\n", m.c_str()); std::exit(2); }
 
 inline std::string Fmt(const char* fmt, ...) {
@@ -484,6 +503,15 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   std::ofstream out(a.close_loops);
   if (!out) Die("cannot write " + a.close_loops);
   out.precision(8);
+  std::ofstream cov_out;
+  if (!a.pose_covariance.empty()) {
+    cov_out.open(a.pose_covariance);
+    if (!cov_out) Die("cannot write " + a.pose_covariance);
+  }
+  std::string cov_lines;
+  double odom_tf_sigmas[6] = {0, 0, 0, 0, 0, 0};
+  bool have_odom_tf_sigmas = false;
+  std::string graph_dump_text;
   if (!a.save_trajectory_map.empty()) {
     struct stat sb;
     if (::mkdir(a.save_trajectory_map.c_str(), 0777) != 0 && !(::stat(a.save_trajectory_map.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode))) Die("cannot create " + a.save_trajectory_map);
@@ -590,11 +618,68 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
       frames.push_back(frame);
       if (!(has_chain_information ? optimizer.AddFrame(frame, from_last, &chain_information) : optimizer.AddFrame(frame, from_last))) { std::fprintf(stderr, "smhip_shard: the pose graph could not be optimised at submap %d\n", k); rc = 3; break; }
     }
+    std::string& graph_dump = graph_dump_text;
+    if (rc == 0 && !a.pose_graph_dump.empty()) {                          // the graph as the final optimisation is about to be given it
+      const be::PoseGraph& g = optimizer.Graph();
+      std::vector<double> gp, gd, gs, gh, gl;
+      std::vector<int32_t> gij, gi;
+      std::vector<uint8_t> gf, gk;
+      g.FlattenFactors(&gp, &gf, &gk, &gij, &gd, &gs);
+      g.FlattenHuber(&gh);
+      g.FlattenInformation(&gi, &gl);
+      graph_dump = Fmt("%d %d\n", g.NodeCount(), static_cast<int>(gk.size()));
+      for (int k = 0; k < g.NodeCount(); ++k) {
+        for (int q = 0; q < 16; ++q) graph_dump += Fmt("%.17g ", gp[16 * static_cast<size_t>(k) + q]);
+        graph_dump += Fmt("%d\n", static_cast<int>(gf[static_cast<size_t>(k)]));
+      }
+      for (size_t f = 0; f < gk.size(); ++f) {
+        graph_dump += Fmt("%d %d %d", static_cast<int>(gk[f]), gij[2 * f], gij[2 * f + 1]);
+        for (int q = 0; q < 16; ++q) graph_dump += Fmt(" %.17g", gd[16 * f + q]);
+        for (int q = 0; q < 6; ++q) graph_dump += Fmt(" %.17g", gs[6 * f + q]);
+        graph_dump += Fmt(" %.17g %d", gh[f], gi[f] >= 0 ? 1 : 0);
+        for (int q = 0; gi[f] >= 0 && q < 36; ++q) graph_dump += Fmt(" %.17g", gl[36 * static_cast<size_t>(gi[f]) + q]);
+        graph_dump += "\n";
+      }
+    }
     if (rc == 0 && !optimizer.RunFinalOptimazation()) rc = 3;
     if (rc == 0 && (a.loop_huber > 0.0 || !a.loop_report.empty())) {
       loop_report = optimizer.LoopEdgeReport();
       if (static_cast<int>(loop_report.size()) != optimizer.LoopEdgeCount()) { std::fprintf(stderr, "smhip_shard: the loop edges' report was refused\n"); rc = 3; }
       for (const be::LoopEdgeWeight& w : loop_report) res.downweighted += w.weight < 1.0;
+    }
+    if (rc == 0 && (!a.pose_covariance.empty() || (io.use_odom && a.odom_calib))) {
+      // the submaps (with the flag), then the calibration and GPS-frame vertices; 256 nodes a call, so that a workgroup runs one query
+      const be::PoseGraph& graph = optimizer.Graph();
+      std::vector<int> nodes;
+      std::vector<std::string> labels;
+      if (!a.pose_covariance.empty()) for (int k = 0; k < graph.VertexCount(); ++k) { nodes.push_back(k); labels.push_back(std::to_string(k)); }
+      if (graph.HasCalibVertex()) { nodes.push_back(graph.CalibNodeIndex()); labels.push_back("calib"); }
+      if (graph.HasFrameVertex() && !a.pose_covariance.empty()) { nodes.push_back(graph.FrameNodeIndex()); labels.push_back("gps_frame"); }
+      std::vector<std::array<double, 36>> cov;
+      const size_t chunk = static_cast<size_t>(a.pose_covariance_chunk);
+      bool refused = false;
+      for (size_t at = 0; at < nodes.size() && !refused; at += chunk) {
+        const std::vector<int> part(nodes.begin() + static_cast<std::ptrdiff_t>(at), nodes.begin() + static_cast<std::ptrdiff_t>(std::min(at + chunk, nodes.size())));
+        std::vector<std::array<double, 36>> got;
+        if (!optimizer.MarginalCovariances(part, &got)) { refused = true; break; }
+        cov.insert(cov.end(), got.begin(), got.end());
+      }
+      if (refused && !a.pose_covariance.empty()) { std::fprintf(stderr, "smhip_shard: the marginal covariances were refused\n"); rc = 3; }
+      // (without --pose-covariance only the extrinsic's sigmas on stdout were wanted: an error bar that could not be had does not
+      // cost the run its poses -- the field is left out)
+      if (refused && a.pose_covariance.empty()) std::fprintf(stderr, "smhip_shard: warning: the extrinsic's covariance was refused; odom_tf_sigmas is left out\n");
+      for (size_t q = 0; q < nodes.size() && rc == 0 && !refused; ++q) {
+        const std::array<double, 36>& c = cov[q];
+        if (nodes[q] == graph.CalibNodeIndex()) { have_odom_tf_sigmas = true; for (int d = 0; d < 6; ++d) odom_tf_sigmas[d] = std::sqrt(c[static_cast<size_t>(7 * d)]); }
+        if (a.pose_covariance.empty()) continue;
+        const bool held = nodes[q] < graph.VertexCount() ? graph.Fixed()[static_cast<size_t>(nodes[q])] != 0 : (nodes[q] == graph.CalibNodeIndex() && graph.CalibVertexHeld());
+        const std::array<double, 9> world = graph.WorldPositionCovariance(nodes[q], c);
+        cov_lines += labels[q] + Fmt(" %d", held ? 1 : 0);
+        for (int d = 0; d < 3; ++d) cov_lines += Fmt(" %.9g", std::sqrt(c[static_cast<size_t>(7 * d)]));
+        for (int d = 0; d < 3; ++d) cov_lines += Fmt(" %.9g", std::sqrt(world[static_cast<size_t>(4 * d)]));
+        for (int r = 0; r < 6; ++r) for (int s = r; s < 6; ++s) cov_lines += Fmt(" %.9g", c[static_cast<size_t>(6 * r + s)]);
+        cov_lines += "\n";
+      }
     }
     if (rc == 0 && a.edge_information) {
       for (const be::LoopEdge& e : optimizer.LoopEdgesWithInformation()) edge_report.push_back({e.close_pair_index.first, e.close_pair_index.second, true, e.information});
@@ -650,7 +735,17 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
     }
   }
   out.close();
-  if (rc != 0) { std::remove(a.close_loops.c_str()); return rc; }
+  if (rc != 0) {
+    std::remove(a.close_loops.c_str());
+    if (!a.pose_covariance.empty()) { cov_out.close(); std::remove(a.pose_covariance.c_str()); }
+    return rc;
+  }
+  if (!a.pose_covariance.empty()) { cov_out << cov_lines; cov_out.close(); }
+  if (!a.pose_graph_dump.empty()) {
+    std::ofstream dump(a.pose_graph_dump);
+    if (!dump) Die("cannot write " + a.pose_graph_dump);
+    dump << graph_dump_text;
+  }
   if (!a.loop_report.empty()) {
     std::ofstream rep(a.loop_report);
     if (!rep) Die("cannot write " + a.loop_report);
@@ -678,7 +773,12 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   if (!a.odom_file.empty()) {
     *fields += Fmt(", \"odom_factors\": %d, \"odom_tf\": [", res.odom_factors);
     for (int q = 0; q < 16; ++q) *fields += Fmt("%.17g%s", res.odom_tf[q], q == 15 ? "]" : ", ");
+    if (a.odom_calib && have_odom_tf_sigmas) {   // of the calibration vertex (lidar -> odom, the inverse of odom_tf) in its own tangent chart: rad x 3, m x 3
+      *fields += ", \"odom_tf_sigmas\": [";
+      for (int d = 0; d < 6; ++d) *fields += Fmt("%.9g%s", odom_tf_sigmas[d], d == 5 ? "]" : ", ");
+    }
   }
+  if (!a.pose_covariance.empty()) *fields += Fmt(", \"pose_covariance_file\": \"%s\"", a.pose_covariance.c_str());
   return 0;
 }
 

@@ -13,8 +13,13 @@
 //   pcg           H p matrix-free (per edge, then per node), M^-1 by one sweep up and one down the levels, dot products as
 //                 per-thread partials folded by wave shuffles and then in wave order: two calls give the same bits
 // The refusals and the CSR list are made on the host (pose_graph_plan.h) before anything is touched.
+//
+// smhip_pose_graph_marginals ("Marginal covariances") is two launches: pose_graph_solve with probe = 3 leaves the
+// Gauss-Newton matrix of the last call's final poses and its preconditioner's factors in global memory, then pose_graph_marginals, one
+// workgroup per CU at most, solves six columns per queried node against them -- many independent solves against one fixed matrix.
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pose_graph_kernel.h"
@@ -59,6 +64,17 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_solve(const pg::Dev d) 
   pg::run(d, c);
 }
 
+// Marginal covariances (pose_graph_kernel.h, "marginal covariances"): workgroup w takes queries w, w + G, w + 2G, ... and runs each
+// one's six column solves through its own slice of ws.  `shared` is only read; no atomics, no grid barrier, nothing between workgroups.
+__global__ __launch_bounds__(kPgThreads) void pose_graph_marginals(const pg::Dev shared, int n_query, const int32_t* query, int n_rows, const int32_t* rows,
+                                                                   double* ws, size_t ws_stride, double* cov, double* blocks, int32_t* info) {
+  __shared__ double s_part[kPgThreads / 64];
+  BlockCtx c{s_part};
+  pg::Dev d = shared;
+  pg::marginal_slice(&d, ws + ws_stride * (size_t)blockIdx.x);
+  pg::marginal_queries(d, c, (int)blockIdx.x, (int)gridDim.x, n_query, query, n_rows, rows, cov, blocks, info);
+}
+
 // doubles and words of the device state per node / per edge, and of the staging the host fills
 constexpr int kNodeD = 3 * 12 + 7 * 36 + 7 * 6 + 2 * 6, kEdgeD = 12 + 6 + 2 * 36 + 2 * 6 + 4 + 36;      // (+ huber, wgt, rep_s, rep_c; sqrt_info)
 constexpr int kNodeI = 2, kEdgeI = 6;           // fixed, csr_off (+1); ij, csr_edge, kind, info_index
@@ -75,6 +91,14 @@ struct smhip_pose_graph_state {
   int last_n = -1, last_m = 0;     // what smhip_pose_graph_last can run again (-1: nothing)
   bool last_huber = false;         // that call uploaded thresholds
   bool last_info = false;          // ... and square-root informations
+  bool last_numeric = false;       // ... and ended NUMERIC: cur is no result (smhip_pose_graph_marginals answers NOT_READY)
+  // smhip_pose_graph_marginals' own: grown to fit a call, never shrunk, freed with the state
+  double *marg_ws = nullptr, *marg_out = nullptr;      // the workgroups' slices; cov then blocks
+  int32_t* marg_int = nullptr;                         // query, rows, info
+  size_t marg_ws_cap = 0, marg_out_cap = 0, marg_int_cap = 0;      // in elements
+  int cus = 0;                                         // the device's CU count (0: not asked yet)
+  std::vector<double> marg_host_d;
+  std::vector<int32_t> marg_host_i;
 };
 
 namespace {
@@ -213,6 +237,7 @@ smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_
   HIPCHK(h, hipMemcpyAsync(out_i, d.out_i, sizeof(out_i), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   st->last_n = n_nodes; st->last_m = n_edges; st->last_huber = robust; st->last_info = with_info;
+  st->last_numeric = out_i[pg::kOutStop] == SMHIP_POSE_GRAPH_STOP_NUMERIC;
   if (stats) {
     stats->initial_cost = out_d[pg::kOutInitial]; stats->final_cost = out_d[pg::kOutFinal]; stats->damping = out_d[pg::kOutLambda];
     stats->stop_reason = out_i[pg::kOutStop]; stats->iterations = out_i[pg::kOutIterations];
@@ -243,7 +268,10 @@ smhip_status pg_optimize(bool calib, smhip_handle h, int n_nodes, double* poses_
 extern "C" {
 
 void smhip_internal_free_pose_graph(smhip_context* h) {
-  delete h->pose_graph;            // (the device arrays are among the handle's allocations)
+  if (smhip_pose_graph_state* st = h->pose_graph) {
+    (void)hipFree(st->marg_ws); (void)hipFree(st->marg_out); (void)hipFree(st->marg_int);      // (nullptr is fine)
+  }
+  delete h->pose_graph;            // (the other device arrays are among the handle's allocations)
   h->pose_graph = nullptr;
 }
 
@@ -363,6 +391,87 @@ smhip_status smhip_pose_graph_last_robust(smhip_handle h, int n_factors, double*
   if (weight) HIPCHK(h, hipMemcpyAsync(weight, d.wgt, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
   if (cost) HIPCHK(h, hipMemcpyAsync(cost, d.rep_c, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
+  return SMHIP_OK;
+}
+
+void smhip_pose_graph_marginals_default_options(smhip_pose_graph_marginals_options* o) {
+  if (o) std::memset(o, 0, sizeof(*o));
+}
+
+smhip_status smhip_pose_graph_marginals(smhip_handle h, int n_nodes, int n_query, const int32_t* query, double* cov, int n_rows, const int32_t* rows,
+                                        double* blocks, const smhip_pose_graph_marginals_options* opts, smhip_pose_graph_marginals_stats* stats) {
+  if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
+  smhip_pose_graph_state* st = h->pose_graph;
+  if (st && st->last_n >= 0 && !st->cus) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceGetAttribute(&st->cus, hipDeviceAttributeMultiprocessorCount, h->device));
+  }
+  int G = 0;
+  if (const smhip_status s = pg::check_marginals(st ? st->last_n : -1, st && st->last_numeric, st ? st->plan.pcg_cap : 0, st ? st->cus : 0, n_nodes, n_query, query,
+                                                 cov, n_rows, rows, blocks, opts ? opts->max_workgroups : 0, &G, &h->err))
+    return s;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int n = st->last_n, m = st->last_m;
+  const size_t Q = (size_t)n_query, R = (size_t)n_rows;
+  const size_t stride = (size_t)pg::kMargNodeDoubles * (size_t)n + (size_t)pg::kMargEdgeDoubles * (size_t)m;
+  const size_t need_ws = stride * (size_t)G, need_out = 36 * Q * (1 + R), need_int = Q + R + pg::kMargInts * Q;
+  auto grow = [&](auto** p, size_t* cap, size_t count) -> smhip_status {
+    if (count <= *cap) return SMHIP_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    void* v = nullptr;
+    HIPCHK(h, hipMalloc(&v, count * sizeof(**p)));
+    *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(v);
+    *cap = count;
+    return SMHIP_OK;
+  };
+  if (const smhip_status s = grow(&st->marg_ws, &st->marg_ws_cap, need_ws)) return s;
+  if (const smhip_status s = grow(&st->marg_out, &st->marg_out_cap, need_out)) return s;
+  if (const smhip_status s = grow(&st->marg_int, &st->marg_int_cap, need_int)) return s;
+  hipStream_t s = h->stream;
+  pg::Dev d = st->dev;
+  d.n = n; d.m = m; d.max_it = 0; d.pcg_cap = st->plan.pcg_cap; d.probe = 3;
+  if (!st->last_huber) d.huber = nullptr;
+  if (!st->last_info) { d.info_index = nullptr; d.sqrt_info = nullptr; }
+  int32_t* d_query = st->marg_int;
+  int32_t* d_rows = d_query + Q;
+  int32_t* d_info = d_rows + R;
+  double* d_cov = st->marg_out;
+  double* d_blocks = R ? d_cov + 36 * Q : nullptr;
+  HIPCHK(h, hipMemcpyAsync(d_query, query, sizeof(int32_t) * Q, hipMemcpyHostToDevice, s));
+  if (R) HIPCHK(h, hipMemcpyAsync(d_rows, rows, sizeof(int32_t) * R, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(pose_graph_solve, dim3(1), dim3(kPgThreads), 0, s, d);
+  HIPCHK(h, hipGetLastError());
+  int32_t numeric = 0;
+  HIPCHK(h, hipMemcpyAsync(&numeric, d.out_i + pg::kOutStop, sizeof(numeric), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (numeric == SMHIP_POSE_GRAPH_STOP_NUMERIC) {
+    h->err = "pose graph marginals: a pivot of the preconditioner's factorisation at the final poses was not positive; nothing is written";
+    return SMHIP_ERR_NO_MATCH;
+  }
+  hipLaunchKernelGGL(pose_graph_marginals, dim3((unsigned)G), dim3(kPgThreads), 0, s, d, n_query, d_query, n_rows, d_rows, st->marg_ws, stride, d_cov, d_blocks, d_info);
+  HIPCHK(h, hipGetLastError());
+  st->marg_host_d.resize(need_out);
+  st->marg_host_i.resize(pg::kMargInts * Q);
+  HIPCHK(h, hipMemcpyAsync(st->marg_host_d.data(), d_cov, sizeof(double) * need_out, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(st->marg_host_i.data(), d_info, sizeof(int32_t) * pg::kMargInts * Q, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  long long total = 0;
+  int longest = 0, capped = 0;
+  for (size_t q = 0; q < Q; ++q) {
+    const int32_t* i = st->marg_host_i.data() + pg::kMargInts * q;
+    total += i[pg::kMargPcg];
+    longest = i[pg::kMargPcgMax] > longest ? i[pg::kMargPcgMax] : longest;
+    capped |= i[pg::kMargCapped];
+  }
+  if (stats) { stats->workgroups = G; stats->pcg_iterations = total > INT32_MAX ? INT32_MAX : (int32_t)total; stats->pcg_max_iterations = longest; stats->pcg_cap = st->plan.pcg_cap; }
+  if (capped) {
+    h->err = "pose graph marginals: a column's solve ended without meeting the tolerance (the cap is " + std::to_string(st->plan.pcg_cap) + " iterations); nothing is written";
+    return SMHIP_ERR_NO_MATCH;
+  }
+  std::memcpy(cov, st->marg_host_d.data(), sizeof(double) * 36 * Q);
+  if (R) std::memcpy(blocks, st->marg_host_d.data() + 36 * Q, sizeof(double) * 36 * Q * R);
   return SMHIP_OK;
 }
 

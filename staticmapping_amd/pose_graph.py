@@ -306,3 +306,24 @@ def last(matcher, n_nodes: int, n_edges: int, v=None):
     matcher._check(matcher._lib.smhip_pose_graph_last(matcher._h, n_nodes, n_edges, _ptr(r, _capi.c_double_p), _ptr(A, _capi.c_double_p), _ptr(B, _capi.c_double_p),
                                                       _ptr(g, _capi.c_double_p), _ptr(v, _capi.c_double_p), _ptr(out, _capi.c_double_p)))
     return dict(r=r, A=A, B=B, g=g, minv_v=out)
+
+
+def marginals(matcher, n_nodes: int, query, rows=None, max_workgroups: int | None = None):
+    """Marginal covariances of the last optimise call on the handle, whichever it was (include/smhip.h, "Marginal covariances"): for every
+    node in `query`, Sigma_k = the symmetrised diagonal block of H^-1 at the poses that call ended at, in the optimiser's tangent chart
+    (rotation first; the translation part in the node's body frame), relative to the held nodes or PRIORs; zeros for a fixed node.
+    rows: node indices whose cross blocks [H^-1]_{r, k} are wanted too.  Returns (cov [Q, 6, 6], blocks [Q, R, 6, 6] or None, stats dict)."""
+    q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1))
+    r = None if rows is None else np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
+    cov = np.zeros((len(q), 6, 6))
+    blocks = None if r is None else np.zeros((len(q), len(r), 6, 6))
+    lib = matcher._lib
+    o = _capi.PoseGraphMarginalsOptions()
+    lib.smhip_pose_graph_marginals_default_options(ctypes.byref(o))
+    if max_workgroups is not None:
+        o.max_workgroups = max_workgroups
+    st = _capi.PoseGraphMarginalsStats()
+    matcher._check(lib.smhip_pose_graph_marginals(matcher._h, n_nodes, len(q), _ptr(q, _capi.c_int32_p), _ptr(cov, _capi.c_double_p),
+                                                  0 if r is None else len(r), _ptr(r, _capi.c_int32_p), _ptr(blocks, _capi.c_double_p),
+                                                  ctypes.byref(o), ctypes.byref(st)))
+    return cov, blocks, {name: getattr(st, name) for name, _ in _capi.PoseGraphMarginalsStats._fields_}

@@ -13,6 +13,10 @@ chord to every submap.  The calibration is held at the truth; with --odom-calib 
 --join: instead, two drives of 909 submaps joined (tests/multi_trajectory_ref.py: the graph MultiTrajectoryMapBuilder solves, DESIGN.md
 section 6, "Joining maps"): the second loaded 0.5 m and 0.5 degrees off, a cross edge on every second of its submaps, once with the base
 map free and once held (profiles/pose_graph_join_probe.json).  The free solve can run for a minute: use --repeats 2 --warmup 1.
+--marginals: instead, the two loop cases optimised and then smhip_pose_graph_marginals for ALL their free submaps (DESIGN.md section 6,
+"Marginal covariances"): the time of the marginals call beside the optimise call's, and beside both the time numpy.linalg.inv takes
+(median of the same repeats after the same warm-up) for the same H (5 454 x 5 454, built by tests/pose_graph_marginals_ref.py at the device's poses) on the host, with the largest
+difference between the two (profiles/pose_graph_marginals_probe.json).
 One JSON line on stdout (and in --out when given)."""
 import argparse
 import json
@@ -121,6 +125,44 @@ def join_cases(m, a):
     return out
 
 
+def marginals_case(m, a, g, n_loops):
+    """optimise, then the marginal covariances of every free submap in one call; numpy's dense inverse of the same H as the yardstick"""
+    import pose_graph_marginals_ref as mref
+    from staticmapping_amd import pose_graph
+
+    def timed(call):
+        for _ in range(a.warmup):
+            call()
+        t, out = [], None
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            out = call()
+            t.append(time.perf_counter() - t0)
+        return t, out
+    t_opt, (poses, stats) = timed(lambda: pose_graph.optimize(m, g["poses"], g["edges"], g["Z"], fixed=g["fixed"]))
+    free = [k for k in range(N_NODES) if not g["fixed"][k]]
+    t_mar, (cov, _, ms) = timed(lambda: pose_graph.marginals(m, N_NODES, free))
+    t_one, _ = timed(lambda: pose_graph.marginals(m, N_NODES, free[-1:]))
+    case = {"loop_edges": n_loops, "edges": int(len(g["edges"])), "queries": len(free), "optimise_median_ms": round(float(np.median(t_opt)) * 1e3, 4),
+            "optimise_pcg_iterations": stats["pcg_iterations"], "marginals_median_ms": round(float(np.median(t_mar)) * 1e3, 4),
+            "marginals_min_ms": round(float(np.min(t_mar)) * 1e3, 4), "marginals_one_query_median_ms": round(float(np.median(t_one)) * 1e3, 4),
+            "workgroups": ms["workgroups"], "marginals_pcg_iterations": ms["pcg_iterations"],
+            "marginals_pcg_longest_column": ms["pcg_max_iterations"], "pcg_cap": ms["pcg_cap"],
+            "iterations_per_query": round(ms["pcg_iterations"] / len(free), 2),
+            "queries_per_workgroup": -(-len(free) // ms["workgroups"]),
+            "largest_position_sigma_m": float(np.sqrt(np.trace(cov[:, 3:, 3:], axis1=1, axis2=2)).max())}
+    if not a.no_restatement:
+        H, fixed, _ = mref.system(g, poses)
+        Hd = np.asarray(H)
+        t_inv, X = timed(lambda: np.linalg.inv(Hd))                        # the same warm-up and repeats as the device calls
+        case["host_numpy_inv_ms"] = round(float(np.median(t_inv)) * 1e3, 1)
+        case["host_numpy_inv_min_ms"] = round(float(np.min(t_inv)) * 1e3, 1)
+        case["host_threads_note"] = "numpy.linalg.inv of the %d x %d H, LAPACK on every core the process may use" % H.shape
+        want = np.stack([0.5 * (X[6 * k:6 * k + 6, 6 * k:6 * k + 6] + X[6 * k:6 * k + 6, 6 * k:6 * k + 6].T) for k in free])
+        case["difference_to_inv_relative"] = float(np.abs(cov - want).max() / np.abs(want).max())
+    return case
+
+
 def robust_case(m, a, drive, n_loops, overlap):
     """the loop case `drive` as factors, plus --bad-loops wrong loop edges, solved with the threshold --huber on the loop edges"""
     import pose_graph_robust_cases as cases
@@ -159,6 +201,7 @@ def main():
     ap.add_argument("--odom", action="store_true", help="an odometry calibration factor on every submap of the drive with 3 loop edges, instead of the two loop cases")
     ap.add_argument("--odom-calib", action="store_true", help="with --odom: the calibration free, from a start 0.1 rad off")
     ap.add_argument("--join", action="store_true", help="two 909-submap drives joined, a cross edge on every second incremental submap, with the base free and held")
+    ap.add_argument("--marginals", action="store_true", help="the two loop cases, then the marginal covariances of all their free submaps, beside numpy's dense inverse")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     try:
@@ -179,6 +222,9 @@ def main():
     for n_loops in (() if a.gps or a.odom or a.join else (3, 60)):
         # the drive overlaps its start by four submaps (three loop edges) or by 64 (sixty: every revisited submap closes on its first visit)
         g = ref.circle_drive(N_NODES, seed=1, loops=[(k, None) for k in range(n_loops)], overlap=4 if n_loops <= 4 else 64)
+        if a.marginals:
+            res["cases"].append(marginals_case(m, a, g, n_loops))
+            continue
         if a.huber > 0.0 or a.bad_loops > 0:
             res["cases"].append(robust_case(m, a, g, n_loops, 4 if n_loops <= 4 else 64))
             continue
