@@ -857,7 +857,8 @@ smhip_status smhip_pose_graph_optimize_info(smhip_handle h, int n_nodes, double*
  * Found by the kernels, SMHIP_ERR_NO_MATCH with cov and blocks not written: a pivot of the factorisation that is not positive; a
  * column whose solve ended without meeting the tolerance -- at pcg_cap, or because a sum was not positive or not finite (stats are
  * written in this case; pcg_iterations saturates at INT32_MAX).
- * Out of scope: using the covariances inside LoopDetector's distance gate (the obvious follow-up), a selected-inversion shortcut for
+ * Out of scope: using the covariances inside LoopDetector's distance gate (the obvious follow-up; the covariance can also size the
+ * window of smhip_guess_search_f32 below, which is what makes a wider gate useful), a selected-inversion shortcut for
  * the chain part, joint marginals of more than two nodes, incremental reuse between calls. */
 typedef struct smhip_pose_graph_marginals_options {
   int32_t max_workgroups;       /* 0 = one per CU */
@@ -873,6 +874,63 @@ void smhip_pose_graph_marginals_default_options(smhip_pose_graph_marginals_optio
 smhip_status smhip_pose_graph_marginals(smhip_handle h, int n_nodes, int n_query, const int32_t* query, double* cov, int n_rows,
                                         const int32_t* rows, double* blocks, const smhip_pose_graph_marginals_options* opts,
                                         smhip_pose_graph_marginals_stats* stats);
+
+/* ---- correlative guess search ("Guess search"; tests/guess_search_ref.py) ----------
+ * Not in the reference: LoopDetector::CloseLoop (back_end/loop_detector.cc:282-318) starts its ICP from the drifted poses, and a local
+ * ICP has no capture range of metres.  Given a target cloud, a source cloud and a guess, every transform of a window around the guess
+ * is scored by how many source points land in an occupied target voxel, and the best one is returned.  All integers after rule 5:
+ *  1 rows       rows with a non-finite x, y or z are dropped from both clouds (icp_pointmatcher.cc:57-66)
+ *  2 sample     n source rows left, M = max_source_points: all of them if n <= M, else rows floor(k n / M), k = 0 .. M-1 (64-bit)
+ *  3 target     v = floorf(p / resolution) per axis, the f32 IEEE quotient; occupancy is a bitmap over the box of the target's v
+ *  4 yaws       a = -yaw_steps .. yaw_steps: R_a = Rz(a * yaw_step) * R0 about the TARGET frame's z, t0 kept; R0, t0 from the guess;
+ *               formed in double on the host (c r0 - s r1 and s r0 + c r1 per column, each product and sum rounded), cast to f32
+ *  5 source     q = ((r00 x + r01 y) + r02 z) + t per row of R_a, every f32 product and sum rounded on its own; w = floorf(q / res)
+ *  6 score      score(a, i, j, k) = #{sampled source points : w + (i, j, k) is an occupied target voxel}, i, j in [-half_xy, half_xy],
+ *               k in [-half_z, half_z]; a voxel outside the bitmap is empty.  Flat index ((a + yaw_steps) * nz + (k + half_z)) * nxy^2 +
+ *               (j + half_xy) * nxy + (i + half_xy) with nxy = 2 half_xy + 1, nz = 2 half_z + 1
+ *  7 pick       the highest score; among equals the smallest i^2 + j^2 + k^2, then the smallest |a|, then the smallest a, k, j, i --
+ *               taken from the stored score volume under that total order, so it does not depend on scheduling
+ *  8 result     rotation Rz(a* yaw_step) R0 and translation t0 + resolution * (i*, j*, k*), in double
+ *  9 also       guess_score = score(0, 0, 0, 0); runner_up_score = the best score among candidates with max(|i-i*|, |j-j*|, |k-k*|) > 2
+ *               or |a-a*| > 1, 0 if there is none: whether the peak stands alone
+ * Refused from the sizes alone, before anything is touched, `result` not written --
+ *   SMHIP_ERR_INVALID_ARGUMENT: a null pointer, a stride other than 4 (x y z intensity) or 5 (InnerPointType), a cloud of no row, a
+ *     resolution that is not finite and positive, a negative half_xy, half_z or yaw_steps, a yaw_step that is not finite,
+ *     max_source_points < 1, a guess with an entry that is not finite;
+ *   SMHIP_ERR_CAPACITY: more than 2^25 candidates (the score volume is one int32 each), a half-width above 2^19, a cloud of more
+ *     rows than max(max_source_points, max_target_points) of the handle.
+ * Found later, `result` not written: a cloud with no finite row -- SMHIP_ERR_INVALID_ARGUMENT (seen while the rows are staged for
+ *   upload; rules 1 and 2 are applied there); a voxel coordinate of either cloud at or beyond 2^30, a target box that with the window
+ *   exceeds 2^20 voxels along an axis, a bitmap above 2^28 bits -- SMHIP_ERR_CAPACITY (the box comes from a device reduction).
+ * The workspace (clouds, bitmap, (2 yaw_steps + 1) x n_source_used packed voxels, the score volume) grows to fit a call and never
+ * shrinks: nothing is allocated by a call no larger than an earlier one.  Same input, same bits.
+ * Out of scope: sizing the window from smhip_pose_graph_marginals, roll and pitch, resident clouds without upload, multi-GPU. */
+typedef struct smhip_guess_search_options {
+  float resolution;              /* 0.5 (metres per voxel) */
+  int32_t max_source_points;     /* 4096 */
+  int32_t half_xy, half_z;       /* 20, 2 (voxels) */
+  int32_t yaw_steps;             /* 10 */
+  int32_t reserved;
+  double yaw_step;               /* 2 degrees, in radians */
+} smhip_guess_search_options;
+typedef struct smhip_guess_search_result {
+  double transform[16];          /* column-major, rule 8 */
+  int32_t best_score, guess_score, runner_up_score;
+  int32_t n_source_used, n_candidates;
+  int32_t best_yaw, best_i, best_j, best_k;     /* a*, i*, j*, k* */
+  int32_t reserved[3];
+} smhip_guess_search_result;
+void smhip_guess_search_default_options(smhip_guess_search_options* o);
+/* guess: 16 doubles, column-major */
+smhip_status smhip_guess_search_f32(smhip_handle h, const float* target, int n_target, int target_stride, const float* source, int n_source,
+                                    int source_stride, const double* guess, const smhip_guess_search_options* opts,
+                                    smhip_guess_search_result* result);
+/* parity-test hook: what the last completed search on the handle left.  Any pointer may be NULL.  volume: the volume_len =
+ * n_candidates scores in the flat order of rule 6; origin3 / extent3: the bitmap's box in voxels; source_voxels: voxels_len = 3 x
+ * (2 yaw_steps + 1) x n_source_used words, w of rule 5 per yaw and sampled point -- INT32_MIN three times for a point that no offset of
+ * the window brings into the box (it is stored as such).  SMHIP_ERR_NOT_READY when no search has completed. */
+smhip_status smhip_guess_search_last(smhip_handle h, int32_t* volume, int volume_len, int32_t* origin3, int32_t* extent3, int32_t* source_voxels,
+                                     int voxels_len);
 
 /* ---- static_map::MultiResolutionVoxelMap (builder/multi_resolution_voxel_map.{h,cc}) ----------
  * The probabilistic hit / miss voxel map with ray casting behind the reference's static-map output (one

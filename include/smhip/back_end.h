@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstring>
 #include <functional>
 #include <limits>
 #include <memory>
@@ -78,7 +79,18 @@ struct LoopEdge {
   double score = 0.0;
   bool has_information = false;                 // LoopDetectorSettings::edge_information: the accepted match's own information,
   EdgeInformation information;                  // measured at `transform` (smhip/edge_information.h)
+  // LoopDetectorSettings::guess_search (not in the reference): what the correlative search around init_guess found.  init_guess stays
+  // the pose-derived one; the ICP started from searched_guess when search_used is set.
+  Matrix4d searched_guess = Matrix4d::Identity();
+  int search_score = 0, guess_score = 0, runner_up_score = 0;    // best_score, guess_score, runner_up_score of smhip_guess_search_result
+  bool search_used = false;                     // search_score > guess_score
 };
+
+inline smhip_guess_search_options DefaultGuessSearchOptions() {
+  smhip_guess_search_options o;
+  smhip_guess_search_default_options(&o);
+  return o;
+}
 
 struct LoopDetectorSettings {                   // back_end/loop_detector_options.h:29-40
   float accept_scan_match_score = 0.75f;
@@ -95,20 +107,44 @@ struct LoopDetectorSettings {                   // back_end/loop_detector_option
   float m2dp_match_score = 0.99f;
   bool edge_information = false;     // (not in the reference) CloseLoop measures an accepted match's 6x6 information and leaves it on the edge
   EdgeInformationOptions edge_information_options;
+  // (not in the reference) CloseLoop searches a window around the pose-derived guess for the transform that puts the most source points
+  // into occupied target voxels (smhip_guess_search_f32, smhip.h) and starts the ICP there when that beats the guess's own score: the
+  // distance gate admits candidates 25 m apart, and a local ICP has no capture range of that size.  Off: nothing is searched.
+  bool guess_search = false;
+  smhip_guess_search_options guess_search_options = DefaultGuessSearchOptions();
 };
+
+// TEST HOOK: what CloseLoop calls for the search instead of scan_matcher->GuessSearch (the SetSolver pattern of smhip/pose_graph.h).
+// false = the search is refused, and the pair fails.
+using GuessSearcher = std::function<bool(const InnerCloudPtr& target, const InnerCloudPtr& source, const Matrix4d& guess,
+                                         const smhip_guess_search_options& options, smhip_guess_search_result* out)>;
 
 // LoopDetector::CloseLoop for one candidate pair of frames.  `scan_matcher` plays the stack matcher of :304; handing in
 // one that outlives the call (the loop detector checks many candidates in a row) keeps its device arena between
 // candidates -- it re-sizes itself when a cloud does not fit -- instead of allocating one per candidate.
 inline bool CloseLoop(const Matrix4d& target_global_pose, const InnerCloudPtr& target_cloud, const Matrix4d& source_global_pose,
                       const InnerCloudPtr& source_cloud, const LoopDetectorSettings& settings, LoopEdge* edge,
-                      registrator::IcpPointMatcherHip* scan_matcher) {
+                      registrator::IcpPointMatcherHip* scan_matcher, const GuessSearcher* searcher = nullptr) {
   Matrix4d init_guess = Multiply(RigidInverse(target_global_pose), source_global_pose);     // :287-288
   init_guess(2, 3) = 0.;                                                                     // :290 ("it is a trick")
   edge->init_guess = init_guess;
+  Matrix4d start = init_guess;
+  if (settings.guess_search) {
+    smhip_guess_search_result found;
+    const bool searched = searcher && *searcher ? (*searcher)(target_cloud, source_cloud, init_guess, settings.guess_search_options, &found)
+                                                : scan_matcher->GuessSearch(target_cloud, source_cloud, init_guess, settings.guess_search_options, &found);
+    if (!searched) {
+      std::fprintf(stderr, "[ERROR] CloseLoop: the guess search was refused; the pair (%d, %d) fails\n", edge->close_pair_index.first, edge->close_pair_index.second);
+      return false;
+    }
+    std::memcpy(edge->searched_guess.data(), found.transform, sizeof(double) * 16);
+    edge->search_score = found.best_score; edge->guess_score = found.guess_score; edge->runner_up_score = found.runner_up_score;
+    edge->search_used = found.best_score > found.guess_score;
+    if (edge->search_used) start = edge->searched_guess;
+  }
   scan_matcher->SetInputSource(source_cloud);
   scan_matcher->SetInputTarget(target_cloud);
-  scan_matcher->Align(init_guess, edge->transform);
+  scan_matcher->Align(start, edge->transform);
   const double match_score = scan_matcher->GetFitnessScore();
   if (match_score > settings.accept_scan_match_score) {                                     // :309
     edge->score = -std::log(match_score);                                                   // :312
@@ -122,10 +158,10 @@ inline bool CloseLoop(const Matrix4d& target_global_pose, const InnerCloudPtr& t
   return false;
 }
 inline bool CloseLoop(const Matrix4d& target_global_pose, const InnerCloudPtr& target_cloud, const Matrix4d& source_global_pose,
-                      const InnerCloudPtr& source_cloud, const LoopDetectorSettings& settings, LoopEdge* edge) {
+                      const InnerCloudPtr& source_cloud, const LoopDetectorSettings& settings, LoopEdge* edge, const GuessSearcher* searcher = nullptr) {
   registrator::IcpPointMatcherHip scan_matcher(settings.device, settings.max_points);       // :304
   scan_matcher.InitWithOptions();
-  return CloseLoop(target_global_pose, target_cloud, source_global_pose, source_cloud, settings, edge, &scan_matcher);
+  return CloseLoop(target_global_pose, target_cloud, source_global_pose, source_cloud, settings, edge, &scan_matcher, searcher);
 }
 
 // ---- LoopDetector (back_end/loop_detector.{h,cc}) ------------------------------------------------------------------------
@@ -341,6 +377,10 @@ class LoopDetector {
   const std::vector<std::shared_ptr<LoopFrame>>& GetFrames() const { return all_frames_; }
   std::pair<int, int> SearchWindow() const { return {search_window_start_, search_window_end_}; }    // (-1, -1): none set
   LoopStatus Status() const { return current_status_; }
+  // TEST HOOKS: `searcher` replaces the device guess search of CloseLoopPair (settings.guess_search), `matcher` the scan matcher it
+  // would create on first use
+  void SetGuessSearcher(GuessSearcher searcher) { guess_searcher_ = std::move(searcher); }
+  void SetScanMatcher(std::unique_ptr<registrator::IcpPointMatcherHip> matcher) { scan_matcher_ = std::move(matcher); }
   // what the last AddFrame that searched selected (for inspection and tests)
   const LoopCandidates& LastCandidates() const { return last_candidates_; }
 
@@ -361,7 +401,7 @@ class LoopDetector {
       scan_matcher_->InitWithOptions();
     }
     return CloseLoop(all_frames_[target_id]->global_pose, target_cloud, all_frames_[source_id]->global_pose, source_cloud, settings_, edge,
-                     scan_matcher_.get());
+                     scan_matcher_.get(), &guess_searcher_);
   }
   static InnerCloudPtr FrameCloud(const LoopFrame& frame) {
     if (frame.cloud) return frame.cloud;
@@ -379,6 +419,7 @@ class LoopDetector {
   int search_window_end_ = -1;
   LoopCandidates last_candidates_;
   std::unique_ptr<registrator::IcpPointMatcherHip> scan_matcher_;
+  GuessSearcher guess_searcher_;
 };
 
 struct SubmapPairMatchResult {

@@ -575,6 +575,7 @@ class IsamOptimizer {
     if (result.close_succeed) {                                                                 // :227-236
       for (const LoopEdge& edge : result.edges) {
         loop_edge_at_.push_back(static_cast<int>(graph_.Edges().size()));
+        loop_edge_searches_.push_back({edge.search_score, edge.guess_score, edge.runner_up_score, edge.search_used});
         if (options_.use_edge_information && edge.has_information) loop_edges_with_information_.push_back(edge);
         if (options_.use_edge_information && edge.has_information)
           graph_.AddLoopCloseEdge(edge.close_pair_index.first, edge.close_pair_index.second, edge.transform, edge.information, options_.loop_closure_huber);
@@ -654,6 +655,10 @@ class IsamOptimizer {
     }
     return out;
   }
+  // what the guess search of LoopDetectorSettings::guess_search found for every loop edge, in the order added (LoopEdgeReport's order);
+  // zeros for an edge that was not searched
+  struct LoopEdgeSearch { int search_score = 0, guess_score = 0, runner_up_score = 0; bool search_used = false; };
+  const std::vector<LoopEdgeSearch>& LoopEdgeSearches() const { return loop_edge_searches_; }
   // the loop edges that entered the graph with their own information (use_edge_information), in the order added
   const std::vector<LoopEdge>& LoopEdgesWithInformation() const { return loop_edges_with_information_; }
   int SolveCount() const { return solves_; }
@@ -727,6 +732,7 @@ class IsamOptimizer {
   Marginalizer marginalizer_;
   std::vector<int> loop_edge_at_;                   // the loop edges' places in graph_.Edges()
   std::vector<LoopEdge> loop_edges_with_information_;
+  std::vector<LoopEdgeSearch> loop_edge_searches_;
   bool main_solved_ = false;                        // the last solve was one of graph_, as it is now, and it succeeded
   PoseGraph graph_;
   std::vector<std::shared_ptr<LoopFrame>> frames_;

@@ -930,6 +930,27 @@ class IcpPointMatcherHip : public Interface {
     return true;
   }
 
+  // The correlative guess search (smhip_guess_search_f32, smhip.h) of `source` onto `target` around `guess`, on this matcher's handle:
+  // the rows go up as they are (InnerPointType, 5 floats) and the clouds an Align left on the device are not touched.  false when the
+  // search is refused or fails, with the reason on stderr and *out untouched.
+  virtual bool GuessSearch(const InnerCloudPtr& target, const InnerCloudPtr& source, const Matrix4d& guess, const smhip_guess_search_options& options,
+                           smhip_guess_search_result* out) {
+    SMHIP_CHECK(out != nullptr, "GuessSearch: out");
+    if (!target || target->Empty() || !source || source->Empty()) { std::fprintf(stderr, "[ERROR] IcpPointMatcherHip::GuessSearch: Empty cloud.\n"); return false; }
+    const auto& s = source->GetInnerCloud();
+    const auto& t = target->GetInnerCloud();
+    bool recreated = false;
+    if (!EnsureHandle(static_cast<int>(s.size()), static_cast<int>(t.size()), &recreated)) return false;
+    if (recreated) reading_on_device_ = reference_on_device_ = false;
+    const smhip_status st = smhip_guess_search_f32(arena_.handle, reinterpret_cast<const float*>(t.data()), static_cast<int>(t.size()), 5,
+                                                   reinterpret_cast<const float*>(s.data()), static_cast<int>(s.size()), 5, guess.data(), &options, out);
+    if (st != SMHIP_OK) {
+      std::fprintf(stderr, "[ERROR] smhip_guess_search_f32: %s (%s)\n", smhip_status_string(st), smhip_last_error(arena_.handle));
+      return false;
+    }
+    return true;
+  }
+
   // K independent (reading, reference) pairs through 2 K pair slots of a handle kept between calls: slots [0, K) hold the
   // ICP pairs, slots [K, 2 K) the score pairs; ONE launch sequence runs the K 150-iteration loops together.
   // accepted[k] = score >= 0.6 (Align's bool); results = guesses for pairs the device could not take.

@@ -123,6 +123,18 @@ class PoseGraphMarginalsStats(ctypes.Structure):
                 ("pcg_cap", ctypes.c_int32)]
 
 
+class GuessSearchOptions(ctypes.Structure):
+    _fields_ = [("resolution", ctypes.c_float), ("max_source_points", ctypes.c_int32), ("half_xy", ctypes.c_int32), ("half_z", ctypes.c_int32),
+                ("yaw_steps", ctypes.c_int32), ("reserved", ctypes.c_int32), ("yaw_step", ctypes.c_double)]
+
+
+class GuessSearchResult(ctypes.Structure):
+    _fields_ = [("transform", ctypes.c_double * 16), ("best_score", ctypes.c_int32), ("guess_score", ctypes.c_int32),
+                ("runner_up_score", ctypes.c_int32), ("n_source_used", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
+                ("best_yaw", ctypes.c_int32), ("best_i", ctypes.c_int32), ("best_j", ctypes.c_int32), ("best_k", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
 # name -> (restype, argtypes): every symbol include/smhip.h declares
 SIGNATURES = {
     "smhip_version": (ctypes.c_int, []),
@@ -257,6 +269,10 @@ SIGNATURES = {
     "smhip_pose_graph_marginals_default_options": (None, [ctypes.POINTER(PoseGraphMarginalsOptions)]),
     "smhip_pose_graph_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, c_double_p, ctypes.c_int, c_int32_p, c_double_p,
                                                   ctypes.POINTER(PoseGraphMarginalsOptions), ctypes.POINTER(PoseGraphMarginalsStats)]),
+    "smhip_guess_search_default_options": (None, [ctypes.POINTER(GuessSearchOptions)]),
+    "smhip_guess_search_f32": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                                              ctypes.POINTER(GuessSearchOptions), ctypes.POINTER(GuessSearchResult)]),
+    "smhip_guess_search_last": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, ctypes.c_int, c_int32_p, c_int32_p, c_int32_p, ctypes.c_int]),
     "smhip_mrvm_default_settings": (None, [ctypes.POINTER(MrvmSettings)]),
     "smhip_mrvm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MrvmSettings), ctypes.POINTER(ctypes.c_void_p)]),
     "smhip_mrvm_destroy": (ctypes.c_int, [ctypes.c_void_p]),

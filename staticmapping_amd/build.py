@@ -21,7 +21,7 @@ FLAGS_STAMP = os.path.join(OBJ_DIR, "flags.txt")          # the compile flags th
 
 # translation units, slowest first (each #includes its kernel files and fragments: its dependency file lists them)
 UNITS = ["smhip_api.hip", "smhip_mrvm.hip", "cloud_filters.hip", "prep_normals.hip", "smhip_ndt_gicp.hip", "smhip_filter_api.hip", "smhip_m2dp.hip",
-         "smhip_submap.hip", "smhip_pose_graph.hip", "smhip_icp_information.hip", "host_cloud.cc", "map_package.cc"]
+         "smhip_submap.hip", "smhip_pose_graph.hip", "smhip_icp_information.hip", "guess_search.hip", "host_cloud.cc", "map_package.cc"]
 
 
 def _hipcc() -> str:

@@ -175,6 +175,16 @@ Args Parse(int argc, char** argv) {
       a.loop_huber_given = true;
     }
     else if (k == "--loop-report") a.loop_report = val();
+    else if (k == "--loop-guess-search") { a.loop.guess_search = std::atoi(val().c_str()) != 0; a.loop_guess_given = true; }
+    else if (k == "--loop-guess-resolution") { a.loop.guess_search_options.resolution = static_cast<float>(std::atof(val().c_str())); a.loop_guess_given = true; }
+    else if (k == "--loop-guess-window") {
+      int hxy = -1, hz = -1, steps = -1;
+      double deg = std::nan("");
+      if (std::sscanf(val().c_str(), "%d,%d,%d,%lf", &hxy, &hz, &steps, &deg) != 4) hxy = -1;             // (refused below)
+      a.loop.guess_search_options.half_xy = hxy; a.loop.guess_search_options.half_z = hz; a.loop.guess_search_options.yaw_steps = steps;
+      a.loop.guess_search_options.yaw_step = deg * M_PI / 180.0;
+      a.loop_guess_given = true;
+    }
     else if (k == "--pose-covariance") a.pose_covariance = val();
     else if (k == "--pose-covariance-chunk") a.pose_covariance_chunk = std::atoi(val().c_str());
     else if (k == "--pose-graph-dump") a.pose_graph_dump = val();
@@ -235,6 +245,8 @@ Args Parse(int argc, char** argv) {
              "  loop closing: [--close-loops corrected_pose.txt] [--loop-ignore-threshold 15] [--loop-detect-count 1] [--loop-history 4] "
              "[--loop-max-distance 25] [--loop-max-z 1] [--loop-use-descriptor 1] [--loop-m2dp-score 0.99] [--loop-accept-score 0.75] "
              "[--loop-huber 0 (the Huber threshold of the loop edges; 0: none)] [--loop-report FILE (a line per loop edge: target source norm weight)] "
+             "[--loop-guess-search 1 (search a window around each candidate's pose-derived guess before its ICP; the report's lines gain "
+             "search_score guess_score runner_up_score search_used)] [--loop-guess-resolution 0.5] [--loop-guess-window half_xy,half_z,yaw_steps,yaw_step_deg (20,2,10,2)] "
              "[--pose-covariance FILE (a line per submap: index held sigma_rot[3] sigma_pos_world[3] cov[21]) [--pose-covariance-chunk 256] [--pose-graph-dump FILE]]\n"
              "  edge information (with --close-loops): [--edge-information 1 (scan-match edges weighted by the matcher's own 6x6 information)] "
              "[--edge-information-scale 1] [--edge-report FILE (a line per edge: i j chain|loop kept residual_sigma strength[6] weakest[6])]\n"
@@ -273,6 +285,12 @@ Args Parse(int argc, char** argv) {
   if (!a.gps_enu.empty() && a.close_loops.empty()) Die("--gps-enu needs --close-loops");
   if (a.loop_huber_given && a.close_loops.empty() && !a.Join()) Die("--loop-huber needs --close-loops");
   if (!a.loop_report.empty() && a.close_loops.empty() && !a.Join()) Die("--loop-report needs --close-loops");
+  if (a.loop_guess_given && a.close_loops.empty() && !a.Join()) Die("--loop-guess-search, --loop-guess-resolution and --loop-guess-window need --close-loops");
+  if (a.loop_guess_given) {
+    const smhip_guess_search_options& g = a.loop.guess_search_options;
+    if (!std::isfinite(g.resolution) || !(g.resolution > 0.f) || g.half_xy < 0 || g.half_z < 0 || g.yaw_steps < 0 || !std::isfinite(g.yaw_step))
+      Die("bad guess search (--loop-guess-resolution finite and > 0, --loop-guess-window half_xy,half_z,yaw_steps,yaw_step_deg, none negative)");
+  }
   if (!a.pose_covariance.empty() && a.close_loops.empty()) Die("--pose-covariance needs --close-loops");
   if ((!a.pose_graph_dump.empty() || a.pose_covariance_chunk != 256) && a.pose_covariance.empty()) Die("--pose-graph-dump and --pose-covariance-chunk need --pose-covariance");
   if (a.pose_covariance_chunk < 1) Die("--pose-covariance-chunk takes a count of at least 1");

@@ -64,6 +64,10 @@ struct Args {
   double loop_huber = 0.0;
   bool loop_huber_given = false;
   std::string loop_report;
+  // --loop-guess-search 1: LoopDetectorSettings::guess_search (in `loop` above), the correlative search around every candidate's
+  // pose-derived guess before its ICP; --loop-guess-resolution R and --loop-guess-window half_xy,half_z,yaw_steps,yaw_step_deg set its
+  // options.  With it on, every --loop-report line gains search_score guess_score runner_up_score search_used.
+  bool loop_guess_given = false;
   // --pose-covariance FILE: after the final optimisation, every submap's marginal covariance (include/smhip.h, "Marginal covariances"):
   // a line per submap, `index held sigma_rot[3] sigma_pos_world[3] cov[21]` -- held: 1 for the submap the graph holds (all zeros);
   // sigma_rot: the square roots of the rotation part's diagonal, rad, in the submap's own frame; sigma_pos_world: those of the diagonal
@@ -500,6 +504,7 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   struct EdgeReportRow { int i, j; bool loop; be::EdgeInformation information; };
   std::vector<EdgeReportRow> edge_report;
   std::vector<smhip::back_end::LoopEdgeWeight> loop_report;
+  std::vector<smhip::back_end::IsamOptimizer::LoopEdgeSearch> loop_searches;
   std::ofstream out(a.close_loops);
   if (!out) Die("cannot write " + a.close_loops);
   out.precision(8);
@@ -646,6 +651,7 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
       loop_report = optimizer.LoopEdgeReport();
       if (static_cast<int>(loop_report.size()) != optimizer.LoopEdgeCount()) { std::fprintf(stderr, "smhip_shard: the loop edges' report was refused\n"); rc = 3; }
       for (const be::LoopEdgeWeight& w : loop_report) res.downweighted += w.weight < 1.0;
+      loop_searches = optimizer.LoopEdgeSearches();
     }
     if (rc == 0 && (!a.pose_covariance.empty() || (io.use_odom && a.odom_calib))) {
       // the submaps (with the flag), then the calibration and GPS-frame vertices; 256 nodes a call, so that a workgroup runs one query
@@ -749,7 +755,13 @@ inline int CloseLoops(const Args& a, const std::vector<std::string>& files, int 
   if (!a.loop_report.empty()) {
     std::ofstream rep(a.loop_report);
     if (!rep) Die("cannot write " + a.loop_report);
-    for (const smhip::back_end::LoopEdgeWeight& w : loop_report) rep << Fmt("%d %d %.8g %.8g\n", w.target, w.source, w.norm, w.weight);
+    for (size_t e = 0; e < loop_report.size(); ++e) {
+      const smhip::back_end::LoopEdgeWeight& w = loop_report[e];
+      rep << Fmt("%d %d %.8g %.8g", w.target, w.source, w.norm, w.weight);
+      if (a.loop.guess_search && e < loop_searches.size())
+        rep << Fmt(" %d %d %d %d", loop_searches[e].search_score, loop_searches[e].guess_score, loop_searches[e].runner_up_score, loop_searches[e].search_used ? 1 : 0);
+      rep << "\n";
+    }
   }
   if (!a.edge_report.empty()) {
     std::ofstream rep(a.edge_report);

@@ -643,6 +643,7 @@ extern "C" void smhip_internal_free_ndt(smhip_context* h);
 extern "C" void smhip_internal_free_gicp(smhip_context* h);
 extern "C" void smhip_internal_free_m2dp(smhip_context* h);
 extern "C" void smhip_internal_free_pose_graph(smhip_context* h);
+extern "C" void smhip_internal_free_guess_search(smhip_context* h);
 
 smhip_status smhip_destroy(smhip_handle h) {
   if (!h) return SMHIP_ERR_INVALID_ARGUMENT;
@@ -652,6 +653,7 @@ smhip_status smhip_destroy(smhip_handle h) {
   smhip_internal_free_gicp(h);
   smhip_internal_free_m2dp(h);
   smhip_internal_free_pose_graph(h);
+  smhip_internal_free_guess_search(h);
   if (h->prep) prep_destroy(h->prep);
   if (h->prep_batch) prep_destroy(h->prep_batch);
   if (h->filt) filt_destroy(h->filt);

@@ -21,12 +21,14 @@ struct smhip_ndt_state;         // the NDT / NdtWithGicp unit's own (smhip_ndt_a
 struct smhip_gicp_state;        // freed through smhip_internal_free_ndt / _gicp
 struct smhip_m2dp_state;        // the descriptor unit's own (smhip_m2dp.hip): created on first use, freed through smhip_internal_free_m2dp
 struct smhip_pose_graph_state;  // the pose-graph unit's own (smhip_pose_graph.hip): created on first use, freed through smhip_internal_free_pose_graph
+struct smhip_guess_search_state;  // the guess-search unit's own (guess_search.hip): created on first use, freed through smhip_internal_free_guess_search
 
 struct smhip_context {
   smhip_ndt_state* ndt = nullptr;
   smhip_gicp_state* gicp = nullptr;
   smhip_m2dp_state* m2dp = nullptr;
   smhip_pose_graph_state* pose_graph = nullptr;
+  smhip_guess_search_state* guess_search = nullptr;
   PrepWorkspace* prep = nullptr;          // device CalculateNormals workspace (allocated on first use)
   PrepWorkspace* prep_batch = nullptr;    // the same sized for every slot at once (batched target preparation)
   FilterWorkspace* filt = nullptr;        // device pre-filters (allocated on first use)
