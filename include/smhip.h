@@ -421,6 +421,9 @@ smhip_status smhip_ndt_compute_derivatives(smhip_handle h, const double pose6[6]
  * (pairs may be NULL). */
 smhip_status smhip_ndt_compute_derivatives_ex(smhip_handle h, const double pose6[6], int compute_hessian, int double_math,
                                               double* score, double grad[6], double hess[36], double* pairs);
+/* the Newton solve of an Align's serial end (JacobiSVD(H).solve(b), ndt_omp_impl.hpp:127-129) as the device computes it, a lane
+ * per system: H holds n row-major 6x6 matrices, b and x n 6-vectors.  Needs no cloud and no voxel table. */
+smhip_status smhip_ndt_debug_solve6(smhip_handle h, int n, const double* H, const double* b, double* x);
 /* measurement hook: `launches` back-to-back computeDerivatives launches (with Hessian) over slots first_slot .. + npairs - 1 at the
  * poses their last Align ended with, HIP events around them on the handle's stream: *ms_per_launch = the average duration of
  * the kernel, *pairs_per_launch = the (point, voxel) pairs one launch works through (for its algorithmic bytes).  The slots'

@@ -183,8 +183,21 @@ def _ndt_lib():
         L.smref_ndt_align.argtypes = [fp, ctypes.c_int, fp, ctypes.c_int, dp, ctypes.c_float, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, ip, ip, dp, dp, ip, dp]
         L.smref_ndt_align.restype = ctypes.c_int
+        L.smref_ndt_align_traced.argtypes = L.smref_ndt_align.argtypes + [ip, ctypes.c_int, ip]
+        L.smref_ndt_align_traced.restype = ctypes.c_int
+        L.smref_ndt_svd_solve6.argtypes = [dp, dp, dp]
+        L.smref_ndt_svd_solve6.restype = None
         L._ndt_ready = True
     return L
+
+
+def ndt_svd_solve6(H, b):
+    """The C restatement's JacobiSVD(H).solve(b) on one 6x6 (ndt_omp_impl.hpp:127-129)."""
+    H, ph = _d(np.asarray(H).reshape(6, 6))
+    b, pb = _d(b)
+    x = np.zeros(6)
+    _ndt_lib().smref_ndt_svd_solve6(ph, pb, x.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return x
 
 
 def _f3(a):
@@ -228,19 +241,25 @@ class NdtGrid:
 
 def ndt_align(source_f32, target_f32, guess=None, resolution=1.0, step_size=0.1, outlier_ratio=0.55, trans_eps=0.1,
               max_iterations=35, nthreads_deriv=6, nthreads_other=1, with_fitness=True):
-    """C restatement of Ndt::Align (ndt.cc:38-64 -> pclomp).  nthreads_deriv = 6 is the reference's setting (ndt.cc:32)."""
+    """C restatement of Ndt::Align (ndt.cc:38-64 -> pclomp).  nthreads_deriv = 6 is the reference's setting (ndt.cc:32).
+    `trace`: per Newton iteration dict(trials = the More-Thuente loop's length, hessian_eval = the closing Hessian-only evaluation
+    happened, clamped = the Newton step was cut to step_size, reversed = the direction was turned round)."""
     L = _ndt_lib()
     s, ps = _f3(source_f32); t, pt = _f3(target_f32)
     g, pg = _d(np.eye(4) if guess is None else guess)
     res = np.zeros((4, 4)); fit = ctypes.c_double(); it = ctypes.c_int(); calls = ctypes.c_int(); tp = ctypes.c_double()
     mn = ctypes.c_double(); nv = ctypes.c_int(); bt = np.zeros(5)
-    rc = L.smref_ndt_align(ps, s.shape[0], pt, t.shape[0], pg, ctypes.c_float(resolution), step_size, outlier_ratio, trans_eps,
-                           max_iterations, nthreads_deriv, nthreads_other, int(with_fitness),
-                           res.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(fit), ctypes.byref(it), ctypes.byref(calls),
-                           ctypes.byref(tp), ctypes.byref(mn), ctypes.byref(nv), bt.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    cap = max(0, int(max_iterations)) + 3
+    tr = np.zeros((cap, 4), dtype=np.int32); tn = ctypes.c_int()
+    rc = L.smref_ndt_align_traced(ps, s.shape[0], pt, t.shape[0], pg, ctypes.c_float(resolution), step_size, outlier_ratio, trans_eps,
+                                  max_iterations, nthreads_deriv, nthreads_other, int(with_fitness),
+                                  res.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(fit), ctypes.byref(it), ctypes.byref(calls),
+                                  ctypes.byref(tp), ctypes.byref(mn), ctypes.byref(nv), bt.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                  tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), cap, ctypes.byref(tn))
     if rc != 0:
         raise RuntimeError(f"smref_ndt_align failed: {rc}")
-    return dict(result=res, score=fit.value, iterations=it.value, derivative_calls=calls.value, trans_probability=tp.value,
+    trace = [dict(trials=int(r[0]), hessian_eval=bool(r[1]), clamped=bool(r[2]), reversed=bool(r[3])) for r in tr[:tn.value]]
+    return dict(result=res, trace=trace, score=fit.value, iterations=it.value, derivative_calls=calls.value, trans_probability=tp.value,
                 mean_neighbours=mn.value, voxels=nv.value,
                 block_times=dict(applyFilter=bt[0], computeDerivatives=bt[1], transformPointCloud=bt[2], getFitnessScore=bt[3], Align=bt[4]))
 

@@ -352,7 +352,8 @@ static double trial_value(double a_l, double f_l, double g_l, double a_u, double
     const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
     const double nxt = fabs(a_c - a_t) < fabs(a_s - a_t) ? a_c : a_s;
     const double lim = a_t + 0.66 * (a_u - a_t);
-    return a_t > a_l ? (lim < nxt ? lim : nxt) : (lim > nxt ? lim : nxt);
+    /* std::min(lim, nxt) / std::max(lim, nxt): a NaN nxt (a_t == a_l, as after every interval update) leaves lim */
+    return a_t > a_l ? (nxt < lim ? nxt : lim) : (lim < nxt ? nxt : lim);
   }
   const double z = 3 * (f_t - f_u) / (a_t - a_u) - g_t - g_u, w = sqrt(z * z - g_t * g_u);
   return a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w);
@@ -362,11 +363,14 @@ static double trial_value(double a_l, double f_l, double g_l, double a_u, double
  * nthreads_deriv: computeDerivatives threads (the reference: 6, ndt.cc:32); nthreads_other: transform / fitness threads
  * (the reference: 1).  block_times[5]: applyFilter, computeDerivatives (summed), transformPointCloud (summed),
  * getFitnessScore (kd-tree build + queries), whole Align. */
-int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const double* guess, float resolution,
-                    double step_size, double outlier_ratio, double trans_eps, int max_iterations,
-                    int nthreads_deriv, int nthreads_other, int with_fitness,
-                    double* result, double* fitness, int* iterations, int* derivative_calls, double* trans_probability,
-                    double* mean_neighbours, int* n_voxels, double* block_times) {
+/* trace (may be NULL): four ints per Newton iteration, at most trace_cap iterations -- the line-search loop's length, whether the
+ * closing Hessian-only evaluation happened, whether the first trial was clamped to step_size, whether the direction was reversed;
+ * *trace_n = the iterations recorded. */
+int smref_ndt_align_traced(const float* src, int ns, const float* tgt, int nt, const double* guess, float resolution,
+                           double step_size, double outlier_ratio, double trans_eps, int max_iterations,
+                           int nthreads_deriv, int nthreads_other, int with_fitness,
+                           double* result, double* fitness, int* iterations, int* derivative_calls, double* trans_probability,
+                           double* mean_neighbours, int* n_voxels, double* block_times, int* trace, int trace_cap, int* trace_n) {
   const double t_begin = now_s();
   double t_grid, t_der = 0, t_tf = 0, t_fit = 0, t0;
   t0 = now_s();
@@ -392,6 +396,7 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
   t_der += now_s() - t0;
   while (!converged) {                                                                                     /* :121 */
     double mg[6], dp[6], step_dir[6];
+    int tr_steps = 0, tr_hess = 0, tr_clamp = 0, tr_rev = 0;
     for (int i = 0; i < 6; ++i) mg[i] = -g[i];
     svd_solve6(H, mg, dp);                                                                                 /* :127-129 */
     double dp_norm = 0;
@@ -408,7 +413,7 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
     int skip = 0;
     if (d_phi_0 >= 0) {
       if (d_phi_0 == 0) skip = 1;
-      else { d_phi_0 = -d_phi_0; for (int i = 0; i < 6; ++i) step_dir[i] = -step_dir[i]; }
+      else { d_phi_0 = -d_phi_0; for (int i = 0; i < 6; ++i) step_dir[i] = -step_dir[i]; tr_rev = 1; }
     }
     if (!skip) {
       const double mu = 1e-4, nu = 0.9;
@@ -416,6 +421,7 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
       int interval_converged = (step_max - step_min) > 0;                                                   /* :795 (sic) */
       int open_interval = 1;
       a_t = step_init < step_max ? step_init : step_max; if (a_t < step_min) a_t = step_min;                /* :797-799 */
+      tr_clamp = step_init > step_max;
       double x_t[6];
       for (int i = 0; i < 6; ++i) x_t[i] = p[i] + step_dir[i] * a_t;
       pose_to_matrix_f32(x_t, fin);                                                                         /* :803-806 */
@@ -451,8 +457,10 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
                                            : update_interval(&a_l, &f_l, &g_l, &a_u, &f_u, &g_u, a_t, phi_t, d_phi_t);
         ++step_iterations;
       }
+      tr_steps = step_iterations;
       if (step_iterations) {                                                                                /* :912-913 */
         double gd[6], sd;
+        tr_hess = 1;
         t0 = now_s();
         smref_ndt_compute_derivatives(grid, src, trans, ns, x_t, outlier_ratio, 1, nthreads_deriv, &sd, gd, H); ++calls;
         t_der += now_s() - t0;
@@ -460,11 +468,13 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
     }
     dp_norm = a_t;                                                                                          /* :142 */
     for (int i = 0; i < 6; ++i) p[i] += step_dir[i] * dp_norm;                                              /* :143, :152 */
+    if (trace && it < trace_cap) { trace[4 * it] = tr_steps; trace[4 * it + 1] = tr_hess; trace[4 * it + 2] = tr_clamp; trace[4 * it + 3] = tr_rev; }
     if (it > max_iterations || (it && fabs(dp_norm) < trans_eps)) converged = 1;                            /* :158-162 */
     ++it;                                                                                                   /* :164 */
   }
   for (int i = 0; i < 16; ++i) result[i] = (double)fin[i];
   *iterations = it; *derivative_calls = calls; *trans_probability = score / ns;
+  if (trace_n) *trace_n = it < trace_cap ? it : trace_cap;
   if (mean_neighbours) *mean_neighbours = (double)pairs / ns;
   if (n_voxels) *n_voxels = grid->nvox;
   *fitness = 0;
@@ -494,3 +504,16 @@ int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const do
   smref_ndt_grid_free(grid);
   return 0;
 }
+
+int smref_ndt_align(const float* src, int ns, const float* tgt, int nt, const double* guess, float resolution,
+                    double step_size, double outlier_ratio, double trans_eps, int max_iterations,
+                    int nthreads_deriv, int nthreads_other, int with_fitness,
+                    double* result, double* fitness, int* iterations, int* derivative_calls, double* trans_probability,
+                    double* mean_neighbours, int* n_voxels, double* block_times) {
+  return smref_ndt_align_traced(src, ns, tgt, nt, guess, resolution, step_size, outlier_ratio, trans_eps, max_iterations, nthreads_deriv,
+                                nthreads_other, with_fitness, result, fitness, iterations, derivative_calls, trans_probability,
+                                mean_neighbours, n_voxels, block_times, 0, 0, 0);
+}
+
+/* the Newton solve alone (JacobiSVD(H).solve(b), :127-129) on one row-major 6x6 */
+void smref_ndt_svd_solve6(const double* H, const double* b, double* x) { svd_solve6(H, b, x); }

@@ -278,6 +278,8 @@ def _update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
 
 
 def _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
+    # (IEEE doubles: 0 / 0 is NaN, not an exception; min / max below answer a NaN second argument with the first, as std::min does)
+    a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t = (np.float64(v) for v in (a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t))
     with np.errstate(all="ignore"):
         if f_t > f_l:
             z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l
@@ -303,6 +305,176 @@ def _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
         return a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w)
 
 
+class _Book:
+    """Branch counters and decision margins of one newton_mt run (tests only).  Every comparison the loop takes goes through
+    cmp(): counts[name] counts the branch, margins holds (name, |a - b| / max(|a|, |b|, scale)) -- how far the decision was from
+    flipping; a comparison of two copies of one number (a clamped trial against the bound it was clamped to) has margin 0 and is
+    listed in `exact`."""
+
+    def __init__(self):
+        self.counts, self.margins, self.exact = {}, [], []
+
+    def hit(self, name):
+        self.counts[name] = self.counts.get(name, 0) + 1
+
+    def cmp(self, name, a, b, scale=0.0):
+        if a != a or b != b:                       # a comparison with a NaN clears no margin
+            self.margins.append((name, 0.0))
+            return
+        den = max(abs(a), abs(b), abs(scale))
+        if a == b:
+            self.exact.append(name)
+        elif den > 0:
+            self.margins.append((name, abs(a - b) / den))
+
+
+class _NoBook:
+    def hit(self, name): pass
+    def cmp(self, name, a, b, scale=0.0): pass
+
+
+def _update_interval_b(book, a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
+    book.cmp("update:f_t>f_l", f_t, f_l)
+    r = _update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t)
+    if f_t > f_l:
+        book.hit("update:1")
+    else:
+        book.cmp("update:g_t*(a_l-a_t)", g_t * (a_l - a_t), 0.0, abs(g_t) * max(abs(a_l), abs(a_t)))
+        book.hit("update:2" if g_t * (a_l - a_t) > 0 else "update:3" if g_t * (a_l - a_t) < 0 else "update:4")
+    return r
+
+
+def _trial_value_b(book, a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
+    book.cmp("trial:f_t>f_l", f_t, f_l)
+    if f_t > f_l:
+        book.hit("trial:1")
+    else:
+        book.cmp("trial:g_t*g_l<0", g_t * g_l, 0.0, abs(g_t) * abs(g_l))
+        if g_t * g_l < 0:
+            book.hit("trial:2")
+        else:
+            book.cmp("trial:|g_t|<=|g_l|", abs(g_t), abs(g_l))
+            book.hit("trial:3" if abs(g_t) <= abs(g_l) else "trial:4")
+    return _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t)
+
+
+def newton_mt(objective, p0, step_size=0.1, trans_eps=0.1, max_iterations=35, trace=None, book=None, solve=None):
+    """computeTransformation's Newton loop with computeStepLengthMT (ndt_omp_impl.hpp:81-171, 757-916) around a callable
+    objective(kind, x, compute_hessian) -> (score, gradient[6], hessian[6, 6] or None); kind is 'init' (:119, at p0), 'trial'
+    (:813), 'mt' (:872, no Hessian) or 'hess' (:912-913, the pose of the last 'mt' once more, only its Hessian is used).
+    -> dict(p, score, iterations, derivative_calls).  `book`: a _Book that counts branches and records decision margins."""
+    B = book if book is not None else _NoBook()
+    solve = solve or svd_solve
+    p = np.array(p0, dtype=np.float64)
+    calls = 0
+    score, g, H = objective("init", p.copy(), True); calls += 1                      # :119
+    it = 0
+    converged = False
+    while not converged:                                                             # :121
+        with np.errstate(all="ignore"):
+            dp = solve(H, -g) if (np.isfinite(H).all() and np.isfinite(g).all()) else np.full(6, np.nan)   # :127-129
+            dp_norm = float(np.sqrt(np.sum(dp * dp)))
+        if dp_norm == 0 or dp_norm != dp_norm:                                       # :134-139
+            B.hit("exit:dp_norm_nan" if dp_norm != dp_norm else "exit:dp_norm_zero")
+            break
+        step_dir = dp / dp_norm                                                      # :141
+        # ---- computeStepLengthMT(p, step_dir, dp_norm, step_size, trans_eps / 2, ...)  :757-916
+        step_init, step_max, step_min = dp_norm, step_size, trans_eps / 2
+        phi_0 = -score
+        d_phi_0 = 0.0
+        for i in range(6):
+            d_phi_0 -= g[i] * step_dir[i]
+        d_phi_0 = float(d_phi_0)
+        B.cmp("d_phi_0>=0", d_phi_0, 0.0, float(np.sum(np.abs(g * step_dir))))
+        a_t = 0.0
+        skip = False
+        rec = dict(trials=0, hessian_eval=False, clamped=False, reversed=False)
+        if d_phi_0 >= 0:
+            if d_phi_0 == 0:
+                skip = True
+                B.hit("d_phi_0==0")
+            else:
+                d_phi_0 *= -1
+                step_dir = -step_dir
+                rec["reversed"] = True
+                B.hit("d_phi_0>0")
+        if not skip:
+            mu, nu = 1e-4, 0.9
+            a_l = a_u = 0.0
+            f_l = _psi(a_l, phi_0, phi_0, d_phi_0, mu); g_l = _dpsi(d_phi_0, d_phi_0, mu)
+            f_u, g_u = f_l, g_l
+            interval_converged = (step_max - step_min) > 0                           # :795 (sic)
+            open_interval = True
+            B.cmp("step_init<step_max", step_init, step_max); B.cmp("step_init>step_min", step_init, step_min)
+            a_t = max(min(step_init, step_max), step_min)                            # :797-799
+            rec["clamped"] = step_init > step_max
+            if step_init > step_max:
+                B.hit("first_trial_clamped")
+            x_t = p + step_dir * a_t
+            score, g, H = objective("trial", x_t.copy(), True); calls += 1           # :803-813
+            phi_t = -score
+            d_phi_t = 0.0
+            for i in range(6):
+                d_phi_t -= g[i] * step_dir[i]
+            d_phi_t = float(d_phi_t)
+            psi_t = _psi(a_t, phi_t, phi_0, d_phi_0, mu); d_psi_t = _dpsi(d_phi_t, d_phi_0, mu)
+            step_iterations = 0
+            while True:
+                if interval_converged or step_iterations >= 10:
+                    if step_iterations >= 10:
+                        B.hit("mt:cap")
+                    break
+                B.cmp("wolfe:psi_t<=0", psi_t, 0.0, abs(phi_t) + abs(phi_0)); B.cmp("wolfe:d_phi_t", d_phi_t, -nu * d_phi_0)
+                if psi_t <= 0 and d_phi_t <= -nu * d_phi_0:
+                    B.hit("mt:wolfe")
+                    break
+                if open_interval:
+                    a_t = _trial_value_b(B, a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t)
+                else:
+                    a_t = _trial_value_b(B, a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t)
+                B.cmp("a_t<step_max", a_t, step_max); B.cmp("a_t>step_min", a_t, step_min)
+                a_t = max(min(a_t, step_max), step_min)
+                x_t = p + step_dir * a_t
+                score, g, _ = objective("mt", x_t.copy(), False); calls += 1         # :870-872
+                phi_t = -score
+                d_phi_t = 0.0
+                for i in range(6):
+                    d_phi_t -= g[i] * step_dir[i]
+                d_phi_t = float(d_phi_t)
+                psi_t = _psi(a_t, phi_t, phi_0, d_phi_0, mu); d_psi_t = _dpsi(d_phi_t, d_phi_0, mu)
+                if open_interval:
+                    B.cmp("close:psi_t<=0", psi_t, 0.0, abs(phi_t) + abs(phi_0)); B.cmp("close:d_psi_t>=0", d_psi_t, 0.0, abs(d_phi_t))
+                if open_interval and (psi_t <= 0 and d_psi_t >= 0):
+                    open_interval = False
+                    B.hit("mt:closed")
+                    f_l = f_l + phi_0 - mu * d_phi_0 * a_l; g_l = g_l + mu * d_phi_0
+                    f_u = f_u + phi_0 - mu * d_phi_0 * a_u; g_u = g_u + mu * d_phi_0
+                if open_interval:
+                    a_l, f_l, g_l, a_u, f_u, g_u, interval_converged = _update_interval_b(B, a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t)
+                else:
+                    a_l, f_l, g_l, a_u, f_u, g_u, interval_converged = _update_interval_b(B, a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t)
+                step_iterations += 1
+            rec["trials"] = step_iterations
+            if step_iterations:                                                      # :912-913
+                _, _, H = objective("hess", x_t.copy(), True); calls += 1
+                rec["hessian_eval"] = True
+                B.hit("loop>=1_with_hess")
+            else:
+                B.hit("loop0_no_hess")
+        dp_norm = a_t                                                                # :142
+        dp = step_dir * dp_norm                                                      # :143
+        p = p + dp                                                                   # :152
+        if trace is not None:
+            trace.append(dict(p=p.copy(), score=score, step=dp_norm, **rec))
+        if it:
+            B.cmp("|dp_norm|<trans_eps", abs(dp_norm), trans_eps)
+        if it > max_iterations or (it and abs(dp_norm) < trans_eps):                 # :158-162
+            converged = True
+            B.hit("exit:max_iterations" if it > max_iterations else "exit:trans_eps")
+        it += 1                                                                      # :164
+    return dict(p=p, score=score, iterations=it, derivative_calls=calls)
+
+
 def ndt_align(source_f32, target_f32, guess=None, resolution=1.0, step_size=0.1, outlier_ratio=0.55,
               trans_eps=0.1, max_iterations=35, grid: VoxelGrid | None = None, with_fitness=True, trace=None, real=None):
     """registrators/ndt.cc:38-64 -> pclomp computeTransformation (ndt_omp_impl.hpp:81-171).
@@ -316,83 +488,25 @@ def ndt_align(source_f32, target_f32, guess=None, resolution=1.0, step_size=0.1,
         grid = VoxelGrid(tgt, resolution)
     d1, d2, _ = gauss_constants(resolution, outlier_ratio)
     G = np.eye(4, dtype=F) if guess is None else np.asarray(guess).astype(F)       # guess.cast<float>(), ndt.cc:58
-    final = G.copy()
-    trans = src.copy()
+    st = dict(final=G.copy(), trans=src.copy())
     if not np.array_equal(G, np.eye(4, dtype=F)):                                    # :95-101
-        trans = transform_cloud_f32(src, G)
+        st["trans"] = transform_cloud_f32(src, G)
     p = np.zeros(6)
-    p[:3] = final[:3, 3].astype(np.float64)                                          # :107-111
-    p[3:] = euler_xyz_from_matrix(final[:3, :3]).astype(F).astype(np.float64)        # Vector3f eulerAngles
-    calls = 0
-    score, g, H, _ = compute_derivatives(grid, src, trans, p, d1, d2, True, real=real); calls += 1    # :119
-    it = 0
-    converged = False
-    while not converged:                                                             # :121
-        dp = svd_solve(H, -g)                                                        # :127-129
-        dp_norm = np.linalg.norm(dp)
-        if dp_norm == 0 or dp_norm != dp_norm:                                       # :134-139
-            break
-        step_dir = dp / dp_norm                                                      # :141
-        # ---- computeStepLengthMT(p, step_dir, dp_norm, step_size, trans_eps / 2, ...)  :757-916
-        step_init, step_max, step_min = dp_norm, step_size, trans_eps / 2
-        phi_0 = -score
-        d_phi_0 = -(g @ step_dir)
-        a_t = 0.0
-        skip = False
-        if d_phi_0 >= 0:
-            if d_phi_0 == 0:
-                skip = True
-            else:
-                d_phi_0 *= -1
-                step_dir = -step_dir
-        if not skip:
-            mu, nu = 1e-4, 0.9
-            a_l = a_u = 0.0
-            f_l = _psi(a_l, phi_0, phi_0, d_phi_0, mu); g_l = _dpsi(d_phi_0, d_phi_0, mu)
-            f_u, g_u = f_l, g_l
-            interval_converged = (step_max - step_min) > 0                           # :795 (sic)
-            open_interval = True
-            a_t = max(min(step_init, step_max), step_min)                            # :797-799
-            x_t = p + step_dir * a_t
-            final = pose_to_matrix_f32(x_t)                                          # :803-806
-            trans = transform_cloud_f32(src, final)                                  # :809
-            score, g, H, _ = compute_derivatives(grid, src, trans, x_t, d1, d2, True, real=real); calls += 1   # :813
-            phi_t = -score; d_phi_t = -(g @ step_dir)
-            psi_t = _psi(a_t, phi_t, phi_0, d_phi_0, mu); d_psi_t = _dpsi(d_phi_t, d_phi_0, mu)
-            step_iterations = 0
-            while (not interval_converged) and step_iterations < 10 and not (psi_t <= 0 and d_phi_t <= -nu * d_phi_0):
-                if open_interval:
-                    a_t = _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t)
-                else:
-                    a_t = _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t)
-                a_t = max(min(a_t, step_max), step_min)
-                x_t = p + step_dir * a_t
-                final = pose_to_matrix_f32(x_t)
-                trans = transform_cloud_f32(src, final)
-                score, g, _, _ = compute_derivatives(grid, src, trans, x_t, d1, d2, False, real=real); calls += 1
-                phi_t = -score; d_phi_t = -(g @ step_dir)
-                psi_t = _psi(a_t, phi_t, phi_0, d_phi_0, mu); d_psi_t = _dpsi(d_phi_t, d_phi_0, mu)
-                if open_interval and (psi_t <= 0 and d_psi_t >= 0):
-                    open_interval = False
-                    f_l = f_l + phi_0 - mu * d_phi_0 * a_l; g_l = g_l + mu * d_phi_0
-                    f_u = f_u + phi_0 - mu * d_phi_0 * a_u; g_u = g_u + mu * d_phi_0
-                if open_interval:
-                    a_l, f_l, g_l, a_u, f_u, g_u, interval_converged = _update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t)
-                else:
-                    a_l, f_l, g_l, a_u, f_u, g_u, interval_converged = _update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t)
-                step_iterations += 1
-            if step_iterations:                                                      # :912-913
-                _, _, H, _ = compute_derivatives(grid, src, trans, x_t, d1, d2, True, real=real); calls += 1
-        dp_norm = a_t                                                                # :142
-        dp = step_dir * dp_norm                                                      # :143
-        p = p + dp                                                                   # :152
-        if trace is not None:
-            trace.append(dict(p=p.copy(), score=score, step=dp_norm))
-        if it > max_iterations or (it and abs(dp_norm) < trans_eps):                 # :158-162
-            converged = True
-        it += 1                                                                      # :164
+    p[:3] = st["final"][:3, 3].astype(np.float64)                                    # :107-111
+    p[3:] = euler_xyz_from_matrix(st["final"][:3, :3]).astype(F).astype(np.float64)  # Vector3f eulerAngles
+
+    def objective(kind, x, hess):
+        if kind in ("trial", "mt"):
+            st["final"] = pose_to_matrix_f32(x)                                      # :803-806
+            st["trans"] = transform_cloud_f32(src, st["final"])                      # :809
+        sc, g, H, _ = compute_derivatives(grid, src, st["trans"], x, d1, d2, hess, real=real)
+        return sc, g, H
+
+    run = newton_mt(objective, p, step_size, trans_eps, max_iterations, trace=trace)
+    final = st["final"]
     result = final.astype(np.float64)                                                # getFinalTransformation().cast<double>()
-    out = dict(result=result, iterations=it, derivative_calls=calls, trans_probability=score / len(src), p=p)
+    out = dict(result=result, iterations=run["iterations"], derivative_calls=run["derivative_calls"],
+               trans_probability=run["score"] / len(src), p=run["p"])
     if with_fitness:                                                                 # pcl::Registration::getFitnessScore, ndt.cc:60
         t = transform_cloud_f32(src, final)
         dist, _ = cKDTree(tgt.astype(np.float64)).query(t.astype(np.float64))

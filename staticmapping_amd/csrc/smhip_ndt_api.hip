@@ -623,6 +623,26 @@ smhip_status smhip_ndt_time_derivatives(smhip_handle h, int first_slot, int npai
   return SMHIP_OK;
 }
 
+// parity-test hook: n 6x6 systems (row-major H, b) through ndt_solve6 on the device, a lane per system
+smhip_status smhip_ndt_debug_solve6(smhip_handle h, int n, const double* H, const double* b, double* x) {
+  if (!h || !H || !b || !x || n < 1 || n > (1 << 20)) return SMHIP_ERR_INVALID_ARGUMENT;
+  HIPCHK(h, hipSetDevice(h->device));
+  double* dev = nullptr;                                       // H | b | x
+  HIPCHK(h, hipMalloc(&dev, sizeof(double) * 48 * (size_t)n));
+  double* dH = dev; double* db = dev + 36 * (size_t)n; double* dx = db + 6 * (size_t)n;
+  hipError_t e = hipMemcpyAsync(dH, H, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ndt_debug_solve6, dim3(ceil_div(n, 64)), dim3(64), 0, h->stream, n, dH, db, dx);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(x, dx, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(dev);
+  HIPCHK(h, e);
+  return SMHIP_OK;
+}
+
 // tuning hook (not in smhip.h): the rows of partial sums the last evaluation of slot 0 left, as raw 8-byte words
 smhip_status smhip_ndt_debug_rows(smhip_handle h, unsigned long long* out, int max_rows, int* rows) {
   if (!h || !out || !rows) return SMHIP_ERR_INVALID_ARGUMENT;

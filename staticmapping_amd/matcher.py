@@ -435,6 +435,16 @@ class NdtHip(IcpFastHip):
                                                                H.ctypes.data_as(_capi.c_double_p), ctypes.byref(pairs)))
         return score.value, g, H.reshape(6, 6), int(pairs.value)
 
+    def debug_solve6(self, H, b):
+        """The Newton solve of the serial end on the device (smhip_ndt_debug_solve6): H [n, 6, 6], b [n, 6] -> x [n, 6]."""
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 36)
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 6)
+        assert len(H) == len(b)
+        x = np.zeros((len(H), 6))
+        self._check(self._lib.smhip_ndt_debug_solve6(self._h, len(H), H.ctypes.data_as(_capi.c_double_p), b.ctypes.data_as(_capi.c_double_p),
+                                                     x.ctypes.data_as(_capi.c_double_p)))
+        return x
+
     def time_derivatives(self, npairs: int = 1, launches: int = 20, first_slot: int = 0):
         """HIP-event time of back-to-back computeDerivatives launches over the slots' last poses (smhip_ndt_time_derivatives):
         (ms per launch, (point, voxel) pairs per launch)."""
