@@ -990,7 +990,8 @@ __device__ __forceinline__ void sweep_run(const float4* __restrict__ tq, uint32_
 // launch would otherwise have too few workgroups to fill the GPU (single pairs: 118 -> 469 workgroups for 120 k points).
 // Diagnostic, compiled out by default (hipcc -DSMHIP_PHASE_TIMING=1, then run with SMHIP_DEBUG_FLAGS=16): per-wave s_memtime
 // deltas per phase of a round, summed into 8 u64 counters that live in the (idle during the iterations) tpart scratch of
-// slot 0; finalize prints their shares and clears them.  What it showed (64 pairs, iterations 1-4, nearly every query
+// slot 0 (phase_counter); finalize prints their shares and clears them (tools/phase_timing.py; tpart is not cleared when it is
+// allocated, so a handle's first Align may print leftovers for iteration 0: the tool aligns twice).  What it showed (64 pairs, iterations 1-4, nearly every query
 // searching): prologue + prefetch 13 %, phase C + compaction 13 %, wait at barrier A 9 %, search-lane setup + box 12 %,
 // staging between barriers B and C 22 %, the search itself 20 %, stores 5 %, histogram flush 6 % -- no phase dominates.
 #ifndef SMHIP_PHASE_TIMING
@@ -998,11 +999,26 @@ __device__ __forceinline__ void sweep_run(const float4* __restrict__ tq, uint32_
 #endif
 #if SMHIP_PHASE_TIMING
 #define SMHIP_PHASE(k) do { if (timing) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[k] += now_ - tprev; tprev = now_; } } while (0)
+// counter k of the 14: tgt_reduce writes doubles 0..8 of each 16-double row of tpart at the start of an Align, so the counters take
+// doubles 9..15 of slot 0's first two rows (nobody else touches them: iteration 0 starts from the zeros finalize left)
+__device__ __forceinline__ unsigned long long* phase_counter(const IcpDev& b, int k) {
+  return reinterpret_cast<unsigned long long*>(b.tpart) + (k / 7) * 16 + 9 + (k % 7);
+}
 #else
 #define SMHIP_PHASE(k) do { } while (0)
 #endif
+// Per-path counts, same build and flag: the search rounds that ran with row tables and points staged / row tables only / global
+// lookups (counters 8, 10, 12) and the cycles their waves spent in them (9, 11, 13), reported by finalize on the same line.
 // FIRST = the launch of iteration 0 (the host knows): no previous match, no certificate, one radius for every query -- the loads,
-// the gather of the previous match and the certificate arithmetic drop out at compile time.
+// the gather of the previous match and the certificate arithmetic drop out at compile time.  Every finite query searches there, so
+// nothing is compacted: a lane searches the query it holds (a result does not depend on the lane that computes it) -- no search list
+// in LDS (5.5 KiB), no ballot / LDS atomic / write / barrier / read-back per round: four barriers a round, 21.2 KiB of LDS.
+// The other instantiations run the certificates of ALL the workgroup's rounds first and append the failing queries to ONE list
+// (18 bytes an entry: position, squared radius, 16-bit index from base0; the seed a search that finds nothing keeps is read again
+// from idx), then search the list in rounds of up to 256 entries -- one box, one staging, four barriers each.  Where less than half of
+// a workgroup's queries fail (iteration 1 of a well-guessed batch: about a third) that is one search round for its two rounds of
+// queries, with full waves instead of two half-empty rounds; where nothing fails, none.  30.2 KiB of LDS at ITEMS = 2 (five
+// workgroups per CU need <= 32 KiB: ITEMS = 4 would take 39.2 KiB).
 // The rounds of one workgroup: ITEMS rounds of 256 queries from source index base0 on.  `st` is the pair's state in global memory
 // (the counters the rounds add to); `ls` is where the rounds READ the pair's pose-dependent state from -- the same object for the
 // kernel below, the workgroup's own LDS copy for the single-pair persistent kernel (icp_one.hip), whose iterations never
@@ -1017,21 +1033,28 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
   const float Mtx = (float)Mc[3], Mty = (float)Mc[7], Mtz = (float)Mc[11];
 #if SMHIP_PHASE_TIMING
   const bool timing = (b.debug_flags & 16) != 0;
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long tacc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 8 phases, then rounds and cycles of the three paths
   unsigned long long tprev = timing ? __builtin_readcyclecounter() : 0ull;
 #endif
   __shared__ uint32_t s_tab[kLdsTableCap];
   __shared__ float4 s_pts[kLdsPointCap];
   __shared__ uint32_t s_roff[kLdsRowCap + 1];
   __shared__ uint32_t s_occ[kLdsRowCap / 32 + 1];   // bit r = staged row r of the box holds target points (+ one word so that two can always be read)
-  __shared__ float4 s_q[kNnThreads];          // queries of the round that need a search: x, y, z, previous match
-  __shared__ float s_r2[kNnThreads];          // their squared search radius
-  __shared__ uint16_t s_lid[kNnThreads];      // their lane in the round
-  __shared__ uint32_t s_nsearch[2];
   __shared__ uint32_t s_w[17];
   __shared__ int s_box[2][6];
+  // the queries of the workgroup's ITEMS rounds that need a search, in one list (not in iteration 0: every finite query searches there,
+  // with one radius, on the lane that holds it -- the instantiation has no list and no barrier behind it)
+  float4* s_e = nullptr;                      // x, y, z, squared search radius
+  uint16_t* s_slot = nullptr;                 // the query's index from base0 (where its result goes)
+  uint32_t* s_nsearch = nullptr;
+  if constexpr (!FIRST) {
+    __shared__ float4 s_e_[ITEMS * kNnThreads];
+    __shared__ uint16_t s_slot_[ITEMS * kNnThreads];
+    __shared__ uint32_t s_nsearch_;
+    s_e = s_e_; s_slot = s_slot_; s_nsearch = &s_nsearch_;
+    if (threadIdx.x == 6) s_nsearch_ = 0;
+  }
   if (threadIdx.x < 6) { s_box[0][threadIdx.x] = threadIdx.x < 3 ? 0x3fffffff : -0x3fffffff; s_box[1][threadIdx.x] = s_box[0][threadIdx.x]; }
-  if (threadIdx.x < 2) s_nsearch[threadIdx.x] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const size_t so = (size_t)pair * b.ns_cap;
@@ -1056,12 +1079,12 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
     if (have_prev) { jp_cur = b.idx[so + i]; if (certify) l_cur = ld_lb(b, so + i); }
   }
 
-  for (int it = 0; it < ITEMS; ++it) {
+  // ---- round `it` of the workgroup, every lane: its query, and (not in iteration 0) the previous match and the certificate; the
+  // queries that need a search are appended to the workgroup's list.  False when the round lies behind the pair's points.
+  auto query_round = [&](const int it, float& qx, float& qy, float& qz, bool& valid) -> bool {
     const int base = base0 + it * kNnThreads;
-    if (base >= ns) break;                               // block-uniform
+    if (base >= ns) return false;                        // block-uniform
     i = base + threadIdx.x;
-    int* box = s_box[it & 1];
-    uint32_t* nsearch = &s_nsearch[it & 1];
     // prefetch level 1 of the next round
     const int i_next = i + kNnThreads;
     float4 s_next = make_float4(0, 0, 0, 0);
@@ -1073,8 +1096,8 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
     }
     SMHIP_PHASE(0);      // prologue / prefetch issue
     // ---- phase C (every lane): query, previous match, certificate
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    bool valid = false;
+    qx = 0.f; qy = 0.f; qz = 0.f;
+    valid = false;
     if (i < ns) {
       double px, py, pz;
       transform_point(Mc, s_cur, px, py, pz);
@@ -1111,18 +1134,18 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
         }
       }
     }
-    // compact the lanes that need a search into s_q (wave-aggregated, order-preserving inside a wave)
-    {
+    // append the lanes that need a search to the workgroup's list (wave-aggregated, order-preserving inside a wave).  An entry is
+    // 18 bytes: the seed a search that finds nothing keeps is the previous match, which that lane reads again from idx.
+    if constexpr (!FIRST) {
       const unsigned long long sm = __ballot(need_search);
       if (sm) {
         uint32_t basepos = 0;
-        if (lane == 0) basepos = atomicAdd(nsearch, (uint32_t)__popcll(sm));
+        if (lane == 0) basepos = atomicAdd(s_nsearch, (uint32_t)__popcll(sm));
         basepos = (uint32_t)__builtin_amdgcn_readlane((int)basepos, 0);   // lane 0 did the atomic
         if (need_search) {
           const uint32_t pos = basepos + __popcll(sm & ((1ull << lane) - 1ull));
-          s_q[pos] = make_float4(qx, qy, qz, __int_as_float(jp_cur));
-          s_r2[pos] = has_jp ? search_radius2(r2cap, dub2, search_margin(delta)) : r2cap;
-          s_lid[pos] = (uint16_t)threadIdx.x;
+          s_e[pos] = make_float4(qx, qy, qz, has_jp ? search_radius2(r2cap, dub2, search_margin(delta)) : r2cap);
+          s_slot[pos] = (uint16_t)(it * kNnThreads + (int)threadIdx.x);
         }
       }
     }
@@ -1135,21 +1158,17 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
         if (hard) b.hlist[so + basepos + __popcll(hm & ((1ull << lane) - 1ull))] = i;
       }
     }
+    s_cur = s_next; jp_cur = jp_next; l_cur = l_next;
     SMHIP_PHASE(1);      // phase C + compaction
-    __syncthreads();                                      // (A) search list complete
-    SMHIP_PHASE(2);      // wait at barrier A
-    const int nq = (int)*nsearch;
-    if (threadIdx.x == 0 && nq) atomicAdd(&st->deferred_count, (uint32_t)nq);     // statistics only
-    // ---- phase S: the first nq threads own one searching query each
-    const bool mine = (int)threadIdx.x < nq;
-    float R2 = 0.f;
-    int jseed = -1, gi = -1;
-    if (mine) {
-      const float4 q4 = s_q[threadIdx.x];
-      qx = q4.x; qy = q4.y; qz = q4.z; jseed = __float_as_int(q4.w);
-      R2 = s_r2[threadIdx.x];
-      gi = base + (int)s_lid[threadIdx.x];
-    }
+    return true;
+  };
+  // ---- search round `sr` of the workgroup: the lanes with `mine` own one searching query each (position, squared radius, source
+  // index gi); wave_live = the lane's wave holds such a lane.  One box, one staging, five barriers -- every thread of the workgroup calls it.
+  auto search_round = [&](const int sr, const bool mine, const bool wave_live, const float qx, const float qy, const float qz, const float R2, const int gi) {
+    int* box = s_box[sr & 1];
+#if SMHIP_PHASE_TIMING
+    const unsigned long long tround = timing ? __builtin_readcyclecounter() : 0ull;
+#endif
     int x0 = 1, x1 = 0, y0 = 1, y1 = 0, z0 = 1, z1 = 0;
     if (mine) {
       const float Rs = __builtin_amdgcn_sqrtf(R2) * 1.0001f + 1.0e-3f * h;
@@ -1158,7 +1177,7 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
       z0 = max(cell_coord(qz - Rs, oz, inv_h), 0); z1 = min(cell_coord(qz + Rs, oz, inv_h), nz - 1);
     }
     const bool inbox = mine && x0 <= x1 && y0 <= y1 && z0 <= z1;
-    if ((int)(threadIdx.x & ~63) < nq) {                  // waves that hold searching queries
+    if (wave_live) {                                      // waves that hold searching queries
       const int big = 0x3fffffff;
       const int mx0 = wave_min_i(inbox ? x0 : big), mx1 = wave_max_i(inbox ? x1 : -big);
       const int my0 = wave_min_i(inbox ? y0 : big), my1 = wave_max_i(inbox ? y1 : -big);
@@ -1192,8 +1211,7 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
       }
     }
     // reset the other round's scratch while nobody reads it
-    if (threadIdx.x < 6) s_box[(it + 1) & 1][threadIdx.x] = threadIdx.x < 3 ? 0x3fffffff : -0x3fffffff;
-    if (threadIdx.x == 6) s_nsearch[(it + 1) & 1] = 0;
+    if (threadIdx.x < 6) s_box[(sr + 1) & 1][threadIdx.x] = threadIdx.x < 3 ? 0x3fffffff : -0x3fffffff;
     // stage the box's target points: every grid row of the box is ONE contiguous run of tq
     const int rows = use_lds ? nyl * nzl : 0;
     bool pts_lds = use_lds && rows <= kLdsRowCap;
@@ -1278,7 +1296,7 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
         lbout = __builtin_amdgcn_sqrtf(fminf(best.s2, R2));  // every other point is at least this far
       } else {                              // certified lower bound
         d2out = R2;
-        jout = best.j >= 0 ? best.j : jseed;
+        jout = best.j >= 0 ? best.j : (have_prev ? b.idx[so + gi] : -1);      // the seed: the previous match (this lane writes it below)
         lbout = -__builtin_amdgcn_sqrtf(R2);
         hard2 = true;
         min_lb = min(min_lb, __float_as_uint(R2));
@@ -1302,13 +1320,53 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
         if (hard2) b.hlist[so + basepos + __popcll(hm & ((1ull << lane) - 1ull))] = gi;
       }
     }
-    s_cur = s_next; jp_cur = jp_next; l_cur = l_next;
     SMHIP_PHASE(6);      // stores + hard list
+#if SMHIP_PHASE_TIMING
+    if (timing) {        // which path the round took: its count (by the workgroup's first wave) and every wave's cycles in it
+      const unsigned long long dt = __builtin_readcyclecounter() - tround, one = threadIdx.x < 64 ? 1ull : 0ull;
+      if (pts_lds) { tacc[8] += one; tacc[9] += dt; }             // row tables and points staged
+      else if (use_lds) { tacc[10] += one; tacc[11] += dt; }      // row tables only
+      else { tacc[12] += one; tacc[13] += dt; }                   // global lookups
+    }
+#endif
+  };
+  if constexpr (FIRST) {
+    // iteration 0: a lane searches the query it holds (a query's result does not depend on the lane that runs it)
+    uint32_t nvalid = 0;                                  // wave-uniform
+    for (int it = 0; it < ITEMS; ++it) {
+      float qx, qy, qz;
+      bool valid;
+      if (!query_round(it, qx, qy, qz, valid)) break;
+      const unsigned long long vm = __ballot(valid);
+      nvalid += (uint32_t)__popcll(vm);
+      SMHIP_PHASE(2);
+      search_round(it, valid, vm != 0ull, qx, qy, qz, r2cap, base0 + it * kNnThreads + (int)threadIdx.x);
+    }
+    if (lane == 0 && nvalid) atomicAdd(&st->deferred_count, nvalid);              // statistics only
+  } else {
+    // later iterations: the certificates of all the workgroup's rounds first, then the failing queries together in rounds of 256 list
+    // entries -- where fewer than half fail that is one box, one staging and one set of barriers instead of ITEMS
+    for (int it = 0; it < ITEMS; ++it) {
+      float qx, qy, qz;
+      bool valid;
+      if (!query_round(it, qx, qy, qz, valid)) break;
+    }
+    __syncthreads();                                      // (A) search list complete
+    SMHIP_PHASE(2);      // wait at barrier A
+    const int nq = (int)*s_nsearch;
+    if (threadIdx.x == 0 && nq) atomicAdd(&st->deferred_count, (uint32_t)nq);     // statistics only
+    for (int sr = 0, e0 = 0; e0 < nq; ++sr, e0 += kNnThreads) {
+      const int e = e0 + (int)threadIdx.x;
+      const bool mine = e < nq;
+      float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      int gi = -1;
+      if (mine) { q4 = s_e[e]; gi = base0 + (int)s_slot[e]; }
+      search_round(sr, mine, (e & ~63) < nq, q4.x, q4.y, q4.z, q4.w, gi);
+    }
   }
 #if SMHIP_PHASE_TIMING
   if (timing && lane == 0) {
-    unsigned long long* tc = reinterpret_cast<unsigned long long*>(b.tpart);
-    for (int k = 0; k < 8; ++k) atomicAdd(&tc[k], tacc[k]);
+    for (int k = 0; k < 14; ++k) atomicAdd(phase_counter(b, k), tacc[k]);
   }
 #endif
 }
@@ -3492,12 +3550,17 @@ __device__ __forceinline__ void finalize_body(const IcpDev& b) {
   if (st->done) return;
 #if SMHIP_PHASE_TIMING
   if ((b.debug_flags & 16) && pair == 0 && threadIdx.x == 0) {            // phase timing report (diagnostic build only)
-    unsigned long long* tc = reinterpret_cast<unsigned long long*>(b.tpart);
+    unsigned long long tc[14];
+    for (int k = 0; k < 14; ++k) { tc[k] = *phase_counter(b, k); *phase_counter(b, k) = 0; }
     unsigned long long tot = 0;
     for (int k = 0; k < 8; ++k) tot += tc[k];
     printf("[phase] iter %d total %llu :", st->iter, tot);
-    for (int k = 0; k < 8; ++k) { printf(" %.1f%%", tot ? 100.0 * (double)tc[k] / (double)tot : 0.0); tc[k] = 0; }
-    printf("\n");
+    for (int k = 0; k < 8; ++k) printf(" %.1f%%", tot ? 100.0 * (double)tc[k] / (double)tot : 0.0);
+    // the search rounds by the path they took (points staged / row tables only / global lookups): their number and their cycles
+    const unsigned long long ptot = tc[9] + tc[11] + tc[13];
+    printf(" | search rounds: staged %llu (%.1f%% of their cycles), table only %llu (%.1f%%), global %llu (%.1f%%); rounds' share of all cycles %.1f%%\n",
+           tc[8], ptot ? 100.0 * (double)tc[9] / (double)ptot : 0.0, tc[10], ptot ? 100.0 * (double)tc[11] / (double)ptot : 0.0,
+           tc[12], ptot ? 100.0 * (double)tc[13] / (double)ptot : 0.0, tot ? 100.0 * (double)ptot / (double)tot : 0.0);
   }
 #endif
   __shared__ uint32_t s_w[17];

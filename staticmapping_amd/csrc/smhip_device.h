@@ -36,7 +36,8 @@ constexpr int kNaboAccBlocks = 8;         // workgroups per pair of accumulate_l
 constexpr int kListedMaxPairs = 1024;   // pairs per launch of the balanced listed search (nn_ball_listed_items: its plan sits in LDS)
 constexpr int kListedItemBlocks = 1280;  // its workgroups: 5 per CU (LDS), each takes an equal run of the launch's items
 constexpr int kListedBlocks = 32;        // workgroups per pair of the listed search (nn_ball_listed): it strides over the list
-constexpr int kBallItems = 2;            // rounds of 256 queries per workgroup in nn_ball_lds / nn_ball (prefetch across rounds; 2 measured best: 4 = +8 %, 1 = +5 %)
+constexpr int kBallItems = 2;            // rounds of 256 queries per workgroup in nn_ball_lds / nn_ball (prefetch across rounds; 2 measured best: 4 = +8 %, 1 = +5 %;
+                                         // nn_ball_lds's list of failing queries holds kBallItems * 256 entries of 18 bytes: 4 would take the workgroup past 32 KiB of LDS)
 constexpr int kListedLaneBudgetMax = 32768;   // largest lane budget of the balanced listed search (SMHIP_LISTED_LANES; default 1024, sync_options)
 constexpr int kFusedListedMax = 16384;   // fused path: with more failing certificates than this in a pair and iteration the sums are left to `accumulate`
                                          // (their listed matches below the band are summed kListedSumChunk entries per work item of iteration_sums,
