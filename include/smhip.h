@@ -424,6 +424,15 @@ smhip_status smhip_ndt_compute_derivatives_ex(smhip_handle h, const double pose6
 /* the Newton solve of an Align's serial end (JacobiSVD(H).solve(b), ndt_omp_impl.hpp:127-129) as the device computes it, a lane
  * per system: H holds n row-major 6x6 matrices, b and x n 6-vectors.  Needs no cloud and no voxel table. */
 smhip_status smhip_ndt_debug_solve6(smhip_handle h, int n, const double* H, const double* b, double* x);
+/* parity-test hook: the fitness search of slots first_slot .. + npairs - 1 at the given poses (npairs column-major 4x4), through the
+ * production path (the same launches as getFitnessScore).  d2 / stage: [npairs][capacity], row k = slot first_slot + k, entries in the
+ * order the device holds the source (smhip_get_source_f32); entries past a slot's ns are left alone.  d2 = squared distance to the
+ * nearest target point as the search found it (+inf for a query that is not finite); stage = the pass that settled the query:
+ * 0 fine cube, 1 mid shells, 2 sweep over the voxel boxes, -1 where d2 is +inf.  scores[k] = the score the same pass reports.
+ * SMHIP_ERR_NOT_READY before a slot's source and target are set; SMHIP_ERR_CAPACITY (nothing written) when capacity is below a
+ * slot's source size. */
+smhip_status smhip_ndt_debug_fitness(smhip_handle h, int first_slot, int npairs, const double* poses, int capacity,
+                                     float* d2, int32_t* stage, double* scores);
 /* measurement hook: `launches` back-to-back computeDerivatives launches (with Hessian) over slots first_slot .. + npairs - 1 at the
  * poses their last Align ended with, HIP events around them on the handle's stream: *ms_per_launch = the average duration of
  * the kernel, *pairs_per_launch = the (point, voxel) pairs one launch works through (for its algorithmic bytes).  The slots'

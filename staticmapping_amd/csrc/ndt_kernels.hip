@@ -158,8 +158,15 @@ __device__ __forceinline__ bool ndt_voxel_of(const NdtGridInfo* g, float x, floa
 }
 // the fine coordinate of a point inside its voxel: floor(16 frac(p * inv)) per axis -- exact float operations on the one rounded
 // product; its upper two bits are the mid cell's coordinate, the lower two the fine cell's inside the mid cell
+// (the product rounded on its own: contracted into the subtraction below, a * b - floor sees the unrounded product, and a point
+// whose product rounds onto a wall lands on either side of it, as each kernel happens to be compiled -- the sort keys of
+// ndt_voxel_keys64 named one mid cell and the hash key of ndt_voxel_heads the next, so a cell's entry stood under its neighbour's key)
+__device__ __forceinline__ float ndt_mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 __device__ __forceinline__ int ndt_fine_axis(float p, float inv) {
-  const float ps = p * inv;
+  const float ps = ndt_mul_rounded(p, inv);
   return min(15, (int)((ps - floorf(ps)) * 16.0f));
 }
 __device__ __forceinline__ uint32_t ndt_voxel_code(const NdtGridInfo* g, const float4 p) {     // word << 5 | bit, or ~0
@@ -1173,7 +1180,7 @@ __device__ __forceinline__ NdtQuery ndt_fit_query(const NdtDev& d, const PairInp
   q.finite = q.finite && isfinite(q.t[0]) && isfinite(q.t[1]) && isfinite(q.t[2]);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float ps = q.t[c] * g->inv, fl = floorf(ps);
+    const float ps = ndt_mul_rounded(q.t[c], g->inv), fl = floorf(ps);          // (rounded on its own, as ndt_fine_axis)
     // (clamped far outside the box: every voxel test fails there anyway, and the int arithmetic stays in range)
     q.iv[c] = (int)fminf(fmaxf(fl - (float)g->min_b[c], -1.0e6f), 1.0e6f);
     q.f[c] = ps - fl;

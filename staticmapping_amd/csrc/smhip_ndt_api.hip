@@ -643,6 +643,50 @@ smhip_status smhip_ndt_debug_solve6(smhip_handle h, int n, const double* H, cons
   return SMHIP_OK;
 }
 
+// parity-test hook: fitness_scores() as it stands, then what its launches left behind -- every query's distance, and the two
+// hand-over lists, from which the pass that settled a query follows (the kernels record nothing for this call)
+smhip_status smhip_ndt_debug_fitness(smhip_handle h, int first_slot, int npairs, const double* poses, int capacity, float* d2, int32_t* stage,
+                                     double* scores) {
+  if (!h || !poses || !d2 || !stage || !scores || npairs < 1 || first_slot < 0 || first_slot + npairs > h->dev.slots || capacity < 0) {
+    if (h) h->err = "bad slot range / poses / outputs";
+    return SMHIP_ERR_INVALID_ARGUMENT;
+  }
+  for (int k = first_slot; k < first_slot + npairs; ++k) {
+    if (h->ns[k] <= 0 || h->nt[k] <= 0) { h->err = "fitness score before SetInputSource/SetInputTarget"; return SMHIP_ERR_NOT_READY; }
+    if (capacity < h->ns[k]) { h->err = "capacity too small"; return SMHIP_ERR_CAPACITY; }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> sc(npairs);
+  smhip_status s = fitness_scores(h, first_slot, npairs, poses, sc.data());
+  if (s) return s;
+  NdtHost& n = ndt_of(h);
+  std::vector<NdtGridInfo> info(npairs);
+  HIPCHK(h, hipMemcpyAsync(info.data(), n.info_all + first_slot, sizeof(NdtGridInfo) * npairs, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::vector<uint32_t> list;
+  for (int k = 0; k < npairs; ++k) {
+    const NdtDev& d = n.devs_host[first_slot + k];
+    const size_t ns = (size_t)h->ns[first_slot + k];
+    const NdtGridInfo& g = info[k];
+    if (g.nlist > ns || g.nleft > g.nlist) { h->err = "fitness search: a hand-over list is longer than what could enter it"; return SMHIP_ERR_HIP; }
+    float* dk = d2 + (size_t)k * capacity;
+    int32_t* sk = stage + (size_t)k * capacity;
+    list.resize((size_t)g.nlist + g.nleft + 1);
+    HIPCHK(h, hipMemcpyAsync(dk, d.fit_d2, sizeof(float) * ns, hipMemcpyDeviceToHost, h->stream));
+    if (g.nlist) HIPCHK(h, hipMemcpyAsync(list.data(), d.qlist, sizeof(uint32_t) * g.nlist, hipMemcpyDeviceToHost, h->stream));
+    if (g.nleft) HIPCHK(h, hipMemcpyAsync(list.data() + g.nlist, d.qleft, sizeof(uint32_t) * g.nleft, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < ns; ++i) sk[i] = 0;
+    for (uint32_t q = 0; q < g.nlist + g.nleft; ++q) {
+      if (list[q] >= ns) { h->err = "fitness search: a hand-over list names a query the slot does not have"; return SMHIP_ERR_HIP; }
+      sk[list[q]] = q < g.nlist ? 1 : 2;
+    }
+    for (size_t i = 0; i < ns; ++i) if (!(dk[i] < INFINITY)) sk[i] = -1;
+    scores[k] = sc[k];
+  }
+  return SMHIP_OK;
+}
+
 // tuning hook (not in smhip.h): the rows of partial sums the last evaluation of slot 0 left, as raw 8-byte words
 smhip_status smhip_ndt_debug_rows(smhip_handle h, unsigned long long* out, int max_rows, int* rows) {
   if (!h || !out || !rows) return SMHIP_ERR_INVALID_ARGUMENT;

@@ -445,6 +445,25 @@ class NdtHip(IcpFastHip):
                                                      x.ctypes.data_as(_capi.c_double_p)))
         return x
 
+    def debug_fitness(self, poses, first_slot: int = 0):
+        """The fitness search of slots first_slot .. + len(poses) - 1 at the given 4x4 poses, through getFitnessScore's own launches
+        (smhip_ndt_debug_fitness).  Per slot: (d2 float32 [ns], stage int32 [ns], score) -- the squared distance of every query to
+        its nearest target point (+inf for a row that is not finite), the pass that settled it (0 fine cube, 1 mid shells, 2 sweep
+        over the voxel boxes, -1 where d2 is +inf) and the score of the same pass; rows in the order of get_source(slot)."""
+        npairs = len(poses)
+        g = self._pack_guesses(npairs, poses)
+        ns = []
+        for k in range(npairs):
+            n = ctypes.c_int32()
+            self._check(self._lib.smhip_get_cloud_sizes(self._h, first_slot + k, ctypes.byref(n), None, None))
+            ns.append(n.value)
+        cap = max(ns + [1])
+        d2 = np.zeros((npairs, cap), np.float32); stage = np.zeros((npairs, cap), np.int32); scores = np.zeros(npairs)
+        self._check(self._lib.smhip_ndt_debug_fitness(self._h, first_slot, npairs, g.ctypes.data_as(_capi.c_double_p), cap,
+                                                      d2.ctypes.data_as(_capi.c_float_p), stage.ctypes.data_as(_capi.c_int32_p),
+                                                      scores.ctypes.data_as(_capi.c_double_p)))
+        return [(d2[k, :ns[k]].copy(), stage[k, :ns[k]].copy(), float(scores[k])) for k in range(npairs)]
+
     def time_derivatives(self, npairs: int = 1, launches: int = 20, first_slot: int = 0):
         """HIP-event time of back-to-back computeDerivatives launches over the slots' last poses (smhip_ndt_time_derivatives):
         (ms per launch, (point, voxel) pairs per launch)."""
