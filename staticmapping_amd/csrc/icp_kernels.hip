@@ -986,6 +986,74 @@ __device__ __forceinline__ void sweep_run(const float4* __restrict__ tq, uint32_
   for (; j < j1; ++j) test_ascending_ru(tq[j], (int)j, qx, qy, qz, best);
 }
 
+// The rows (z, y) of one query's block [x0, x1] x [y0, y1] x [z0, z1] with every lookup from global memory -- the rounds of
+// ball_lds_rounds whose box misses the table cap (a third of the bench batch's search rounds: sparse, far-range queries with ~8 rows
+// a ball of which ~2 hold a cell in range, ~6 candidates, and three in ten queries none at all).  A row at a time that walk is a chain
+// of dependent loads per row (words -> cstart -> tq) in a kernel whose waves wait 80 % of the time: ~28 dependent levels a wave and
+// round.  Here a lane takes its rows FOUR at a time and issues their lookups level by level: the four rows' words, then the run bounds
+// of the rows with a cell in range, then the four runs' points as ONE sequence, four loads in flight across the runs' ends (a batch
+// holds ~3 candidates: one level, where a sweep per run is one level per occupied row).
+// This is the scheme of listed_search_one, restated and not shared: there one query's rows go round L lanes and every lookup is issued
+// unmasked from a clamped row; here each lookup is predicated (a row past the last, a row outside the ball, a row with no cell in
+// range and an empty batch issue nothing, so nothing is read at an address made from a masked row), the second word is only read where
+// x0 and x1 lie in different words, the rows are counted up in (z, y) and not decoded from an index (any row count), and there is no
+// level of first points (measured: with it iteration 0's instantiation needs 88 VGPRs or scratch, and is slower than the walk it
+// replaces; two rows at a time with it, and skipping the rows outside the ball without giving them a slot, are slower than this).
+// The tests keep the walk's order -- rows ascending in (z, y), a run's points ascending -- so Best's tie rule, the runner-up and the
+// seed are bit for bit those of the row-at-a-time walk (nn_ball's, which the tests compare with).
+// position in the sorted target of candidate c of a batch's four runs laid end to end: run k ends at e_k, c + o_k lies in run k
+__device__ __forceinline__ uint32_t run_pos(uint32_t c, uint32_t e0, uint32_t e1, uint32_t e2, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) {
+  return c + (c < e0 ? o0 : c < e1 ? o1 : c < e2 ? o2 : o3);
+}
+// (the caller has checked x0 <= x1, y0 <= y1 and z0 <= z1: with y0 > y1 the row counter below would never leave the first slab)
+__device__ __forceinline__ void sweep_rows_global(const uint2* __restrict__ words, const uint32_t* __restrict__ cstart, const float4* __restrict__ tq,
+                                                  int ny, int wx, float oy, float oz, float h, float slack, int x0, int x1, int y0, int y1, int z0, int z1,
+                                                  float qx, float qy, float qz, float R2, Best& best) {
+  const int wa_i = x0 >> 5, wc_i = x1 >> 5;
+  const bool two = wa_i != wc_i;
+  const uint32_t ma = (1u << (x0 & 31)) - 1u, mc = 0xffffffffu >> (31 - (x1 & 31));
+  int y = y0, z = z0;
+  while (z <= z1) {
+    uint2 wa[4], wc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float zl = oz + (float)z * h, yl = oy + (float)y * h;
+      const float dz = fmaxf(fmaxf(zl - qz, qz - (zl + h)) - slack, 0.f);
+      const float dy = fmaxf(fmaxf(yl - qy, qy - (yl + h)) - slack, 0.f);
+      wa[k] = make_uint2(0u, 0u); wc[k] = make_uint2(0u, 0u);     // (a row past the last / outside the ball: words without a cell)
+      if (z <= z1 && !(fmaf(dy, dy, dz * dz) > R2)) {
+        const int rowbase = (z * ny + y) * wx;
+        wa[k] = words[rowbase + wa_i];
+        if (two) wc[k] = words[rowbase + wc_i];
+      }
+      if (++y > y1) { y = y0; ++z; }
+    }
+    uint32_t j0[4], j1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint2 c = two ? wc[k] : wa[k];
+      const uint32_t sb = wa[k].y + __popc(wa[k].x & ma), se = c.y + __popc(c.x & mc);
+      j0[k] = 0u; j1[k] = 0u;                                 // (no cell of the row in range: an empty run)
+      if (se > sb) { j0[k] = cstart[sb]; j1[k] = cstart[se]; }
+    }
+    // candidate c of the batch's sequence is position c + o_k of the sorted target for the first run k with c < e_k (passed by value:
+    // arrays indexed in a loop, or a lambda capturing them by reference that the compiler does not inline, put them in scratch)
+    const uint32_t e0 = j1[0] - j0[0], e1 = e0 + (j1[1] - j0[1]), e2 = e1 + (j1[2] - j0[2]), tot = e2 + (j1[3] - j0[3]);
+    const uint32_t o0 = j0[0], o1 = j0[1] - e0, o2 = j0[2] - e1, o3 = j0[3] - e2;
+    for (uint32_t c = 0u; c < tot; c += 4) {
+      const uint32_t e = tot - 1u;
+      const uint32_t cb = min(c + 1u, e), cc = min(c + 2u, e), cd = min(c + 3u, e);
+      const uint32_t ja = run_pos(c, e0, e1, e2, o0, o1, o2, o3), jb = run_pos(cb, e0, e1, e2, o0, o1, o2, o3);
+      const uint32_t jc = run_pos(cc, e0, e1, e2, o0, o1, o2, o3), jd = run_pos(cd, e0, e1, e2, o0, o1, o2, o3);
+      const float4 a0 = tq[ja], a1 = tq[jb], a2 = tq[jc], a3 = tq[jd];
+      test_ascending_ru(a0, (int)ja, qx, qy, qz, best);
+      if (c + 1u <= e) test_ascending_ru(a1, (int)jb, qx, qy, qz, best);
+      if (c + 2u <= e) test_ascending_ru(a2, (int)jc, qx, qy, qz, best);
+      if (c + 3u <= e) test_ascending_ru(a3, (int)jd, qx, qy, qz, best);
+    }
+  }
+}
+
 // ITEMS = rounds of 256 queries per workgroup: 4 for batches (fewer histogram flushes, prefetch across rounds), 1 when a
 // launch would otherwise have too few workgroups to fill the GPU (single pairs: 118 -> 469 workgroups for 120 k points).
 // Diagnostic, compiled out by default (hipcc -DSMHIP_PHASE_TIMING=1, then run with SMHIP_DEBUG_FLAGS=16): per-wave s_memtime
@@ -1012,7 +1080,8 @@ __device__ __forceinline__ unsigned long long* phase_counter(const IcpDev& b, in
 // FIRST = the launch of iteration 0 (the host knows): no previous match, no certificate, one radius for every query -- the loads,
 // the gather of the previous match and the certificate arithmetic drop out at compile time.  Every finite query searches there, so
 // nothing is compacted: a lane searches the query it holds (a result does not depend on the lane that computes it) -- no search list
-// in LDS (5.5 KiB), no ballot / LDS atomic / write / barrier / read-back per round: four barriers a round, 21.2 KiB of LDS.
+// in LDS (5.5 KiB), no ballot / LDS atomic / write / barrier / read-back per round: four barriers a round; the LDS
+// goes to a larger s_pts (kLdsPointCapFirst: every table-only round of the bench batch misses the point cap, none the row cap): 25.2 KiB.
 // The other instantiations run the certificates of ALL the workgroup's rounds first and append the failing queries to ONE list
 // (18 bytes an entry: position, squared radius, 16-bit index from base0; the seed a search that finds nothing keeps is read again
 // from idx), then search the list in rounds of up to 256 entries -- one box, one staging, four barriers each.  Where less than half of
@@ -1037,7 +1106,8 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
   unsigned long long tprev = timing ? __builtin_readcyclecounter() : 0ull;
 #endif
   __shared__ uint32_t s_tab[kLdsTableCap];
-  __shared__ float4 s_pts[kLdsPointCap];
+  constexpr int kPointCap = FIRST ? kLdsPointCapFirst : kLdsPointCap;      // (iteration 0 has no search list: its LDS goes to the points)
+  __shared__ float4 s_pts[kPointCap];
   __shared__ uint32_t s_roff[kLdsRowCap + 1];
   __shared__ uint32_t s_occ[kLdsRowCap / 32 + 1];   // bit r = staged row r of the box holds target points (+ one word so that two can always be read)
   __shared__ uint32_t s_w[17];
@@ -1222,7 +1292,9 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
       {   // which rows of the box hold a point at all: most (z, y) rows around a surface do not, and a query's row loop pays
           // ~50 vector instructions per row whether the row has candidates or not (kLdsRowCap = blockDim: thread r owns row r)
         const unsigned long long om = __ballot(len > 0);
-        if (lane == 0) { s_occ[2 * (threadIdx.x >> 6)] = (uint32_t)om; s_occ[2 * (threadIdx.x >> 6) + 1] = (uint32_t)(om >> 32); }
+        // (the index from the wave's number in an SGPR: two per-lane LDS addresses kept across the rounds were what iteration 0's
+        // instantiation spilled to scratch at 80 VGPRs)
+        if (lane == 0) { const int w2 = 2 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); s_occ[w2] = (uint32_t)om; s_occ[w2 + 1] = (uint32_t)(om >> 32); }
         if (threadIdx.x == 0) s_occ[kLdsRowCap / 32] = 0u;
       }
       uint32_t total;
@@ -1230,7 +1302,7 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
       if ((int)threadIdx.x < rows) s_roff[threadIdx.x] = off;
       if (threadIdx.x == 0) s_roff[rows] = total;
       __syncthreads();
-      pts_lds = total <= (uint32_t)kLdsPointCap;
+      pts_lds = total <= (uint32_t)kPointCap;
       if (pts_lds) {
         for (uint32_t k = threadIdx.x; k < total; k += kNnThreads) {
           int lo = 0, hi = rows - 1;                               // last row with roff <= k
@@ -1254,8 +1326,10 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
         // any are visited (s_occ): around a surface most rows of a ball are empty, and a row costs ~50 vector instructions before
         // its first candidate whether it has one or not.  (A block spans at most 31 rows in y: the search radius is capped at 14
         // cells, sync_options.)
-        const uint32_t ymask = (2u << (y1 - y0)) - 1u;
-        for (int z = z0; z <= z1; ++z) {
+        // (a round whose box misses the table cap -- block-uniform -- looks every row up in global memory, four rows at a time)
+        if (!use_lds) sweep_rows_global(words, cstart, tq, ny, wx, oy, oz, h, slack, x0, x1, y0, y1, z0, z1, qx, qy, qz, R2, best);
+        else for (int z = z0; z <= z1; ++z) {
+          const uint32_t ymask = (2u << (y1 - y0)) - 1u;
           const float zl = oz + (float)z * h;
           const float dz = fmaxf(fmaxf(zl - qz, qz - (zl + h)) - slack, 0.f);
           const int ra = (z - Z0) * nyl + (y0 - Y0);                 // staged row of (z, y0) (LDS paths)
@@ -1277,13 +1351,9 @@ __device__ __forceinline__ void ball_lds_rounds(const IcpDev& b, PairState* st, 
                 const float4 t = *tp;
                 test_ascending_ru(t, __float_as_int(t.w), qx, qy, qz, best);
               }
-            } else if (use_lds) {
+            } else {
               const int rb = (ra + bpos) * nxl - X0;
               sweep_run(tq, s_tab[rb + x0], s_tab[rb + x1 + 1], qx, qy, qz, best);
-            } else {
-              uint32_t sb, se;
-              row_slots(words, (z * ny + y) * wx, x0, x1, sb, se);
-              if (se > sb) sweep_run(tq, cstart[sb], cstart[se], qx, qy, qz, best);
             }
           }
         }
@@ -1390,10 +1460,16 @@ __device__ __forceinline__ void flush_min_lb_and_hist(const IcpDev& b, PairState
   flush_hist(b, pair, s_hist);
 }
 
+// (Iteration 0's instantiation is held to six waves per SIMD, 80 VGPRs -- its 25.2 KiB of LDS allow six workgroups per CU -- since
+// with the bound of five the compiler spends up to 96 on it and the sixth wave is worth more than the registers: measured with the
+// four-row walk, 88 VGPRs at five waves ran slower than the parent's walk.  The others are held to five by their LDS.)
 template <int ITEMS, bool FIRST = false>
-__global__ __launch_bounds__(kNnThreads, 5) void nn_ball_lds(IcpDev b, int nblk) {
+__global__ __launch_bounds__(kNnThreads, FIRST ? 6 : 5) void nn_ball_lds(IcpDev b, int nblk) {
   int pair, blk;
   if (!xcd_block(nblk, b.npairs, b.pair_base, pair, blk)) return;
+  // (xcd_block divides by nblk on the vector unit: told that the two are uniform, the compiler keeps the pair's array bases in SGPRs
+  // and not in six VGPRs a lane, which iteration 0's instantiation does not have to spare)
+  pair = __builtin_amdgcn_readfirstlane(pair); blk = __builtin_amdgcn_readfirstlane(blk);
   PairState* st = &b.state[pair];
   if (st->done) return;
   const int base0 = blk * (kNnThreads * ITEMS);

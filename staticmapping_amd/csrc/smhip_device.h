@@ -30,6 +30,7 @@ constexpr int kBruteTile = 1024;         // target points staged in LDS per tile
 constexpr int kFallbackSlices = 64;      // target slices the fallback sweep is spread over
 constexpr int kLdsTableCap = 1024;        // u32 entries of the per-workgroup row table in nn_ball_lds (4 KiB)
 constexpr int kLdsPointCap = 512;         // target points staged per round (8 KiB)
+constexpr int kLdsPointCapFirst = 768;    // ... in iteration 0's instantiation, which has no search list (12 KiB: 25.2 KiB in all, six workgroups per CU need <= 26.6)
 constexpr int kLdsRowCap = 256;           // grid rows of the box whose runs are staged (<= workgroup size)
 constexpr int kWideBlocks = 512;         // workgroups (4 waves = 4 queries at a time) per pair of nn_ring_wide
 constexpr int kNaboAccBlocks = 8;         // workgroups per pair of accumulate_listed (reference-search mode, fused path)
